@@ -2,7 +2,7 @@
 """Benchmark of the k-diffusion sampling hot path on MI355X (contract: see the task statement).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
-    python bench.py --gpus N --steps K --warmup W          (starts its own ranks: re-executes itself under the launcher below)
+    python bench.py --gpus N --steps K --warmup W          (starts its own ranks: runs itself under the launcher below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -16,7 +16,8 @@ OUTPUT (round 6).  Rank 0 prints ONE compact JSON line (< 4 KiB, the LAST line o
 quiet) with the contract's keys -- metric / value / unit / n_gpus / steps / warmup / ms_per_step / dtype / config / roofline /
 cpu_baseline -- plus ``parity`` (distance of this build on this box to the reference's 50-step batch-32 golden of this workload),
 ``mode_values`` and ``detail_file``.  Everything longer (per-mode entries with their per-family rooflines, and the opt-in blocks) goes to
-``bench_detail.json`` (``--detail-file``).
+``bench_detail.json`` (``--detail-file``).  ``--dump-outputs DIR`` writes what the last timed step computed (the finished images, and the
+gathered ones when the exchange step ran) as ``DIR/<name>.npy``: inputs and weights are seeded, so two builds compare output for output.
 
 Arithmetic mode (``--mode``, default split3): ``value`` / ``dtype`` / ``roofline`` belong to that mode.  The default is the
 fp32-PARITY mode -- the reference samples in fp32 (sample.py:39-47, no mixed precision) and north_star asks for images within
@@ -85,6 +86,9 @@ def parse(argv=None):
     p.add_argument("--no-kernel-events", action="store_true", help="do not record per-launch HIP events in the extra pass behind the timed region")
     p.add_argument("--kernel-table", default=None, help="write the per-kernel event timings to this JSON file")
     p.add_argument("--no-parity", action="store_true", help="skip the golden-vector parity block (the 50-step batch-32 golden of this workload per measured mode)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all; a fixed "
+                        "seeded sample of images when an output is larger): two builds run with the same arguments compare output for output")
     p.add_argument("--backend", default=None, choices=["nccl", "gloo"], help="process-group backend (default: nccl = RCCL on a GPU box; gloo is for the "
                                                                               "launcher's CPU test together with --stub-workload)")
     p.add_argument("--force-collectives", action="store_true",
@@ -95,6 +99,8 @@ def parse(argv=None):
     for gone in ("--no-other-configs", "--no-power", "--no-small-batch", "--no-job"):     # rounds 2 - 5: these blocks were on by default; the command
         p.add_argument(gone, action="store_true", help=argparse.SUPPRESS)                 # lists of benchmarks/profile_round*.sh still name the flags
     args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
     if args.detail:
         args.other_configs = args.small_batch = args.job = True
     if args.modes is None:
@@ -664,11 +670,42 @@ def claim_stdout():
         os.dup2(2, 1)
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all arrays together
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each (name, tensor) of ``arrays``, in order, as ``out_dir/<name>.npy`` in float32.  An array that does not fit in
+    what is left of DUMP_LIMIT_BYTES keeps a fixed seeded sample of its rows along dim 0 (the images), in index order, and the chosen row
+    indices go to ``out_dir/<name>_rows.npy`` (float64).  The directory gets a ``.gitignore`` of ``*``.  Returns {name: shape written} for the detail file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if not os.path.exists(os.path.join(out_dir, ".gitignore")):        # a dump inside a work tree stays out of `git status`
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:
+            f.write("*\n")
+    left, written = DUMP_LIMIT_BYTES, {}
+    for name, t in arrays:
+        a = t.detach().float().cpu().contiguous().numpy()
+        row_bytes = a[:1].nbytes or 4
+        if a.nbytes > left:
+            keep = max(0, (left - 8 * a.shape[0]) // row_bytes)
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], size=min(keep, a.shape[0]), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            left -= rows.size * 8
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
+
+
 def launch_ranks(args):
-    """``python bench.py --gpus N`` typed plainly (no WORLD_SIZE in the environment): replace this process by the launcher the contract
-    names -- ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same
-    arguments>`` -- which starts one rank per GPU; rank 0 of that run prints the JSON line.  The port is a free one asked of the kernel."""
+    """``python bench.py --gpus N`` typed plainly (no WORLD_SIZE in the environment): run the launcher the contract names -- ``python -m
+    torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same arguments>`` -- as a child
+    process that inherits stdout / stderr, and exit with its status; it starts one rank per GPU, and rank 0 of that run prints the JSON
+    line.  The port is a free one asked of the kernel."""
     import socket
+    import subprocess
     with socket.socket() as sock:
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
@@ -677,7 +714,8 @@ def launch_ranks(args):
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.run(cmd).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 def stub_line(args, ctx):
@@ -715,7 +753,7 @@ def stub_line(args, ctx):
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        launch_ranks(args)                         # does not return
+        launch_ranks(args)                         # does not return: exits with the launcher's status
     claim_stdout()
     os.environ["KDIFF_GEMM"] = args.mode
     if args.stub_workload:
@@ -769,6 +807,10 @@ def main():
     if gather_events:
         g = last_gathered[0]
         assert g.shape[0] == args.gpus * B and (g.dtype == torch.uint8) == (args.gather == "uint8")
+    dumped = None
+    if args.dump_outputs and ctx.is_main_process:
+        # the last timed step's results: this rank's finished fp32 images, and -- when the exchange step ran -- the gathered images of all ranks
+        dumped = dump_outputs(args.dump_outputs, [("images", out)] + ([("gathered", last_gathered[0])] if gather_events else []))
 
     if ctx.is_main_process:
         n_img = args.gpus * B * args.steps
@@ -802,6 +844,8 @@ def main():
             "algorithmic_tflops": round(n_img * 2 * mac * (nfe or 0) / dt / 1e12, 2) if nfe else None,
             "roofline": head.get("roofline", {"bound": "hbm", "achieved": 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": 0.0, "traffic": None}),
         }
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if args.gpus == 1 and not args.no_other_modes:
             # the other arithmetic modes of the same build on the same box: same --steps / --warmup, own event pass, own roofline
             result["modes"] = {args.mode: {k: v for k, v in head.items() if k != "roofline"}}

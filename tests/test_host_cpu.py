@@ -401,6 +401,9 @@ def test_shard_range_covers_everything(KD):
 _WORKER = r"""
 import os, sys, torch
 sys.path.insert(0, {repo!r})
+# a CPU-only gloo rank: dist.barrier() asks torch for the machine's accelerator first, and asking opens the GPU device on a GPU
+# machine (up to 8 ranks at once here); the answer for this rank is the CPU
+torch._C._get_accelerator = lambda: torch.device("cpu")
 import k_diffusion_amd as K
 ctx = K.distributed.RankContext(device="cpu", backend="gloo")
 assert ctx.num_processes == 2
@@ -423,6 +426,9 @@ ctx.shutdown()
 _WORKER_INDEXED = r"""
 import os, sys, torch
 sys.path.insert(0, {repo!r})
+# a CPU-only gloo rank: dist.barrier() asks torch for the machine's accelerator first, and asking opens the GPU device on a GPU
+# machine (up to 8 ranks at once here); the answer for this rank is the CPU
+torch._C._get_accelerator = lambda: torch.device("cpu")
 import k_diffusion_amd as K
 import sample
 ctx = K.distributed.RankContext(device="cpu", backend="gloo")
@@ -546,21 +552,14 @@ def test_oracle_brownian_tree_stands_in_for_torchsde():
     assert torch.equal(ob.OracleBrownianTree(0.01, w0, 160.0, entropy=1234)(1.0, 2.0), ab)
     assert not torch.equal(ob.OracleBrownianTree(0.01, w0, 160.0, entropy=1235)(1.0, 2.0), ab)
     assert torch.equal(tree(2.0, 1.0), -ab)
-    if ob_ref_available():
-        from oracle import ref_import
-        K = ref_import.load()
-        K.sampling.torchsde.BrownianTree = ob.OracleBrownianTree
-        x = torch.zeros(2, 3, 8, 8)
-        ns = K.sampling.BrownianTreeNoiseSampler(x, 0.01, 160.0, seed=[7, 8])            # the reference's own class
-        n = ns(torch.tensor(4.0), torch.tensor(1.0))                                      # descending sigmas, as the samplers ask
-        inc = ob.brownian_increment([7, 8], 192, 0.01, 160.0, 1.0, 4.0)
-        want = -torch.from_numpy(inc).view(2, 3, 8, 8) / (torch.tensor(1.0) - torch.tensor(4.0)).abs().sqrt()
-        assert torch.allclose(n, want, atol=1e-4)          # (the reference hands the tree fp32 end points: 0.01 -> 0.0099999998)
-
-
-def ob_ref_available():
-    from oracle import ref_import
-    return ref_import.available()
+    # the reference's own BrownianTreeNoiseSampler over this tree (seeds [7, 8], 2 x 3 x 8 x 8, sigmas 4 -> 1, descending as the samplers
+    # ask), recorded by oracle/make_golden_brownian.py
+    from safetensors.torch import load_file
+    from tests.golden import cases
+    n = load_file(os.path.join(cases.GOLDEN_DIR, "brownian_sampler.safetensors"))["noise"]
+    inc = ob.brownian_increment([7, 8], 192, 0.01, 160.0, 1.0, 4.0)
+    want = -torch.from_numpy(inc).view(2, 3, 8, 8) / (torch.tensor(1.0) - torch.tensor(4.0)).abs().sqrt()
+    assert torch.allclose(n, want, atol=1e-4)              # (the reference hands the tree fp32 end points: 0.01 -> 0.0099999998)
 
 
 def test_run_list_entries_are_packed_by_the_rule_the_library_unpacks_by():
@@ -862,6 +861,32 @@ def _load_bench():
     finally:
         sys.argv = argv
     return mod
+
+
+def test_bench_dump_outputs_writes_float32_within_the_budget(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float32; one that does not fit in what is left of the 64 MB keeps a seeded
+    sample of whole images (the same rows every run, listed in <name>_rows.npy); the total stays inside the budget.  --steps below 1 is refused."""
+    import numpy as np
+    bench = _load_bench()
+    imgs = torch.randn(32, 3, 256, 256)                                     # the headline's 25 MB of fp32 images
+    gathered = torch.randint(0, 256, (256, 3, 256, 256), dtype=torch.uint8)  # an 8-rank uint8 gather: 201 MB as float32
+    for run in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / run), [("images", imgs), ("gathered", gathered)])
+        assert shapes["images"] == [32, 3, 256, 256] and 0 < shapes["gathered"][0] < 256
+    files = sorted(f for f in os.listdir(tmp_path / "a") if f != ".gitignore")              # (the dump directory ignores itself)
+    assert files == ["gathered.npy", "gathered_rows.npy", "images.npy"]
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(np.load(tmp_path / "a" / "images.npy"), imgs.numpy())
+    rows = np.load(tmp_path / "a" / "gathered_rows.npy").astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(np.load(tmp_path / "a" / "gathered.npy"), gathered[rows].float().numpy())
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    assert bench.parse(["--steps", "7", "--warmup", "0"]).steps == 7
 
 
 def test_bench_global_attention_block_figure_from_a_recorded_kernel_table(KD):
