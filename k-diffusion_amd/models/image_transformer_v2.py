@@ -30,7 +30,7 @@ import weakref
 import os
 import math
 from dataclasses import dataclass
-from typing import Union
+from typing import Optional, Union
 
 import torch
 from torch import nn
@@ -44,8 +44,8 @@ D_HEAD = 64
 SCHEDULE_TABLE_MAX_BYTES = 1 << 30
 SCHEDULES_KEPT = 4            # a run of a two-stage solver hints two tables; older records (and their tensors) are dropped
 SCHEDULE_CHAINS_KEPT = 2      # conditioning workspaces kept per plan, by schedule length (least recently used dropped)
-# environment switches read while a plan is built (name, default): part of the plan key
 MAX_PLANS = 16     # cached launch plans (one per batch / size / conditioning kinds / device / arithmetic mode / switches) per model: least recently used beyond that
+# environment switches of the kernel routing (name, default): read in _plan_for, part of the plan key, passed to route_layer
 PLAN_SWITCHES = (("KDIFF_ATTN_BLOCK", "1"), ("KDIFF_PROJ_BLOCK", "1"), ("KDIFF_FFN_OUT", "all"), ("KDIFF_RUN_LIST", "1"))
 CLASS_IDS_KEPT = 4            # range-checked class_cond tensors remembered per plan (cond / uncond pairs of a guidance wrapper)
 
@@ -145,14 +145,138 @@ def _rms_scale(n):
     return _Holder(scale=nn.Parameter(torch.ones(n)))
 
 
+# ---------------------------------------------------------------------------------- kernel routing
+
+_ATTN_KIND = {GlobalAttentionSpec: "global", NeighborhoodAttentionSpec: "neighborhood", ShiftedWindowAttentionSpec: "shifted-window"}
+_CORE = {"global": "attn_global", "neighborhood": "attn_na2d", "shifted-window": "attn_window"}
+
+
+@dataclass(frozen=True)
+class LayerRoute:
+    """The kernels of one layer (``route_layer``).  qkv: "attn_block" (projection + attention core in one launch), "proj_block",
+    "mx8", "split" (kd_norm_split_f32 planes, then the GEMM), "plain" or None (no attention); core: the attention core's entry point
+    (None: none, or inside the attention block); fuse_out: the out projection runs inside the FF kernel; ff: "kd_ffn_f32" /
+    "kd_ffn_bf16" (one kernel) or "pair", whose up projection is routed like qkv (``up``) and whose down projection may be fp8."""
+    qkv: Optional[str]
+    core: Optional[str]
+    fuse_out: bool
+    ff: str
+    up: Optional[str] = None
+    down_mx8: bool = False
+
+
+def _prepass(mode, width):
+    """split3: widths the fused norm -> projection kernel (gemm_x3.hip) does not take (tiles of 128 features): their normalised rows
+    travel as bf16 planes of their own (kd_norm_split_f32)."""
+    return mode == nat.PREC_SPLIT3 and width not in (128, 256, 512) and width > 256 and width % 128 == 0 and width <= 2048
+
+
+def _mx8_ok(lib, mode, M, N, K, epi):
+    """fp8 mode: this norm -> projection goes to the block-scaled fp8 matrix instruction (kd_gemm_mx8)."""
+    # (from 4 096 rows on -- library option mx8_min_rows: below that the few-rows bf16 kernels are ahead -- batch 1: 0.512 against 0.552 ms
+    # per forward, profiles/r06_bench_detail_full.json)
+    return mode == nat.PREC_FP8 and M >= lib.kd_get_option(b"mx8_min_rows", 4096) and bool(lib.kd_gemm_mx8_supported(M, N, K, epi, 1))
+
+
+def route_layer(lib, mode, B, T, rps, d, d_ff, nh, attn, switches):
+    """The kernels of a layer of width ``d`` over ``T`` = B x ``rps`` tokens in arithmetic mode ``mode`` (nat.PREC_*, PREC_FP8 included):
+    ``attn`` is "global" / "neighborhood" / "shifted-window", or None for a layer without attention (``nh`` heads); ``switches`` maps
+    the names of PLAN_SWITCHES to the plan's values.  Asks only host-side predicates of the library (``lib``): no tensors, no device."""
+    bf = mode in (nat.PREC_BF16, nat.PREC_FP8)
+    proj_block = bf and switches["KDIFF_PROJ_BLOCK"] != "0"
+    ffn_x3 = mode == nat.PREC_SPLIT3 and bool(lib.kd_ffn_f32_supported(T, d, d_ff))      # (library option ffn_x3)
+    ffn_bf = bf and bool(lib.kd_ffn_bf16_supported(T, d, d_ff))
+    # out projection fused into the FF kernel: width 128 (+3.5 % images/s in round 3) and, since round 5, width 256 too: in round 3
+    # that measured level (176.1 vs 176.0: one wave per SIMD there); with the round-4 / 5 kernels around it the removed launch + the
+    # attention rows' HBM round trip are worth +1.5 .. +3.0 % on two boxes (same box, back to back: 207.9 / 207.9 / 208.7 vs 214.3;
+    # 186.9 / 186.9 / 187.0 vs 189.4 / 190.0).  KDIFF_FFN_OUT: 0 never, 1 = width 128 only, all (default) = every width the kernel
+    # takes, or ONE width
+    fo = switches["KDIFF_FFN_OUT"]
+    fuse_out = attn is not None and ((ffn_x3 and d in (128, 256)) or (ffn_bf and d == 128)) and (d == 128 if fo == "1" else fo in ("all", str(d)))
+    qkv = core = None
+    if attn is not None:
+        # bf16 mode, global attention at 256 tokens per sample: norm -> qkv projection of a head -> cosine-sim + RoPE -> attention in
+        # ONE launch per layer (csrc/block_bf16.hip: attn_block_bf16_kernel; q, k, v never reach HBM).  The descriptor is the qkv
+        # projection's, its C the attention output
+        # From 32 (sample, head) workgroups on: below that (batch 1 - 2 at level 2) the few-rows projection + the dense core are faster
+        # (0.514 against 0.543 ms per forward at batch 1; from batch 4 on the one-launch form wins: profiles/r05_attn_block.md)
+        # fp8 mode: the qkv projection on the fp8 matrix instruction -- except where the one-launch bf16 attention block takes the layer
+        # (level 2 of the 256 x 256 configs: 25.5 us against 25.6 + 13.6 us for fp8 projection + dense core, profiles/r06_fp8_mode.md)
+        if bf and attn == "global" and T % 256 == 0 and switches["KDIFF_ATTN_BLOCK"] != "0" and lib.kd_attn_block_bf16_supported(rps, d, nh) \
+                and (B * nh >= 32 or switches["KDIFF_ATTN_BLOCK"] == "force"):
+            qkv = "attn_block"
+        elif _prepass(mode, d) and nh <= 16:
+            # AdaRMSNorm -> planes once, then a GEMM whose two operands both move by LDS-DMA
+            # (the tiled qkv epilogue keeps its per-head constants in a 16-head LDS table, csrc/gemm_x3t.hip: wider levels -- 1152 =
+            # 18 heads and up -- take the fp32-A norm -> projection kernels of round 1 like every shape the fused kernels refuse)
+            qkv = "split"
+        elif _mx8_ok(lib, mode, T, 3 * d, d, nat.EPI_QKV):
+            qkv = "mx8"
+        elif proj_block and lib.kd_proj_block_bf16_supported(rps, d, 3 * d, nat.EPI_QKV) and 192 <= (T // 256) * (3 * d // 384) <= 256:
+            # bf16 mode, K = 256 / 512 with an attention core of its own (neighbourhood / window levels): the projection in the block
+            # form (kd_proj_block_bf16: a workgroup per (256-row group, 6 head vectors), rows normalised once) for one-round grids (192 .. 256)
+            qkv = "proj_block"
+        else:
+            qkv = "plain"
+        if qkv != "attn_block":
+            core = f"kd_{_CORE[attn]}_{'bf16' if bf else 'f32'}"
+    if ffn_x3 or ffn_bf:
+        # the whole FeedForwardBlock (:487-493) in one kernel (csrc/ffn_x3.hip, csrc/ffn_bf16.hip): the d_ff-wide hidden activation stays
+        # on the chip
+        return LayerRoute(qkv, core, fuse_out, "kd_ffn_f32" if ffn_x3 else "kd_ffn_bf16")
+    if _prepass(mode, d) and d_ff % 64 == 0:
+        return LayerRoute(qkv, core, fuse_out, "pair", "split")
+    # fp8 mode: the hidden activation leaves the GEGLU epilogue as e4m3 rows + one power-of-two scale per (row, 32 features) -- in
+    # the first half of `hid`, the scale bytes behind them -- and the down projection takes both operands as e4m3 by LDS-DMA
+    up_mx8 = _mx8_ok(lib, mode, T, d_ff, d, nat.EPI_GEGLU)
+    down_mx8 = up_mx8 and d_ff % 128 == 0 and bool(lib.kd_gemm_mx8_supported(T, d, d_ff, nat.EPI_RESIDUAL, 0))
+    if up_mx8:
+        up = "mx8"
+    elif proj_block and lib.kd_proj_block_bf16_supported(rps, d, d_ff, nat.EPI_GEGLU) and 192 <= (T // 256) * (d_ff // 192) <= 256:
+        # bf16 mode, rows per sample a multiple of 256: the projection in the attention block's form (a workgroup per (256-row group,
+        # 192-output slice), rows normalised once; csrc/block_bf16.hip: proj_block_bf16_kernel) for grids that fill ONE round of the
+        # chip's 256 CUs (192 .. 256 workgroups): two rounds measured level with the A-stationary kernel (42.3 against 41.5 us at
+        # level 1), and a workgroup's six passes are a serial chain -- at 32 - 128 workgroups the A-stationary kernel, which splits
+        # the same work over up to 512 slots, is faster (batch 4: 0.645 against 0.759 ms per forward; batch 16: level); same bits
+        up = "proj_block"
+    else:
+        up = "plain"
+    return LayerRoute(qkv, core, fuse_out, "pair", up, down_mx8)
+
+
 # ---------------------------------------------------------------------------------- the plan
 
 class _Launch:
-    __slots__ = ("fn", "args", "what", "enc")
+    """One launch: entry point, its arguments without the stream (nat.encode_call's form), a name for error messages."""
+    __slots__ = ("name", "args", "what")
 
-    def __init__(self, fn, args, what, enc=None):
-        # enc: (entry point name, its arguments without the stream) for a kd_run_list entry; None = only callable from Python
-        self.fn, self.args, self.what, self.enc = fn, args, what, enc
+    def __init__(self, name, args, what):
+        self.name, self.args, self.what = name, args, what
+
+    def __call__(self, lib, stream):
+        """Issue it directly: descriptors by reference, a patched pointer (_ScaleRef) as it is now."""
+        return getattr(lib, self.name)(*[C.byref(a) if isinstance(a, C.Structure) else a.scale if isinstance(a, _ScaleRef) else a
+                                         for a in self.args], stream)
+
+
+class _ScaleRef:
+    """A scale-table address passed as a plain argument (kd_norm_split_f32), patched per run like ``_Plan.norm_descs``' descriptors."""
+
+    def __init__(self):
+        self._scale, self._call, self._index = None, None, 0
+
+    def bind_call(self, call, index):               # (nat.encode_call: this pointer lives in a kd_run_list entry too)
+        self._call, self._index = call, index
+
+    @property
+    def scale(self):
+        return self._scale
+
+    @scale.setter
+    def scale(self, v):
+        self._scale = v
+        if self._call is not None:
+            self._call.p[self._index] = v
 
 
 def _ptr(t):
@@ -164,8 +288,8 @@ class _CondChain:
     Every kernel of the chain works row by row (the products go through the per-row fp32 FMA kernel, KdGemm.per_row), so
     a row's scales do not depend on how many rows share the launches: B rows per solver step or steps x B rows at once."""
 
-    def __init__(self, rows):
-        self.rows, self.launches, self.keep = rows, [], []
+    def __init__(self, rows, lib):
+        self.rows, self.lib, self.launches, self.keep = rows, lib, [], []
         self.c_sigma = self.class_ids = self.aug_in = self.map_in = self.d_scales = None
 
     def fill(self, sigma, aug_cond, class_cond, mapping_cond, repeat=1):
@@ -185,7 +309,7 @@ class _CondChain:
         """Scales of every AdaRMSNorm of the network for every row -> [rows, scale_width] fp32 at ``table_ptr``."""
         self.d_scales.C = table_ptr
         for ln in self.launches:
-            rc = ln.fn(*ln.args, stream)
+            rc = ln(self.lib, stream)
             if rc:
                 nat.check(rc, ln.what)
 
@@ -219,23 +343,24 @@ class _Plan:
         The callers (eviction, ``_drop_plans``: rare events) run the collector once behind this for the helper objects' own cycles."""
         self.__dict__.clear()
 
-    def __init__(self, model, B, H, W, has_aug, has_class, has_mapping_cond, device):
-        lib = nat.lib()
-        m = model
-        precision = nat.default_precision()
+    def __init__(self, model, B, H, W, has_aug, has_class, has_mapping_cond, device, mode, switches):
+        """``mode``: the arithmetic mode (nat.PREC_*); ``switches``: the values of PLAN_SWITCHES by name (both from the plan key)."""
+        self.lib = nat.lib()
+        m = self.model = model
+        self.mode, self.switches = mode, switches
         # fp8 mode: the bf16 plan with the norm -> qkv / norm -> GEGLU projections of the K = 256 / 512 levels on the fp8 matrix instruction
-        fp8 = precision == nat.PREC_FP8
-        precision = nat.PREC_BF16 if fp8 else precision
+        self.precision = precision = nat.PREC_BF16 if mode == nat.PREC_FP8 else mode
         bf = precision == nat.PREC_BF16
-        cond_precision = nat.PREC_SPLIT3 if bf else precision      # the per-sample conditioning chain stays fp32 in every mode
-        self.keep = []           # descriptors and tensors that must outlive the plan
+        self.cond_precision = nat.PREC_SPLIT3 if bf else precision      # the per-sample conditioning chain stays fp32 in every mode
+        self.has_aug, self.has_class, self.has_mapping_cond, self.device = has_aug, has_class, has_mapping_cond, device
+        self.keep = []           # tensors that must outlive the plan (descriptors live in the launches)
         self.launches = []
         f32 = dict(device=device, dtype=torch.float32)
         act = dict(device=device, dtype=torch.bfloat16 if bf else torch.float32)   # residual stream, qkv, attention out, FF hidden
         ph, pw = m.patch_size
         if H % ph or W % pw:
             raise ValueError(f"input {H}x{W} not divisible by the patch size {ph}x{pw}")
-        levels = m.level_specs
+        levels = self.levels = m.level_specs
         n_lv = len(levels)
         grids = [(H // ph, W // pw)]
         for _ in range(n_lv - 1):
@@ -246,349 +371,210 @@ class _Plan:
         self.B, self.grids = B, grids
         self.out_shape = (B, m.out_channels, H, W)
         self.class_checked = {}                             # identities of the range-checked class_cond tensors (_plan_for) -> the tensor
-        mw, mdff = m.mapping_spec.width, m.mapping_spec.d_ff
 
         # ---- static buffers -----------------------------------------------------------------
         self.sigma = torch.empty(B, **f32)                  # preconditioning sigmas of the MAIN chain when the caller's cannot be read in place
         self.sigma_ptr = self.sigma.data_ptr()
-        xs = [torch.empty(B, gh, gw, lv.width, **act) for (gh, gw), lv in zip(grids, levels)]
-        toks = [B * gh * gw for gh, gw in grids]
-        qkv = torch.empty(max(t * 3 * lv.width for t, lv in zip(toks, levels)), **act)
-        att = torch.empty(max(t * lv.width for t, lv in zip(toks, levels)), **act)
-        hid = torch.empty(max(t * lv.d_ff for t, lv in zip(toks, levels)), **act)
+        self.xs = xs = [torch.empty(B, gh, gw, lv.width, **act) for (gh, gw), lv in zip(grids, levels)]
+        self.toks = toks = [B * gh * gw for gh, gw in grids]
+        self.qkv = torch.empty(max(t * 3 * lv.width for t, lv in zip(toks, levels)), **act)
+        self.att = torch.empty(max(t * lv.width for t, lv in zip(toks, levels)), **act)
+        self.hid = torch.empty(max(t * lv.d_ff for t, lv in zip(toks, levels)), **act)
         # fp32-parity mode, round 3: GEMM operands that a producer can split once travel as two bf16 planes (hi, lo: the same bytes as
         # fp32) and the consumer GEMM moves them by LDS-DMA (csrc/gemm_x3t.hip).  Planes of the FF hidden activation live in `hid`
         # (hi in its first half, lo in the second); the normalised rows of the levels whose width exceeds the fused norm -> projection
         # kernel's register budget (> 256) get planes of their own (`xn`, written by kd_norm_split_f32).
-        planes = precision == nat.PREC_SPLIT3
-        def prepass(width):                                  # widths the fused norm -> projection kernel (gemm_x3.hip) does not take
-            return planes and width not in (128, 256, 512) and width > 256 and width % 128 == 0 and width <= 2048    # (tiles of 128 features)
-        wide = [t * lv.width for t, lv in zip(toks, levels) if prepass(lv.width)]
-        xn = torch.empty(max(wide), **f32) if wide else None
-        self.keep.append(xn)
+        wide = [t * lv.width for t, lv in zip(toks, levels) if _prepass(mode, lv.width)]
+        self.xn = torch.empty(max(wide), **f32) if wide else None
         norm_mods = m._ada_norm_modules()
-        offsets, total = {}, 0
+        self.table_offsets, total = {}, 0                  # byte offset of each AdaRMSNorm's scales in a scale table row
         for name, mod in norm_mods:
-            offsets[name] = total
+            self.table_offsets[name] = 4 * total
             total += mod.linear.weight.shape[0]
         # one concatenation of the AdaRMSNorm projections per MODEL, not per plan: it is a function of the weights only, and the packed-image
         # cache keeps its source alive -- made per plan, every batch size ever seen left 2 x 7.5 MB behind (256 x 256 configs) until the
         # weights changed.  (model._packed goes with the plans whenever the weights do.)
-        wcat_ent = m._packed.get("ada_norm_wcat")
-        if wcat_ent is None or wcat_ent.device != device:
-            wcat_ent = m._packed["ada_norm_wcat"] = torch.cat([mod.linear.weight.detach() for _, mod in norm_mods], dim=0).contiguous()
-        wcat = wcat_ent
+        wcat = m._packed.get("ada_norm_wcat")
+        if wcat is None or wcat.device != device:
+            wcat = m._packed["ada_norm_wcat"] = torch.cat([mod.linear.weight.detach() for _, mod in norm_mods], dim=0).contiguous()
+        self.wcat = wcat
         # AdaRMSNorm scale tables, ping-pong: the main chain reads one while the next step's table is being written
         self.scales = [torch.empty(B, total, **f32), torch.empty(B, total, **f32)]
-        self.norm_descs = []                                # (descriptor, byte offset into a scale table)
+        self.norm_descs = []                                # (descriptor or _ScaleRef, byte offset into a scale table)
         self.last_buf, self.prefetched = 1, None            # prefetched: (identity of the conditioning tensors, table, done event)
         self.side_stream = torch.cuda.Stream(device=device)
         self.main_entry = torch.cuda.Event()
         self.schedules, self.schedule_chains = [], {}       # conditioning of whole sigma schedules (prefetch_schedule); chains by length
-        self.keep += [xs, qkv, att, hid, wcat]
-        self.xs = xs
-
-        def gemm(what, A, Wt, Cc, M, N, K, a_mode=nat.A_PLAIN, epi=nat.EPI_STORE, scale_ptr=None, scale_stride=0,
-                 rows_per_sample=0, R=None, grid=(0, 0), patch=(0, 0, 0), out_add=0.0, sigma=None, fac=None, qk=None,
-                 a_planes=None, c_planes=None, mx8=False):
-            d = nat.KdGemm()
-            d.M, d.N, d.K, d.a_mode, d.epi = M, N, K, a_mode, epi
-            main = target is self.launches
-            d.precision = precision if main else cond_precision
-            d.per_row = 0 if main else 1                    # conditioning products: one row per sample, see _CondChain
-            if mx8:
-                d.Wp = m._packed_image(Wt, N, K, epi == nat.EPI_GEGLU, bf16="mx8").data_ptr()
-            elif d.precision == nat.PREC_BF16:
-                d.Wp = m._packed_image(Wt, N, K, epi == nat.EPI_GEGLU, bf16=True).data_ptr()
-            elif d.precision == nat.PREC_SPLIT3:
-                d.Wp = m._packed_image(Wt, N, K, epi == nat.EPI_GEGLU).data_ptr()
-            d.norm = 1 if scale_ptr is not None else 0
-            d.rows_per_sample, d.scale_stride = rows_per_sample, scale_stride
-            d.gh, d.gw = grid
-            d.ph, d.pw, d.chan = patch
-            d.eps, d.out_add, d.sigma_data = 1e-6, out_add, 1.0
-            d.A = None if A is None else A.data_ptr()
-            d.W, d.C = Wt.data_ptr(), (None if Cc is None else Cc.data_ptr())
-            if a_planes is not None:                        # (hi address, lo address): pre-split bf16 planes instead of fp32 A
-                d.a_split, d.A, d.A_lo = 1, a_planes[0], a_planes[1]
-            if c_planes is not None:
-                d.c_split, d.C, d.C_lo = 1, c_planes[0], c_planes[1]
-            d.R = None if R is None else R.data_ptr()
-            d.scale = scale_ptr if not isinstance(scale_ptr, tuple) else None
-            if isinstance(scale_ptr, tuple):                # ("table", byte offset): patched per run to the live scale table
-                self.norm_descs.append((d, scale_ptr[1]))
-            d.sigma = None if sigma is None else sigma.data_ptr()
-            d.fac = None if fac is None else fac.data_ptr()
-            if qk is not None and d.precision == nat.PREC_BF16:      # (scale_h, rope_pos, rope_freq, nh)
-                d.qk_scale, d.rope_pos, d.rope_freq, d.n_heads = qk[0].data_ptr(), qk[1].data_ptr(), qk[2].data_ptr(), qk[3]
-            elif qk is not None:
-                d.qk_scale, d.rope_cos, d.rope_sin, d.n_heads = qk[0].data_ptr(), qk[1].data_ptr(), qk[2].data_ptr(), qk[3]
-                if len(qk) >= 6:                                     # split3: positions / frequencies for the round-3 kernels (gemm_x3*.hip)
-                    d.rope_pos, d.rope_freq = qk[4].data_ptr(), qk[5].data_ptr()
-            (self.keep if main else chain.keep).append(d)
-            name = "kd_gemm_mx8" if mx8 else ("kd_gemm_bf16" if d.precision == nat.PREC_BF16 else "kd_gemm_f32")
-            target.append(_Launch(getattr(lib, name), (C.byref(d),), what + ("(mx8)" if mx8 else ""), enc=(name, (d,))))
-            return d
-
-        def mx8_ok(M, N, K, epi):
-            """fp8 mode: this norm -> projection of the main chain goes to the block-scaled fp8 matrix instruction (kd_gemm_mx8)."""
-            # (from 4 096 rows on -- library option mx8_min_rows: below that the few-rows bf16 kernels are ahead -- batch 1: 0.512 against 0.552 ms
-            # per forward, profiles/r06_bench_detail_full.json)
-            return fp8 and target is self.launches and M >= lib.kd_get_option(b"mx8_min_rows", 4096) and bool(lib.kd_gemm_mx8_supported(M, N, K, epi, 1))
-
-        def call(what, fn, *args):
-            target.append(_Launch(fn, args, what, enc=(fn.__name__, args)))
-
-        def build_cond(rows):
-            """The conditioning chain (image_transformer_v2.py:734-740, :569-581) for ``rows`` rows: FourierFeatures ->
-            mapping network -> every AdaRMSNorm scale of the network, with its own input and work buffers."""
-            nonlocal target, chain
-            ch = _CondChain(rows)
-            saved, target, chain = target, ch.launches, ch
-            try:
-                ch.c_sigma = torch.empty(rows, **f32)
-                ch.class_ids = torch.zeros(rows, device=device, dtype=torch.int64)
-                ch.aug_in = torch.zeros(rows, 9, **f32) if has_aug else None
-                ch.map_in = torch.zeros(rows, m.mapping_cond_dim, **f32) if has_mapping_cond else None
-                ff, temb, emb, mres, cond = (torch.empty(rows, mw, **f32) for _ in range(5))
-                mh = torch.empty(rows, mdff, **f32)
-                ch.keep += [ff, temb, emb, mres, cond, mh]
-                call("fourier_sigma", lib.kd_fourier_sigma_f32, _ptr(ch.c_sigma), _ptr(m.time_emb.weight), _ptr(ff), rows, mw // 2)
-                gemm("time_in_proj", ff, m.time_in_proj.weight, temb, rows, mw, mw)
-                if has_aug:
-                    aug_ff, aug_proj = torch.empty(rows, mw, **f32), torch.empty(rows, mw, **f32)
-                    ch.keep += [aug_ff, aug_proj]
-                    call("fourier_aug", lib.kd_fourier_f32, _ptr(ch.aug_in), _ptr(m.aug_emb.weight), _ptr(aug_ff), rows, 9, mw // 2)
-                    gemm("aug_in_proj", aug_ff, m.aug_in_proj.weight, aug_proj, rows, mw, mw)
-                    aug_term, aug_rows = aug_proj, 1
-                else:
-                    # aug_cond = zeros  =>  FourierFeatures = [cos 0, sin 0] = [1..1, 0..0]: a constant vector
-                    z_ff, aug_const = torch.empty(1, mw, **f32), torch.empty(1, mw, **f32)
-                    zeros9 = torch.zeros(1, 9, **f32)
-                    ch.keep += [z_ff, aug_const, zeros9]
-                    call("fourier_aug0", lib.kd_fourier_f32, _ptr(zeros9), _ptr(m.aug_emb.weight), _ptr(z_ff), 1, 9, mw // 2)
-                    gemm("aug_in_proj0", z_ff, m.aug_in_proj.weight, aug_const, 1, mw, mw)
-                    aug_term, aug_rows = aug_const, 0
-                map_term = None
-                if has_mapping_cond:
-                    map_term = torch.empty(rows, mw, **f32)
-                    ch.keep.append(map_term)
-                    gemm("mapping_cond_in_proj", ch.map_in, m.mapping_cond_in_proj.weight, map_term, rows, mw, m.mapping_cond_dim)
-                call("cond_sum", lib.kd_cond_sum_f32, _ptr(emb), _ptr(temb), _ptr(aug_term), aug_rows,
-                     _ptr(m.class_emb.weight) if has_class else None, _ptr(ch.class_ids) if has_class else None,
-                     None if map_term is None else _ptr(map_term), rows, mw)
-                call("mapping.in_norm", lib.kd_rmsnorm_f32, _ptr(emb), _ptr(m.mapping.in_norm.scale), _ptr(mres), rows, mw, C.c_float(1e-6))
-                for blk in m.mapping.blocks:
-                    gemm("mapping.up_proj", mres, blk.up_proj.weight, mh, rows, mdff, mw, epi=nat.EPI_GEGLU,
-                         scale_ptr=blk.norm.scale.data_ptr(), scale_stride=0, rows_per_sample=rows)
-                    gemm("mapping.down_proj", mh, blk.down_proj.weight, mres, rows, mw, mdff, epi=nat.EPI_RESIDUAL, R=mres)
-                call("mapping.out_norm", lib.kd_rmsnorm_f32, _ptr(mres), _ptr(m.mapping.out_norm.scale), _ptr(cond), rows, mw, C.c_float(1e-6))
-                ch.d_scales = gemm("ada_norm_scales", cond, wcat, None, rows, total, mw, out_add=1.0)
-            finally:
-                target, chain = saved, None
-            return ch
-
-        target = chain = None
-        self.build_cond = build_cond
         self.scale_width = total
-        self.step_chain = build_cond(B)                     # the per-step chain (inline, or one step ahead on the side stream)
+        self.step_chain = self.build_cond(B)                # the per-step chain (inline, or one step ahead on the side stream)
 
         # ---- hourglass ------------------------------------------------------------------------
-        target = self.launches
-        self.d_patch_in = gemm("patch_in", None, m.patch_in.proj.weight, xs[0], toks[0], levels[0].width, m.in_channels * ph * pw,
-                               a_mode=nat.A_PATCH_NCHW, grid=grids[0], patch=(ph, pw, m.in_channels))
-
-        def scale_ptr(name):
-            return ("table", 4 * offsets[name])
-
-        class _ScaleRef:                                    # patched per run like the descriptors in norm_descs
-            def __init__(self):
-                self._scale, self._call, self._index = None, None, 0
-
-            def bind_call(self, call, index):               # (nat.encode_call: this pointer lives in a kd_run_list entry too)
-                self._call, self._index = call, index
-
-            @property
-            def scale(self):
-                return self._scale
-
-            @scale.setter
-            def scale(self, v):
-                self._scale = v
-                if self._call is not None:
-                    self._call.p[self._index] = v
-
-        def norm_split(what, x_t, table_off, T_, d_, rps_):
-            """AdaRMSNorm of the fp32 rows of ``x_t`` -> (hi, lo) bf16 planes in ``xn`` (kd_norm_split_f32)."""
-            ref = _ScaleRef()
-            self.norm_descs.append((ref, table_off))
-            hi_p, lo_p = xn.data_ptr(), xn.data_ptr() + 2 * T_ * d_
-            xp = x_t.data_ptr()
-            target.append(_Launch(lambda stream, ref=ref: lib.kd_norm_split_f32(xp, ref.scale, total, rps_, hi_p, lo_p, T_, d_, 1e-6, stream),
-                                  (), what + " (split)", enc=("kd_norm_split_f32", (xp, ref, total, rps_, hi_p, lo_p, T_, d_, 1e-6))))
-            return (hi_p, lo_p)
-
-        packed_qkv = precision == nat.PREC_SPLIT3
-
-        def add_layer(li, prefix, mod, index):
-            lv, (gh, gw), T = levels[li], grids[li], toks[li]
-            d, x = lv.width, xs[li]
-            rps = gh * gw
-            ffn_x3 = precision == nat.PREC_SPLIT3 and target is self.launches and lib.kd_ffn_f32_supported(T, d, lv.d_ff)     # (library option ffn_x3)
-            # out projection fused into the FF kernel: width 128 (+3.5 % images/s in round 3) and, since round 5, width 256 too: in round 3
-            # that measured level (176.1 vs 176.0: one wave per SIMD there); with the round-4 / 5 kernels around it the removed launch + the
-            # attention rows' HBM round trip are worth +1.5 .. +3.0 % on two boxes (same box, back to back: 207.9 / 207.9 / 208.7 vs 214.3;
-            # 186.9 / 186.9 / 187.0 vs 189.4 / 190.0).  KDIFF_FFN_OUT: 0 never, 1 = width 128 only, all (default) = every width the kernel
-            # takes, or ONE width
-            fo = os.environ.get("KDIFF_FFN_OUT", "all")
-            ffn_bf = bf and target is self.launches and bool(lib.kd_ffn_bf16_supported(T, d, lv.d_ff))
-            fuse_out = hasattr(mod, "self_attn") and ((ffn_x3 and d in (128, 256)) or (ffn_bf and d == 128)) \
-                and (d == 128 if fo == "1" else fo in ("all", str(d)))
-            if hasattr(mod, "self_attn"):
-                sa, spec = mod.self_attn, lv.self_attn
-                nh = d // spec.d_head
-                if bf:
-                    # bf16 mode: the qkv epilogue evaluates the RoPE angles itself (hardware sin / cos) from the token's axial
-                    # position and the head's frequencies in revolutions -- two tiny tables instead of cos / sin per (token, head)
-                    cos_t, sin_t = m._rope_pos_freq(li, grids, sa, device)
-                else:
-                    cos_t, sin_t = m._rope_tables(li, grids, sa, device)
-                self.keep += [cos_t, sin_t]
-                qk = (sa.scale, cos_t, sin_t, nh)
-                if precision == nat.PREC_SPLIT3:
-                    # the split3 projections of round 3 evaluate the angles like the bf16 ones (no table loads beside their LDS-DMA ring);
-                    # the tables stay for the round-1 kernels they fall back to (ragged shapes) and for the exact mode
-                    pos_t, freq_t = m._rope_pos_freq(li, grids, sa, device)
-                    self.keep += [pos_t, freq_t]
-                    qk += (pos_t, freq_t)
-                # q, k leave the qkv GEMM already prepared (cosine-sim scale + RoPE in its epilogue): every halo /
-                # window / key tile of the attention cores would otherwise redo that work per use
-                # ... and, for the split-bf16x3 cores, already SPLIT (hi / lo bf16 chunks in the fp32 slots): the cores take
-                # their operands as stored instead of converting every halo / window / key-block element again
-                # (the tiled qkv epilogue keeps its per-head constants in a 16-head LDS table, csrc/gemm_x3t.hip: wider levels -- 1152 =
-                # 18 heads and up -- take the fp32-A norm -> projection kernels of round 1 like every shape the fused kernels refuse)
-                # bf16 mode, global attention at 256 tokens per sample: norm -> qkv projection of a head -> cosine-sim + RoPE -> attention in
-                # ONE launch per layer (csrc/block_bf16.hip: attn_block_bf16_kernel; q, k, v never reach HBM).  The descriptor is the qkv
-                # projection's, its C the attention output
-                # From 32 (sample, head) workgroups on: below that (batch 1 - 2 at level 2) the few-rows projection + the dense core are faster
-                # (0.514 against 0.543 ms per forward at batch 1; from batch 4 on the one-launch form wins: profiles/r05_attn_block.md)
-                fused_block = bf and isinstance(spec, GlobalAttentionSpec) and target is self.launches and T % 256 == 0 \
-                    and os.environ.get("KDIFF_ATTN_BLOCK", "1") != "0" and bool(lib.kd_attn_block_bf16_supported(rps, d, nh)) \
-                    and (B * nh >= 32 or os.environ.get("KDIFF_ATTN_BLOCK", "1") == "force")
-                # fp8 mode: the qkv projection on the fp8 matrix instruction -- except where the one-launch bf16 attention block takes the layer
-                # (level 2 of the 256 x 256 configs: 25.5 us against 25.6 + 13.6 us for fp8 projection + dense core, profiles/r06_fp8_mode.md)
-                qkv_mx8 = not fused_block and mx8_ok(T, 3 * d, d, nat.EPI_QKV)
-                if fused_block:
-                    dq = gemm(prefix + "attn_block", x, sa.qkv_proj.weight, att, T, 3 * d, d, epi=nat.EPI_QKV,
-                              scale_ptr=scale_ptr(prefix + "self_attn.norm"), scale_stride=total, rows_per_sample=rps, qk=qk)
-                    target.pop()
-                    target.append(_Launch(lib.kd_attn_block_bf16, (C.byref(dq),), prefix + "attn_block", enc=("kd_attn_block_bf16", (dq,))))
-                elif xn is not None and prepass(d) and nh <= 16:
-                    # AdaRMSNorm -> planes once, then a GEMM whose two operands both move by LDS-DMA
-                    xn_planes = norm_split(prefix + "self_attn.norm", x, scale_ptr(prefix + "self_attn.norm")[1], T, d, rps)
-                    dq = gemm(prefix + "qkv_proj", None, sa.qkv_proj.weight, qkv, T, 3 * d, d, epi=nat.EPI_QKV, rows_per_sample=rps, qk=qk,
-                              a_planes=xn_planes)
-                else:
-                    dq = gemm(prefix + "qkv_proj", x, sa.qkv_proj.weight, qkv, T, 3 * d, d, epi=nat.EPI_QKV,
-                              scale_ptr=scale_ptr(prefix + "self_attn.norm"), scale_stride=total, rows_per_sample=rps, qk=qk, mx8=qkv_mx8)
-                    # bf16 mode, K = 256 / 512 with an attention core of its own (neighbourhood / window levels): the projection in the block
-                    # form (kd_proj_block_bf16: a workgroup per (256-row group, 6 head vectors), rows normalised once) for one-round grids (192 .. 256)
-                    if bf and not qkv_mx8 and target is self.launches and os.environ.get("KDIFF_PROJ_BLOCK", "1") != "0" \
-                            and bool(lib.kd_proj_block_bf16_supported(rps, d, 3 * d, nat.EPI_QKV)) and 192 <= (T // 256) * (3 * d // 384) <= 256:
-                        target[-1] = _Launch(lib.kd_proj_block_bf16, (C.byref(dq),), prefix + "qkv_proj(block)", enc=("kd_proj_block_bf16", (dq,)))
-                dq.qkv_packed = 1 if packed_qkv else 0
-                prep = (2 if packed_qkv else 0, None, None, None, C.c_float(1e-6), precision)
-                shift = 0
-                if isinstance(spec, ShiftedWindowAttentionSpec):
-                    shift = spec.window_size // 2 if index % 2 == 1 else 0          # :523
-                if fused_block:
-                    pass
-                elif bf and isinstance(spec, GlobalAttentionSpec):
-                    call(prefix + "attn_global", lib.kd_attn_global_bf16, _ptr(qkv), _ptr(att), B, gh * gw, nh)
-                elif bf and isinstance(spec, NeighborhoodAttentionSpec):
-                    call(prefix + "attn_na2d", lib.kd_attn_na2d_bf16, _ptr(qkv), _ptr(att), B, gh, gw, nh, spec.kernel_size)
-                elif bf:
-                    call(prefix + "attn_window", lib.kd_attn_window_bf16, _ptr(qkv), _ptr(att), B, gh, gw, nh, spec.window_size, shift)
-                elif isinstance(spec, GlobalAttentionSpec):
-                    call(prefix + "attn_global", lib.kd_attn_global_f32, _ptr(qkv), _ptr(att), B, gh * gw, nh, *prep)
-                elif isinstance(spec, NeighborhoodAttentionSpec):
-                    call(prefix + "attn_na2d", lib.kd_attn_na2d_f32, _ptr(qkv), _ptr(att), B, gh, gw, nh, spec.kernel_size, *prep)
-                else:
-                    call(prefix + "attn_window", lib.kd_attn_window_f32, _ptr(qkv), _ptr(att), B, gh, gw, nh, spec.window_size, shift, *prep)
-                if not fuse_out:
-                    gemm(prefix + "out_proj", att, sa.out_proj.weight, x, T, d, d, epi=nat.EPI_RESIDUAL, R=x)
-            if ffn_x3:
-                # fp32-parity mode: the whole FeedForwardBlock in one kernel (csrc/ffn_x3.hip), hidden activation on the chip; at widths 128 / 256
-                # the attention block's out projection runs in front of it in the same kernel (x + att W_out^T never crosses HBM)
-                fd = nat.KdFfn()
-                fd.x = fd.out = x.data_ptr()
-                fd.scale_stride, fd.rows_per_sample, fd.eps = total, rps, 1e-6
-                fd.Wp_up = m._packed_image(mod.ff.up_proj.weight, lv.d_ff, d, 3 if fuse_out else 1).data_ptr()
-                fd.Wp_down = m._packed_image(mod.ff.down_proj.weight, d, lv.d_ff, 2).data_ptr()
-                if fuse_out:
-                    fd.attn = att.data_ptr()
-                    fd.Wp_out = m._packed_image(mod.self_attn.out_proj.weight, d, d, 0).data_ptr()
-                fd.M, fd.K, fd.d_ff = T, d, lv.d_ff
-                self.norm_descs.append((fd, scale_ptr(prefix + "ff.norm")[1]))
-                self.keep.append(fd)
-                target.append(_Launch(lib.kd_ffn_f32, (C.byref(fd),), prefix + "ff", enc=("kd_ffn_f32", (fd,))))
-            elif ffn_bf:
-                # the whole FeedForwardBlock (:487-493) in one kernel: the d_ff-wide hidden activation stays on the chip (width 128: with
-                # the attention block's out projection in front of it)
-                fd = nat.KdFfn()
-                fd.x = fd.out = x.data_ptr()
-                fd.scale_stride, fd.rows_per_sample, fd.eps = total, rps, 1e-6
-                fd.Wp_up = m._packed_image(mod.ff.up_proj.weight, lv.d_ff, d, 3 if fuse_out else 1, bf16=True).data_ptr()
-                fd.Wp_down = m._packed_image(mod.ff.down_proj.weight, d, lv.d_ff, 2, bf16=True).data_ptr()
-                if fuse_out:
-                    fd.attn = att.data_ptr()
-                    fd.Wp_out = m._packed_image(mod.self_attn.out_proj.weight, d, d, 0, bf16=True).data_ptr()
-                fd.M, fd.K, fd.d_ff = T, d, lv.d_ff
-                self.norm_descs.append((fd, scale_ptr(prefix + "ff.norm")[1]))
-                self.keep.append(fd)
-                target.append(_Launch(lib.kd_ffn_bf16, (C.byref(fd),), prefix + "ff", enc=("kd_ffn_bf16", (fd,))))
-            else:
-                hid8 = None
-                if xn is not None and target is self.launches and prepass(d) and lv.d_ff % 64 == 0:
-                    xn_planes = norm_split(prefix + "ff.norm", x, scale_ptr(prefix + "ff.norm")[1], T, d, rps)
-                    gemm(prefix + "up_proj", None, mod.ff.up_proj.weight, hid, T, lv.d_ff, d, epi=nat.EPI_GEGLU, a_planes=xn_planes)
-                else:
-                    up_mx8 = mx8_ok(T, lv.d_ff, d, nat.EPI_GEGLU)
-                    # fp8 mode: the hidden activation leaves the GEGLU epilogue as e4m3 rows + one power-of-two scale per (row, 32 features) -- in
-                    # the first half of `hid`, the scale bytes behind them -- and the down projection takes both operands as e4m3 by LDS-DMA
-                    down_mx8 = up_mx8 and lv.d_ff % 128 == 0 and bool(lib.kd_gemm_mx8_supported(T, d, lv.d_ff, nat.EPI_RESIDUAL, 0))
-                    hid8 = (hid.data_ptr(), hid.data_ptr() + T * lv.d_ff) if down_mx8 else None
-                    du = gemm(prefix + "up_proj", x, mod.ff.up_proj.weight, hid, T, lv.d_ff, d, epi=nat.EPI_GEGLU,
-                              scale_ptr=scale_ptr(prefix + "ff.norm"), scale_stride=total, rows_per_sample=rps, mx8=up_mx8, c_planes=hid8)
-                    # bf16 mode, rows per sample a multiple of 256: the projection in the attention block's form (a workgroup per (256-row group,
-                    # 192-output slice), rows normalised once; csrc/block_bf16.hip: proj_block_bf16_kernel) for grids that fill ONE round of the
-                    # chip's 256 CUs (192 .. 256 workgroups): two rounds measured level with the A-stationary kernel (42.3 against 41.5 us at
-                    # level 1), and a workgroup's six passes are a serial chain -- at 32 - 128 workgroups the A-stationary kernel, which splits
-                    # the same work over up to 512 slots, is faster (batch 4: 0.645 against 0.759 ms per forward; batch 16: level); same bits
-                    if bf and not up_mx8 and target is self.launches and os.environ.get("KDIFF_PROJ_BLOCK", "1") != "0" \
-                            and bool(lib.kd_proj_block_bf16_supported(rps, d, lv.d_ff, nat.EPI_GEGLU)) and 192 <= (T // 256) * (lv.d_ff // 192) <= 256:
-                        target[-1] = _Launch(lib.kd_proj_block_bf16, (C.byref(du),), prefix + "up_proj(block)", enc=("kd_proj_block_bf16", (du,)))
-                if hid8 is not None:
-                    gemm(prefix + "down_proj", None, mod.ff.down_proj.weight, x, T, d, lv.d_ff, epi=nat.EPI_RESIDUAL, R=x, a_planes=hid8, mx8=True)
-                else:
-                    gemm(prefix + "down_proj", hid, mod.ff.down_proj.weight, x, T, d, lv.d_ff, epi=nat.EPI_RESIDUAL, R=x)
-
+        L = self.launches
+        self.d_patch_in = self._gemm(L, "patch_in", None, m.patch_in.proj.weight, xs[0], toks[0], levels[0].width, m.in_channels * ph * pw,
+                                     a_mode=nat.A_PATCH_NCHW, grid=grids[0], patch=(ph, pw, m.in_channels))
         for li in range(n_lv - 1):
             for i, mod in enumerate(m.down_levels[li]):
-                add_layer(li, f"down_levels.{li}.{i}.", mod, i)
-            gemm(f"merges.{li}", xs[li], m.merges[li].proj.weight, xs[li + 1], toks[li + 1], levels[li + 1].width, 4 * levels[li].width,
-                 a_mode=nat.A_MERGE2x2, grid=grids[li + 1])
+                self._add_layer(li, f"down_levels.{li}.{i}.", mod, i)
+            self._gemm(L, f"merges.{li}", xs[li], m.merges[li].proj.weight, xs[li + 1], toks[li + 1], levels[li + 1].width,
+                       4 * levels[li].width, a_mode=nat.A_MERGE2x2, grid=grids[li + 1])
         for i, mod in enumerate(m.mid_level):
-            add_layer(n_lv - 1, f"mid_level.{i}.", mod, i)
+            self._add_layer(n_lv - 1, f"mid_level.{i}.", mod, i)
         for li in reversed(range(n_lv - 1)):
-            gemm(f"splits.{li}", xs[li + 1], m.splits[li].proj.weight, xs[li], toks[li + 1], 4 * levels[li].width, levels[li + 1].width,
-                 epi=nat.EPI_SPLIT_LERP, R=xs[li], fac=m.splits[li].fac, grid=grids[li + 1])
+            self._gemm(L, f"splits.{li}", xs[li + 1], m.splits[li].proj.weight, xs[li], toks[li + 1], 4 * levels[li].width,
+                       levels[li + 1].width, epi=nat.EPI_SPLIT_LERP, residual=xs[li], fac=m.splits[li].fac, grid=grids[li + 1])
             for i, mod in enumerate(m.up_levels[li]):
-                add_layer(li, f"up_levels.{li}.{i}.", mod, i + levels[li].depth)                      # :697
-        self.d_patch_out = gemm("patch_out", xs[0], m.patch_out.proj.weight, None, toks[0], m.out_channels * ph * pw, levels[0].width,
-                                epi=nat.EPI_UNPATCH_NCHW, scale_ptr=m.out_norm.scale.data_ptr(), scale_stride=0,
-                                rows_per_sample=grids[0][0] * grids[0][1], grid=grids[0], patch=(ph, pw, m.out_channels))
+                self._add_layer(li, f"up_levels.{li}.{i}.", mod, i + levels[li].depth)                      # :697
+        self.d_patch_out = self._gemm(L, "patch_out", xs[0], m.patch_out.proj.weight, None, toks[0], m.out_channels * ph * pw,
+                                      levels[0].width, epi=nat.EPI_UNPATCH_NCHW, norm_scale=m.out_norm.scale, scale_stride=0,
+                                      rows_per_sample=grids[0][0] * grids[0][1], grid=grids[0], patch=(ph, pw, m.out_channels))
         self._encode_launches()
+
+    def _gemm(self, launches, what, A, Wt, Cc, M, N, K, cond=False, table=None, entry=None, mx8=False, **kw):
+        """An ``ops.gemm`` descriptor (weight images from the model's cache) appended to ``launches`` as a launch of ``entry`` (default: the
+        plain GEMM of its precision).  ``cond``: a product of a conditioning chain (fp32 in every mode, one row per sample: _CondChain);
+        ``table``: name of the AdaRMSNorm whose scales it reads from the live scale table (the address is patched per run)."""
+        precision = self.cond_precision if cond else self.precision
+        if table is not None:
+            kw.update(scale_ptr=0, scale_stride=self.scale_width)
+        d = ops.gemm(A, Wt, Cc, M=M, N=N, K=K, precision=precision, per_row=cond, mx8=mx8, launch=False, pack=self.model._packed_image, **kw)
+        if table is not None:
+            self.norm_descs.append((d, self.table_offsets[table]))
+        launches.append(_Launch(entry or ops._gemm_entry(precision, mx8), (d,), what + ("(mx8)" if mx8 else "")))
+        return d
+
+    def _norm_split(self, launches, table, x, T, d, rps):
+        """AdaRMSNorm ``table`` of the fp32 rows of ``x`` -> (hi, lo) bf16 planes in ``xn`` (kd_norm_split_f32)."""
+        ref = _ScaleRef()
+        self.norm_descs.append((ref, self.table_offsets[table]))
+        planes = self.xn.view(torch.bfloat16)
+        hi, lo = planes[:T * d], planes[T * d:2 * T * d]
+        launches.append(_Launch("kd_norm_split_f32", (_ptr(x), ref, self.scale_width, rps, _ptr(hi), _ptr(lo), T, d, 1e-6), table + " (split)"))
+        return hi, lo
+
+    def build_cond(self, rows):
+        """The conditioning chain (image_transformer_v2.py:734-740, :569-581) for ``rows`` rows: FourierFeatures ->
+        mapping network -> every AdaRMSNorm scale of the network, with its own input and work buffers."""
+        m, f32 = self.model, dict(device=self.device, dtype=torch.float32)
+        mw, mdff = m.mapping_spec.width, m.mapping_spec.d_ff
+        ch = _CondChain(rows, self.lib)
+        L = ch.launches
+        ch.c_sigma = torch.empty(rows, **f32)
+        ch.class_ids = torch.zeros(rows, device=self.device, dtype=torch.int64)
+        ch.aug_in = torch.zeros(rows, 9, **f32) if self.has_aug else None
+        ch.map_in = torch.zeros(rows, m.mapping_cond_dim, **f32) if self.has_mapping_cond else None
+        ff, temb, emb, mres, cond = (torch.empty(rows, mw, **f32) for _ in range(5))
+        mh = torch.empty(rows, mdff, **f32)
+        ch.keep += [ff, temb, emb, mres, cond, mh]
+        L.append(_Launch("kd_fourier_sigma_f32", (_ptr(ch.c_sigma), _ptr(m.time_emb.weight), _ptr(ff), rows, mw // 2), "fourier_sigma"))
+        self._gemm(L, "time_in_proj", ff, m.time_in_proj.weight, temb, rows, mw, mw, cond=True)
+        if self.has_aug:
+            aug_ff, aug_proj = torch.empty(rows, mw, **f32), torch.empty(rows, mw, **f32)
+            ch.keep += [aug_ff, aug_proj]
+            L.append(_Launch("kd_fourier_f32", (_ptr(ch.aug_in), _ptr(m.aug_emb.weight), _ptr(aug_ff), rows, 9, mw // 2), "fourier_aug"))
+            self._gemm(L, "aug_in_proj", aug_ff, m.aug_in_proj.weight, aug_proj, rows, mw, mw, cond=True)
+            aug_term, aug_rows = aug_proj, 1
+        else:
+            # aug_cond = zeros  =>  FourierFeatures = [cos 0, sin 0] = [1..1, 0..0]: a constant vector
+            z_ff, aug_const = torch.empty(1, mw, **f32), torch.empty(1, mw, **f32)
+            zeros9 = torch.zeros(1, 9, **f32)
+            ch.keep += [z_ff, aug_const, zeros9]
+            L.append(_Launch("kd_fourier_f32", (_ptr(zeros9), _ptr(m.aug_emb.weight), _ptr(z_ff), 1, 9, mw // 2), "fourier_aug0"))
+            self._gemm(L, "aug_in_proj0", z_ff, m.aug_in_proj.weight, aug_const, 1, mw, mw, cond=True)
+            aug_term, aug_rows = aug_const, 0
+        map_term = None
+        if self.has_mapping_cond:
+            map_term = torch.empty(rows, mw, **f32)
+            ch.keep.append(map_term)
+            self._gemm(L, "mapping_cond_in_proj", ch.map_in, m.mapping_cond_in_proj.weight, map_term, rows, mw, m.mapping_cond_dim, cond=True)
+        L.append(_Launch("kd_cond_sum_f32", (_ptr(emb), _ptr(temb), _ptr(aug_term), aug_rows,
+                                             _ptr(m.class_emb.weight) if self.has_class else None, _ptr(ch.class_ids) if self.has_class else None,
+                                             None if map_term is None else _ptr(map_term), rows, mw), "cond_sum"))
+        L.append(_Launch("kd_rmsnorm_f32", (_ptr(emb), _ptr(m.mapping.in_norm.scale), _ptr(mres), rows, mw, C.c_float(1e-6)), "mapping.in_norm"))
+        for blk in m.mapping.blocks:
+            self._gemm(L, "mapping.up_proj", mres, blk.up_proj.weight, mh, rows, mdff, mw, cond=True, epi=nat.EPI_GEGLU,
+                       norm_scale=blk.norm.scale, scale_stride=0, rows_per_sample=rows)
+            self._gemm(L, "mapping.down_proj", mh, blk.down_proj.weight, mres, rows, mw, mdff, cond=True, epi=nat.EPI_RESIDUAL, residual=mres)
+        L.append(_Launch("kd_rmsnorm_f32", (_ptr(mres), _ptr(m.mapping.out_norm.scale), _ptr(cond), rows, mw, C.c_float(1e-6)), "mapping.out_norm"))
+        ch.d_scales = self._gemm(L, "ada_norm_scales", cond, self.wcat, None, rows, self.scale_width, mw, cond=True, out_add=1.0)
+        return ch
+
+    def _qk(self, li, sa, nh):
+        """Per-head constants of the qkv epilogue: (cosine-sim scale, RoPE tables, nh[, positions, frequencies])."""
+        m = self.model
+        if self.precision == nat.PREC_BF16:
+            # bf16 mode: the qkv epilogue evaluates the RoPE angles itself (hardware sin / cos) from the token's axial
+            # position and the head's frequencies in revolutions -- two tiny tables instead of cos / sin per (token, head)
+            cos_t, sin_t = m._rope_pos_freq(li, self.grids, sa, self.device)
+        else:
+            cos_t, sin_t = m._rope_tables(li, self.grids, sa, self.device)
+        self.keep += [cos_t, sin_t]
+        qk = (sa.scale, cos_t, sin_t, nh)
+        if self.precision == nat.PREC_SPLIT3:
+            # the split3 projections of round 3 evaluate the angles like the bf16 ones (no table loads beside their LDS-DMA ring);
+            # the tables stay for the round-1 kernels they fall back to (ragged shapes) and for the exact mode
+            pos_t, freq_t = m._rope_pos_freq(li, self.grids, sa, self.device)
+            self.keep += [pos_t, freq_t]
+            qk += (pos_t, freq_t)
+        return qk
+
+    def _add_layer(self, li, prefix, mod, index):
+        L, lv, (gh, gw), T = self.launches, self.levels[li], self.grids[li], self.toks[li]
+        d, d_ff, x, rps = lv.width, lv.d_ff, self.xs[li], gh * gw
+        spec = lv.self_attn
+        nh = d // spec.d_head if hasattr(mod, "self_attn") else 0
+        r = route_layer(self.lib, self.mode, self.B, T, rps, d, d_ff, nh, _ATTN_KIND[type(spec)] if nh else None, self.switches)
+        split3 = self.precision == nat.PREC_SPLIT3
+        if nh:
+            sa, norm = mod.self_attn, prefix + "self_attn.norm"
+            # q, k leave the qkv GEMM already prepared (cosine-sim scale + RoPE in its epilogue): every halo /
+            # window / key tile of the attention cores would otherwise redo that work per use
+            # ... and, for the split-bf16x3 cores, already SPLIT (hi / lo bf16 chunks in the fp32 slots): the cores take
+            # their operands as stored instead of converting every halo / window / key-block element again
+            q = dict(epi=nat.EPI_QKV, rows_per_sample=rps, qk=self._qk(li, sa, nh), qkv_packed=split3)
+            if r.qkv == "attn_block":
+                self._gemm(L, prefix + "attn_block", x, sa.qkv_proj.weight, self.att, T, 3 * d, d, table=norm, entry="kd_attn_block_bf16", **q)
+            elif r.qkv == "split":
+                planes = self._norm_split(L, norm, x, T, d, rps)
+                self._gemm(L, prefix + "qkv_proj", None, sa.qkv_proj.weight, self.qkv, T, 3 * d, d, a_planes=planes, **q)
+            elif r.qkv == "proj_block":
+                self._gemm(L, prefix + "qkv_proj(block)", x, sa.qkv_proj.weight, self.qkv, T, 3 * d, d, table=norm, entry="kd_proj_block_bf16", **q)
+            else:
+                self._gemm(L, prefix + "qkv_proj", x, sa.qkv_proj.weight, self.qkv, T, 3 * d, d, table=norm, mx8=r.qkv == "mx8", **q)
+            if r.core is not None:
+                if isinstance(spec, GlobalAttentionSpec):
+                    geo = (gh * gw, nh)
+                elif isinstance(spec, NeighborhoodAttentionSpec):
+                    geo = (gh, gw, nh, spec.kernel_size)
+                else:
+                    geo = (gh, gw, nh, spec.window_size, spec.window_size // 2 if index % 2 == 1 else 0)          # shift: :523
+                prep = () if r.core.endswith("_bf16") else (2 if split3 else 0, None, None, None, C.c_float(1e-6), self.precision)
+                L.append(_Launch(r.core, (_ptr(self.qkv), _ptr(self.att), self.B, *geo, *prep), prefix + _CORE[_ATTN_KIND[type(spec)]]))
+            if not r.fuse_out:
+                self._gemm(L, prefix + "out_proj", self.att, sa.out_proj.weight, x, T, d, d, epi=nat.EPI_RESIDUAL, residual=x)
+        norm, w_up, w_down = prefix + "ff.norm", mod.ff.up_proj.weight, mod.ff.down_proj.weight
+        if r.ff != "pair":
+            # the whole FeedForwardBlock in one kernel; with r.fuse_out the attention block's out projection runs in front of it in the same
+            # kernel (x + att W_out^T never crosses HBM)
+            fd = ops.ffn(x, None, w_up, w_down, out=x, scale_stride=self.scale_width, rows_per_sample=rps, attn=self.att if r.fuse_out else None,
+                         w_out=mod.self_attn.out_proj.weight if r.fuse_out else None, launch=False, pack=self.model._packed_image)
+            self.norm_descs.append((fd, self.table_offsets[norm]))
+            L.append(_Launch(r.ff, (fd,), prefix + "ff"))
+            return
+        hid8 = None
+        if r.up == "split":
+            planes = self._norm_split(L, norm, x, T, d, rps)
+            self._gemm(L, prefix + "up_proj", None, w_up, self.hid, T, d_ff, d, epi=nat.EPI_GEGLU, a_planes=planes)
+        else:
+            if r.down_mx8:                                  # (e4m3 rows, scale bytes behind them) in `hid`
+                b = self.hid.view(torch.uint8)
+                hid8 = (b[:T * d_ff], b[T * d_ff:T * d_ff + T * d_ff // 32])
+            block = r.up == "proj_block"
+            self._gemm(L, prefix + ("up_proj(block)" if block else "up_proj"), x, w_up, self.hid, T, d_ff, d, epi=nat.EPI_GEGLU, table=norm,
+                       rows_per_sample=rps, mx8=r.up == "mx8", c_planes=hid8, entry="kd_proj_block_bf16" if block else None)
+        if r.down_mx8:
+            self._gemm(L, prefix + "down_proj", None, w_down, x, T, d, d_ff, epi=nat.EPI_RESIDUAL, residual=x, a_planes=hid8, mx8=True)
+        else:
+            self._gemm(L, prefix + "down_proj", self.hid, w_down, x, T, d, d_ff, epi=nat.EPI_RESIDUAL, residual=x)
 
     def run_cond(self, buf, stream):
         """Per-step conditioning chain into scale table ``buf`` on ``stream``; its inputs were filled by the caller on the
@@ -619,18 +605,18 @@ class _Plan:
                 nat.check(rc, self.launches[self.failed.value].what)
             return
         for ln in self.launches:
-            rc = ln.fn(*ln.args, stream)
+            rc = ln(self.lib, stream)
             if rc:
                 nat.check(rc, ln.what)
 
     def _encode_launches(self):
         """The main chain as a kd_run_list array, if every launch of it can be named there (and KDIFF_RUN_LIST is not 0)."""
-        self.calls, self.failed, self.run_list = None, C.c_int(0), nat.lib().kd_run_list
-        if os.environ.get("KDIFF_RUN_LIST", "1") == "0" or not self.launches or any(ln.enc is None for ln in self.launches):
+        self.calls, self.failed, self.run_list = None, C.c_int(0), self.lib.kd_run_list
+        if self.switches["KDIFF_RUN_LIST"] == "0" or not self.launches:
             return
         calls = (nat.KdCall * len(self.launches))()
         for call, ln in zip(calls, self.launches):
-            if not nat.encode_call(call, *ln.enc):
+            if not nat.encode_call(call, ln.name, ln.args):
                 return
         self.calls = calls
 
@@ -881,7 +867,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
             self._drop_plans()
             self._fingerprint, self._packed = fp, {}
         has_class = self.class_emb is not None
-        # Kernel selection is fixed when a plan is built: by the arithmetic mode, by the environment switches read in _Plan and by
+        # Kernel selection is fixed when a plan is built (route_layer): by the arithmetic mode, by the environment switches read here and by
         # library options (kd_ffn_f32_supported follows "ffn_x3").  The switches are part of the key; a change of any library option
         # (nat.option_epoch, bumped by set_option and by a changed KDIFF_OPTIONS / KDIFF_* variable) drops the cached plans, so an
         # A/B run on ONE model object really compares two plans.
@@ -908,7 +894,8 @@ class ImageTransformerDenoiserModelV2(nn.Module):
                 self._plans.pop(next(iter(self._plans))).release()
                 gc.collect()
             with torch.inference_mode(False):     # (workspaces made under inference_mode could not be written in place outside it later)
-                plan = self._plans[key] = _Plan(self, B, H, W, key[3], has_class, key[5], x.device)
+                plan = self._plans[key] = _Plan(self, B, H, W, key[3], has_class, key[5], x.device, key[7],
+                                                dict(zip((name for name, _ in PLAN_SWITCHES), key[8:])))
         if plan is not None and has_class and class_cond is not None:
             # nn.Embedding raises on an out-of-range id (on every call); the HIP kernel would read past the table.  Checked whenever
             # the ids are a tensor this plan has not seen in this state (address, version): one device->host read per new id

@@ -88,7 +88,7 @@ def pack_weight(W, N, K, geglu, cache=True, bf16=False):
 def gemm(A, W, out, *, M, N, K, a_mode=nat.A_PLAIN, epi=nat.EPI_STORE, norm_scale=None, scale_stride=0,
          rows_per_sample=0, residual=None, grid=(0, 0), patch=(0, 0, 0), eps=1e-6, out_add=0.0,
          sigma=None, sigma_data=1.0, fac=None, scale_ptr=None, precision=None, qk=None, qkv_packed=False, per_row=False,
-         a_planes=None, c_planes=None, launch=True, mx8=False):
+         a_planes=None, c_planes=None, launch=True, mx8=False, pack=pack_weight):
     """Fused GEMM (see KdGemm in include/kdiff_hip.h).  ``norm_scale`` may be a tensor or, with
     ``scale_ptr``, a raw device address inside a larger scale table.  ``precision``: nat.PREC_EXACT /
     nat.PREC_SPLIT3 / nat.PREC_BF16 (default: KDIFF_GEMM env, split3).  In bf16 mode A, out and residual are bf16 tensors
@@ -96,8 +96,10 @@ def gemm(A, W, out, *, M, N, K, a_mode=nat.A_PLAIN, epi=nat.EPI_STORE, norm_scal
     ``per_row`` (fp32 modes): the per-row FMA kernel of the conditioning chain whatever M (KdGemm.per_row).
     ``a_planes`` / ``c_planes`` (split3): (hi, lo) bf16 tensors instead of the fp32 ``A`` / ``out`` (KdGemm.a_split / c_split; ``A`` / ``out``
     are then ignored and may be None).  ``launch=False``: only build and return the descriptor (for entry points that take one, e.g.
-    kd_attn_block_bf16).  ``mx8`` (bf16 tensors, norm -> store / qkv / GEGLU at K = 256 / 512): the product on the block-scaled fp8 matrix
-    instruction (kd_gemm_mx8: e4m3 weights with power-of-two channel scales, activations quantised per 32-k block)."""
+    kd_attn_block_bf16); ``A`` / ``out`` may then be None and ``scale_ptr`` 0, addresses the caller sets before each launch.
+    ``pack``: the weight-image provider (``pack_weight``'s signature; the model's plans share one cache per model).  ``mx8`` (bf16
+    tensors, norm -> store / qkv / GEGLU at K = 256 / 512): the product on the block-scaled fp8 matrix instruction (kd_gemm_mx8: e4m3
+    weights with power-of-two channel scales, activations quantised per 32-k block)."""
     d = nat.KdGemm()
     d.per_row = 1 if per_row else 0
     d.precision = nat.kernel_precision() if precision is None else precision
@@ -108,11 +110,11 @@ def gemm(A, W, out, *, M, N, K, a_mode=nat.A_PLAIN, epi=nat.EPI_STORE, norm_scal
     if mx8:
         if not bf:
             raise TypeError("mx8: bf16 activations only (precision=PREC_BF16)")
-        d.Wp = pack_weight(W, N, K, epi == nat.EPI_GEGLU, bf16="mx8").data_ptr()
+        d.Wp = pack(W, N, K, epi == nat.EPI_GEGLU, bf16="mx8").data_ptr()
     elif bf:
-        d.Wp = pack_weight(W, N, K, epi == nat.EPI_GEGLU, bf16=True).data_ptr()
+        d.Wp = pack(W, N, K, epi == nat.EPI_GEGLU, bf16=True).data_ptr()
     elif d.precision == nat.PREC_SPLIT3:
-        d.Wp = pack_weight(W, N, K, epi == nat.EPI_GEGLU).data_ptr()
+        d.Wp = pack(W, N, K, epi == nat.EPI_GEGLU).data_ptr()
     d.M, d.N, d.K = M, N, K
     d.a_mode, d.epi = a_mode, epi
     d.norm = 1 if (norm_scale is not None or scale_ptr is not None) else 0
@@ -125,7 +127,7 @@ def gemm(A, W, out, *, M, N, K, a_mode=nat.A_PLAIN, epi=nat.EPI_STORE, norm_scal
         d.a_split, d.A, d.A_lo = 1, _chk(a_planes[0], "A e4m3", torch.uint8).data_ptr(), _chk(a_planes[1], "A scales", torch.uint8).data_ptr()
     elif a_planes is not None:
         d.a_split, d.A, d.A_lo = 1, _chk(a_planes[0], "A hi", torch.bfloat16).data_ptr(), _chk(a_planes[1], "A lo", torch.bfloat16).data_ptr()
-    else:
+    elif A is not None or launch:
         d.A = _chk(A, "A", a_dt).data_ptr()
     if c_planes is not None and mx8:          # the GEGLU result as (e4m3 rows [M, N], scale bytes [M, N / 32])
         d.c_split, d.C, d.C_lo = 1, _chk(c_planes[0], "C e4m3", torch.uint8).data_ptr(), _chk(c_planes[1], "C scales", torch.uint8).data_ptr()
@@ -133,7 +135,7 @@ def gemm(A, W, out, *, M, N, K, a_mode=nat.A_PLAIN, epi=nat.EPI_STORE, norm_scal
     elif c_planes is not None:
         d.c_split, d.C, d.C_lo = 1, _chk(c_planes[0], "C hi", torch.bfloat16).data_ptr(), _chk(c_planes[1], "C lo", torch.bfloat16).data_ptr()
         out = c_planes
-    else:
+    elif out is not None or launch:
         d.C = _chk(out, "C", c_dt).data_ptr()
     d.R = None if residual is None else _chk(residual, "R", c_dt).data_ptr()
     d.scale = scale_ptr if scale_ptr is not None else (None if norm_scale is None else _chk(norm_scale, "scale").data_ptr())
@@ -150,13 +152,13 @@ def gemm(A, W, out, *, M, N, K, a_mode=nat.A_PLAIN, epi=nat.EPI_STORE, norm_scal
         d.qkv_packed = 1 if qkv_packed else 0      # q, k, v stored as split-bf16 chunks for the attention cores (prep="packed")
     if not launch:
         return d
-    if mx8:
-        nat.check(nat.lib().kd_gemm_mx8(C.byref(d), _stream()), "kd_gemm_mx8")
-    elif bf:
-        nat.check(nat.lib().kd_gemm_bf16(C.byref(d), _stream()), "kd_gemm_bf16")
-    else:
-        nat.check(nat.lib().kd_gemm_f32(C.byref(d), _stream()), "kd_gemm_f32")
+    name = _gemm_entry(d.precision, mx8)
+    nat.check(getattr(nat.lib(), name)(C.byref(d), _stream()), name)
     return out
+
+
+def _gemm_entry(precision, mx8=False):        # entry point of a plain ``gemm`` descriptor
+    return "kd_gemm_mx8" if mx8 else ("kd_gemm_bf16" if precision == nat.PREC_BF16 else "kd_gemm_f32")
 
 
 def _prec_of(x):
@@ -312,13 +314,15 @@ def ffn_supported(M, K, d_ff, bf16=True):
     return bool(fn(int(M), int(K), int(d_ff)))
 
 
-def ffn(x, norm_scale, w_up, w_down, out=None, scale_stride=None, rows_per_sample=None, eps=1e-6, attn=None, w_out=None):
+def ffn(x, norm_scale, w_up, w_down, out=None, scale_stride=None, rows_per_sample=None, eps=1e-6, attn=None, w_out=None, launch=True,
+        pack=pack_weight):
     """FeedForwardBlock.forward (image_transformer_v2.py:487-493) in one kernel:
     out = x + down_proj(GEGLU(up_proj(rms_norm(x) * norm_scale))).  x: bf16 or fp32 [..., K]; norm_scale: fp32 [B, K] (one row per
     sample; ``rows_per_sample`` tokens each) ; w_up: fp32 [2 d_ff, K]; w_down: fp32 [K, d_ff].  ``out`` may be x.
     With ``attn`` ([..., K], the attention core's output, same dtype as x) and ``w_out`` ([K, K]) the attention block's out projection
     runs in front of the block in the same kernel: x' = x + attn @ w_out.T, out = x' + ff(x') (:473-476, :487-493); widths 128 (bf16,
-    fp32) and 256 (fp32)."""
+    fp32) and 256 (fp32).  ``launch`` / ``pack`` as in ``gemm``: with ``launch=False`` only the descriptor is built and returned, and
+    ``norm_scale`` may be None (the caller sets ``scale`` before each launch; ``scale_stride`` / ``rows_per_sample`` are then given)."""
     K = x.shape[-1]
     M = x.numel() // K
     d_ff = w_down.shape[1]
@@ -327,23 +331,25 @@ def ffn(x, norm_scale, w_up, w_down, out=None, scale_stride=None, rows_per_sampl
     bf = x.dtype == torch.bfloat16
     out = torch.empty_like(x) if out is None else out
     d = nat.KdFfn()
-    d.x, d.out, d.scale = _p(_chk(x, "x", x.dtype)), _p(_chk(out, "out", x.dtype)), _p(_chk(norm_scale, "norm_scale"))
+    d.x, d.out = _p(_chk(x, "x", x.dtype)), _p(_chk(out, "out", x.dtype))
+    if norm_scale is not None or launch:
+        d.scale = _p(_chk(norm_scale, "norm_scale"))
     d.scale_stride = norm_scale.shape[-1] if scale_stride is None else scale_stride
     d.rows_per_sample = (M // max(norm_scale.numel() // norm_scale.shape[-1], 1)) if rows_per_sample is None else rows_per_sample
     d.eps = eps
     fused_out = attn is not None
     if fused_out and w_out is None:
         raise ValueError("ffn: attn and w_out go together")
-    up_img, down_img = pack_weight(w_up, d_ff, K, 3 if fused_out else 1, bf16=bf), pack_weight(w_down, K, d_ff, 2, bf16=bf)
+    up_img, down_img = pack(w_up, d_ff, K, 3 if fused_out else 1, bf16=bf), pack(w_down, K, d_ff, 2, bf16=bf)
     d.Wp_up, d.Wp_down = _p(up_img), _p(down_img)
     d.M, d.K, d.d_ff = M, K, d_ff
     if fused_out:
-        out_img = pack_weight(w_out, K, K, 0, bf16=bf)
+        out_img = pack(w_out, K, K, 0, bf16=bf)
         d.attn, d.Wp_out = _p(_chk(attn, "attn", x.dtype)), _p(out_img)
-    if bf:
-        nat.check(nat.lib().kd_ffn_bf16(C.byref(d), _stream()), "kd_ffn_bf16")
-    else:
-        nat.check(nat.lib().kd_ffn_f32(C.byref(d), _stream()), "kd_ffn_f32")
+    if not launch:
+        return d
+    name = "kd_ffn_bf16" if bf else "kd_ffn_f32"
+    nat.check(getattr(nat.lib(), name)(C.byref(d), _stream()), name)
     return out
 
 

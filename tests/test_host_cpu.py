@@ -1002,3 +1002,126 @@ def test_bench_optional_blocks_never_cost_the_line(monkeypatch):
     assert os.environ["KDIFF_GEMM"] == "split3"
     with pytest.raises(KeyboardInterrupt):                      # an interrupt is not swallowed
         bench.run_guarded(line, "int", lambda: (_ for _ in ()).throw(KeyboardInterrupt()), "split3")
+
+
+# Kernel routing of configs/config_oxford_flowers.json (route_layer) per arithmetic mode, routing switch and batch, level by level (widths
+# 128 / 256 / 512: "qkv core ff"; ff is the one-kernel FF block, +out with the out projection inside it, or the up projection of an up +
+# down pair).  Recorded from the launch plans that the plan builder made on an MI355X before routing was a function of its own.
+FLOWERS_ROUTES = {
+    "exact 1": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact 4": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact 32": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact ATTN_BLOCK=0 1": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact ATTN_BLOCK=0 4": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact ATTN_BLOCK=0 32": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact ATTN_BLOCK=force 1": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact ATTN_BLOCK=force 4": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact ATTN_BLOCK=force 32": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact PROJ_BLOCK=0 1": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact PROJ_BLOCK=0 4": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact PROJ_BLOCK=0 32": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact FFN_OUT=0 1": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact FFN_OUT=0 4": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact FFN_OUT=0 32": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact FFN_OUT=1 1": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact FFN_OUT=1 4": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact FFN_OUT=1 32": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact FFN_OUT=256 1": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact FFN_OUT=256 4": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "exact FFN_OUT=256 32": "plain na2d_f32 up=plain | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 1": "plain na2d_f32 ffn_f32+out | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 4": "plain na2d_f32 ffn_f32+out | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 32": "plain na2d_f32 ffn_f32+out | plain na2d_f32 ffn_f32+out | plain global_f32 up=plain",
+    "split3 ATTN_BLOCK=0 1": "plain na2d_f32 ffn_f32+out | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 ATTN_BLOCK=0 4": "plain na2d_f32 ffn_f32+out | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 ATTN_BLOCK=0 32": "plain na2d_f32 ffn_f32+out | plain na2d_f32 ffn_f32+out | plain global_f32 up=plain",
+    "split3 ATTN_BLOCK=force 1": "plain na2d_f32 ffn_f32+out | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 ATTN_BLOCK=force 4": "plain na2d_f32 ffn_f32+out | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 ATTN_BLOCK=force 32": "plain na2d_f32 ffn_f32+out | plain na2d_f32 ffn_f32+out | plain global_f32 up=plain",
+    "split3 PROJ_BLOCK=0 1": "plain na2d_f32 ffn_f32+out | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 PROJ_BLOCK=0 4": "plain na2d_f32 ffn_f32+out | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 PROJ_BLOCK=0 32": "plain na2d_f32 ffn_f32+out | plain na2d_f32 ffn_f32+out | plain global_f32 up=plain",
+    "split3 FFN_OUT=0 1": "plain na2d_f32 ffn_f32 | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 FFN_OUT=0 4": "plain na2d_f32 ffn_f32 | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 FFN_OUT=0 32": "plain na2d_f32 ffn_f32 | plain na2d_f32 ffn_f32 | plain global_f32 up=plain",
+    "split3 FFN_OUT=1 1": "plain na2d_f32 ffn_f32+out | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 FFN_OUT=1 4": "plain na2d_f32 ffn_f32+out | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 FFN_OUT=1 32": "plain na2d_f32 ffn_f32+out | plain na2d_f32 ffn_f32 | plain global_f32 up=plain",
+    "split3 FFN_OUT=256 1": "plain na2d_f32 ffn_f32 | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 FFN_OUT=256 4": "plain na2d_f32 ffn_f32 | plain na2d_f32 up=plain | plain global_f32 up=plain",
+    "split3 FFN_OUT=256 32": "plain na2d_f32 ffn_f32 | plain na2d_f32 ffn_f32+out | plain global_f32 up=plain",
+    "bf16 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "bf16 4": "plain na2d_bf16 ffn_bf16+out | plain na2d_bf16 up=plain | attn_block - up=plain",
+    "bf16 32": "plain na2d_bf16 ffn_bf16+out | proj_block na2d_bf16 up=plain | attn_block - up=proj_block",
+    "bf16 ATTN_BLOCK=0 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "bf16 ATTN_BLOCK=0 4": "plain na2d_bf16 ffn_bf16+out | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "bf16 ATTN_BLOCK=0 32": "plain na2d_bf16 ffn_bf16+out | proj_block na2d_bf16 up=plain | plain global_bf16 up=proj_block",
+    "bf16 ATTN_BLOCK=force 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | attn_block - up=plain",
+    "bf16 ATTN_BLOCK=force 4": "plain na2d_bf16 ffn_bf16+out | plain na2d_bf16 up=plain | attn_block - up=plain",
+    "bf16 ATTN_BLOCK=force 32": "plain na2d_bf16 ffn_bf16+out | proj_block na2d_bf16 up=plain | attn_block - up=proj_block",
+    "bf16 PROJ_BLOCK=0 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "bf16 PROJ_BLOCK=0 4": "plain na2d_bf16 ffn_bf16+out | plain na2d_bf16 up=plain | attn_block - up=plain",
+    "bf16 PROJ_BLOCK=0 32": "plain na2d_bf16 ffn_bf16+out | plain na2d_bf16 up=plain | attn_block - up=plain",
+    "bf16 FFN_OUT=0 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "bf16 FFN_OUT=0 4": "plain na2d_bf16 ffn_bf16 | plain na2d_bf16 up=plain | attn_block - up=plain",
+    "bf16 FFN_OUT=0 32": "plain na2d_bf16 ffn_bf16 | proj_block na2d_bf16 up=plain | attn_block - up=proj_block",
+    "bf16 FFN_OUT=1 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "bf16 FFN_OUT=1 4": "plain na2d_bf16 ffn_bf16+out | plain na2d_bf16 up=plain | attn_block - up=plain",
+    "bf16 FFN_OUT=1 32": "plain na2d_bf16 ffn_bf16+out | proj_block na2d_bf16 up=plain | attn_block - up=proj_block",
+    "bf16 FFN_OUT=256 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "bf16 FFN_OUT=256 4": "plain na2d_bf16 ffn_bf16 | plain na2d_bf16 up=plain | attn_block - up=plain",
+    "bf16 FFN_OUT=256 32": "plain na2d_bf16 ffn_bf16 | proj_block na2d_bf16 up=plain | attn_block - up=proj_block",
+    "fp8 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "fp8 4": "plain na2d_bf16 ffn_bf16+out | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=plain",
+    "fp8 32": "plain na2d_bf16 ffn_bf16+out | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=mx8,down=mx8",
+    "fp8 ATTN_BLOCK=0 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "fp8 ATTN_BLOCK=0 4": "plain na2d_bf16 ffn_bf16+out | mx8 na2d_bf16 up=mx8,down=mx8 | plain global_bf16 up=plain",
+    "fp8 ATTN_BLOCK=0 32": "plain na2d_bf16 ffn_bf16+out | mx8 na2d_bf16 up=mx8,down=mx8 | mx8 global_bf16 up=mx8,down=mx8",
+    "fp8 ATTN_BLOCK=force 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | attn_block - up=plain",
+    "fp8 ATTN_BLOCK=force 4": "plain na2d_bf16 ffn_bf16+out | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=plain",
+    "fp8 ATTN_BLOCK=force 32": "plain na2d_bf16 ffn_bf16+out | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=mx8,down=mx8",
+    "fp8 PROJ_BLOCK=0 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "fp8 PROJ_BLOCK=0 4": "plain na2d_bf16 ffn_bf16+out | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=plain",
+    "fp8 PROJ_BLOCK=0 32": "plain na2d_bf16 ffn_bf16+out | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=mx8,down=mx8",
+    "fp8 FFN_OUT=0 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "fp8 FFN_OUT=0 4": "plain na2d_bf16 ffn_bf16 | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=plain",
+    "fp8 FFN_OUT=0 32": "plain na2d_bf16 ffn_bf16 | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=mx8,down=mx8",
+    "fp8 FFN_OUT=1 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "fp8 FFN_OUT=1 4": "plain na2d_bf16 ffn_bf16+out | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=plain",
+    "fp8 FFN_OUT=1 32": "plain na2d_bf16 ffn_bf16+out | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=mx8,down=mx8",
+    "fp8 FFN_OUT=256 1": "plain na2d_bf16 up=plain | plain na2d_bf16 up=plain | plain global_bf16 up=plain",
+    "fp8 FFN_OUT=256 4": "plain na2d_bf16 ffn_bf16 | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=plain",
+    "fp8 FFN_OUT=256 32": "plain na2d_bf16 ffn_bf16 | mx8 na2d_bf16 up=mx8,down=mx8 | attn_block - up=mx8,down=mx8",
+}
+
+
+def _route_code(r):
+    s = f"{r.qkv} {r.core[len('kd_attn_'):] if r.core else '-'} "
+    if r.ff != "pair":
+        return s + r.ff[len("kd_"):] + ("+out" if r.fuse_out else "")
+    return s + "up=" + r.up + (",down=mx8" if r.down_mx8 else "")
+
+
+def test_layer_routing_of_the_headline_config(KD):
+    """route_layer asks host-side predicates of the library only, so a plan's kernels can be read off without a GPU.
+    kd_ffn_f32_supported asks the device for its CU count and takes 256 when there is none: the MI355X has 256 CUs, so these
+    are the answers of the GPU machine."""
+    import json
+    itv2 = KD.models.image_transformer_v2
+    nat = KD._native
+    cfg = KD.config.load_config(json.load(open(os.path.join(REPO, "configs", "config_oxford_flowers.json"))))
+    model = KD.config.make_model(cfg)
+    (H, W), (ph, pw) = cfg["model"]["input_size"], model.patch_size
+    modes = {"exact": nat.PREC_EXACT, "split3": nat.PREC_SPLIT3, "bf16": nat.PREC_BF16, "fp8": nat.PREC_FP8}
+    lib = nat.lib()
+    for key, want in FLOWERS_ROUTES.items():
+        mode, *switch, B = key.split()
+        switches = dict(itv2.PLAN_SWITCHES)
+        switches.update(("KDIFF_" + s.split("=")[0], s.split("=")[1]) for s in switch)
+        got = []
+        for li, lv in enumerate(model.level_specs):
+            rps = (H // ph >> li) * (W // pw >> li)
+            kind = {"NeighborhoodAttentionSpec": "neighborhood", "GlobalAttentionSpec": "global"}[type(lv.self_attn).__name__]
+            got.append(_route_code(itv2.route_layer(lib, modes[mode], int(B), int(B) * rps, rps, lv.width, lv.d_ff,
+                                                    lv.width // lv.self_attn.d_head, kind, switches)))
+        assert " | ".join(got) == want, key
