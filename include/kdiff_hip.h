@@ -370,6 +370,49 @@ int kd_brownian_cached_f32(float* out, float* w0, float* w1, int have0, int have
 int kd_randn_f32(float* out, const unsigned long long* seeds, int batch, long long per_sample, unsigned long long draw, float scale,
                  void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Forward-mode derivatives (tangents) for log_likelihood (k_diffusion/sampling.py:280-301), fp32 arithmetic: a DUAL pass runs the
+ * primal x and its tangent x_dot side by side.  The reference takes v . (v^T J) with a reverse-mode pass through the model; this
+ * package takes v^T (J v) forward.  The linear pieces of the network run their tangent on kd_gemm_f32; these are the nonlinear ones.
+ * Products are fp32 FMAs on the vector ALU; every reduction has a fixed order (bit-identical on repeat, no atomics).
+ *   kd_rmsnorm_jvp_f32 : rms_norm / AdaRMSNorm (image_transformer_v2.py:98-103, :142-166), rows x d (d % 4 == 0, scale_stride % 4 == 0):
+ *                        r = rsqrt(mean(x^2) + eps), s = scale[(row / rows_per_sample) * scale_stride + :] (stride 0: a shared gain),
+ *                        y = s * x * r,  y_dot = s * (x_dot * r - x * r^3 * mean(x * x_dot)).
+ *   kd_geglu_jvp_f32   : linear_geglu's gate (:89-95): h = [a | g] rows of 2 d_ff (value first), y = a * gelu(g),
+ *                        y_dot = a_dot * gelu(g) + a * gelu'(g) * g_dot, erf-GELU with gelu'(g) = Phi(g) + g * phi(g).
+ *   kd_qk_prep_jvp_f32 : kd_qk_prep_f32 (:106-121, :187-231) in place on qkv AND its tangent qkv_dot (same layout and tables): with
+ *                        rho = rsqrt(sum q^2 + eps), c = sqrt(scale_h), q' = c q rho, q'_dot = c (q_dot rho - q rho^3 (q . q_dot)), then
+ *                        the same RoPE rotation of both.
+ *   kd_attn_{global,window,na2d}_jvp_f32 : softmax attention (scale 1.0) on prepared q, k and its tangent, geometry as the fp32 cores
+ *                        (global: any T; window: ws 4 / 8 / 16, shift 0 .. ws-1 under the reference's mask, :253-337; neighbourhood:
+ *                        odd ks 3 .. 13, clamped window, H, W >= ks): with l_j = q . k_j and l_dot_j = q_dot . k_j + q . k_dot_j,
+ *                        o = sum e_j v_j / Z and o_dot = (sum e_j l_dot_j v_j + sum e_j v_dot_j) / Z - (sum e_j l_dot_j / Z) o.
+ *                        out / out_dot: [tokens, nh * 64].
+ *   kd_ll_div_f32      : d = (x - D) / sigma_b (to_d, sampling.py:46) and d_ll[b] = sum over sample b of v * (v - D_dot) / sigma_b
+ *                        (the divergence of d along v: v . J_d v).  sigma: [batch] device floats.
+ *   kd_gauss_logp_f32  : out[b] = add[b] + sum over sample b of log N(z; 0, sigma^2) (add may be NULL).
+ *   kd_rk_combine_f32  : out = y0 + sum_j c[j] * k[j]  (y0 may be NULL), nk <= 7 terms; k (device pointers) and c are HOST arrays read
+ *                        at the call.
+ *   kd_rk_error_f32    : kd_rk_error_partials() per-workgroup partial sums, on a fixed grid, of
+ *                        (sum_j c[j] k[j] / (atol + rtol * max(|y0|, |y1|)))^2 (y1 NULL: |y0| alone); the caller adds them up. */
+int kd_rmsnorm_jvp_f32(const float* x, const float* x_dot, const float* scale, int scale_stride, int rows_per_sample, float* y, float* y_dot,
+                       int rows, int d, float eps, void* stream);
+int kd_geglu_jvp_f32(const float* h, const float* h_dot, float* y, float* y_dot, int rows, int d_ff, void* stream);
+int kd_qk_prep_jvp_f32(float* qkv, float* qkv_dot, const float* scale_h, const float* cos_t, const float* sin_t, int batch,
+                       int tokens_per_sample, int nh, float eps, void* stream);
+int kd_attn_global_jvp_f32(const float* qkv, const float* qkv_dot, float* out, float* out_dot, int batch, int T, int nh, void* stream);
+int kd_attn_window_jvp_f32(const float* qkv, const float* qkv_dot, float* out, float* out_dot, int batch, int H, int W, int nh, int ws,
+                           int shift, void* stream);
+int kd_attn_na2d_jvp_f32(const float* qkv, const float* qkv_dot, float* out, float* out_dot, int batch, int H, int W, int nh, int ks,
+                         void* stream);
+int kd_ll_div_f32(const float* x, const float* D, const float* D_dot, const float* v, const float* sigma, float* d, float* d_ll, int batch,
+                  long long per_sample, void* stream);
+int kd_gauss_logp_f32(const float* z, float sigma, const float* add, float* out, int batch, long long per_sample, void* stream);
+int kd_rk_combine_f32(float* out, const float* y0, const float* const* k, const float* c, int nk, long long n, void* stream);
+int kd_rk_error_partials(void);
+int kd_rk_error_f32(const float* const* k, const float* c, int nk, const float* y0, const float* y1, float atol, float rtol, long long n,
+                    float* partial, void* stream);
+
 /* Final image conversion (k_diffusion/utils.py:27-34 to_pil_image): u8 = trunc((clamp(x,-1,1)+1)/2*255)
  * (torchvision's to_pil_image does mul(255).byte(), i.e. truncation) */
 int kd_to_uint8(const float* x, unsigned char* y, long long n, void* stream);

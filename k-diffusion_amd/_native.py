@@ -131,6 +131,17 @@ SIGNATURES = {
     "kd_randn_f32": [_vp, _vp, _i, _ll, C.c_ulonglong, _f, _vp],
     "kd_to_uint8": [_vp, _vp, _ll, _vp],
     "kd_norm_split_f32": [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp],
+    "kd_rmsnorm_jvp_f32": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp],
+    "kd_geglu_jvp_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp],
+    "kd_qk_prep_jvp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "kd_attn_global_jvp_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "kd_attn_window_jvp_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "kd_attn_na2d_jvp_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "kd_ll_div_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _vp],
+    "kd_gauss_logp_f32": [_vp, _f, _vp, _vp, _i, _ll, _vp],
+    "kd_rk_combine_f32": [_vp, _vp, _vp, _vp, _i, _ll, _vp],
+    "kd_rk_error_partials": [],
+    "kd_rk_error_f32": [_vp, _vp, _i, _vp, _vp, _f, _f, _ll, _vp, _vp],
     "kd_prof_enable": [_i],
     "kd_prof_count": [],
     "kd_prof_get": [_i, C.c_char_p, _i, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double)],

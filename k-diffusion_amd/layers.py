@@ -54,6 +54,24 @@ class Denoiser(nn.Module):
         return ops.precond_out(f.contiguous(), x, sigma, self.sigma_data)
 
 
+    def forward_jvp(self, input, sigma, tangent, **kwargs):
+        """(D(input, sigma), J_D tangent): the forward-mode derivative of the denoiser along ``tangent``, sigma and the conditioning held
+        fixed (what ``likelihood.log_likelihood`` needs).  A native inner model runs its dual pass with the preconditioning folded in; a
+        foreign inner model needs a ``forward_jvp(x, sigma, x_dot, **kwargs) -> (F, F_dot)`` of its own, and the preconditioning -- linear
+        in x -- goes through the same kernels as in ``forward``."""
+        inner = self.inner_model
+        rule = getattr(inner, 'forward_jvp', None)
+        if rule is None:
+            raise NotImplementedError(f'Denoiser.forward_jvp: the inner model {type(inner).__name__} has no forward_jvp rule (a forward-mode '
+                                      f'JVP rule is needed for log_likelihood on the HIP path)')
+        if getattr(inner, 'forward_preconditioned', None) is not None:
+            return rule(input, sigma, tangent, sigma_data=self.sigma_data, **kwargs)
+        sigma = sigma.to(device=input.device, dtype=torch.float32).reshape(-1).expand(input.shape[0]).contiguous()
+        x, xd = input.contiguous(), tangent.contiguous()
+        f, fd = rule(ops.precond_in(x, sigma, self.sigma_data), sigma, ops.precond_in(xd, sigma, self.sigma_data), **kwargs)
+        return ops.precond_out(f.contiguous(), x, sigma, self.sigma_data), ops.precond_out(fd.contiguous(), xd, sigma, self.sigma_data)
+
+
 class DenoiserWithVariance(Denoiser):
     """What ``make_denoiser_wrapper`` returns for ``has_variance`` configs (config.py:223-224; layers.py:93-101).  The reference's class
     overrides ``loss`` only (the model's log-variance output is a training quantity): ``forward`` / ``get_scalings`` -- the sampling path --

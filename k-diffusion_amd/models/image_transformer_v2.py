@@ -802,6 +802,12 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         with c_in folded into the patch gather and c_out / c_skip into the un-patch scatter."""
         return self._run(x, sigma, aug_cond, class_cond, mapping_cond, sigma_data)
 
+    def forward_jvp(self, x, sigma, x_dot, aug_cond=None, class_cond=None, mapping_cond=None, sigma_data=None):
+        """Dual pass (forward-mode JVP, models/jvp.py): (F(x, sigma), J_F x_dot) with the conditioning held fixed, or with ``sigma_data``
+        the same for the Karras denoiser D(x) = F(x c_in) c_out + x c_skip.  fp32 in every arithmetic mode; no launch plan involved."""
+        from . import jvp
+        return jvp.forward_jvp(self, x, sigma, x_dot, aug_cond=aug_cond, class_cond=class_cond, mapping_cond=mapping_cond, sigma_data=sigma_data)
+
     @torch.no_grad()
     def _run(self, x, sigma, aug_cond, class_cond, mapping_cond, sigma_data):
         if class_cond is None and self.class_emb is not None:

@@ -582,3 +582,139 @@ def to_uint8(x, out=None):
         return out
     nat.check(nat.lib().kd_to_uint8(_p(_chk(x, "x")), _p(_chk(out, "y", torch.uint8)), x.numel(), _stream()), "kd_to_uint8")
     return out
+
+
+# ---- forward-mode (tangent) ops of the dual pass (log_likelihood; csrc/jvp_f32.hip).  fp32 tensors only: the dual pass is fp32 whatever
+# KDIFF_GEMM says.  Each takes the primal and its tangent and returns both.
+
+def rms_norm_jvp(x, x_dot, scale, rows_per_sample=None, eps=1e-6):
+    """rms_norm / AdaRMSNorm (:98-103, :155-166) and its tangent.  x, x_dot: [..., d]; ``scale``: [d] shared gain, or [B, d] per-sample
+    AdaRMSNorm scales with ``rows_per_sample`` rows each."""
+    d = x.shape[-1]
+    rows = x.numel() // d
+    y, yd = torch.empty_like(x), torch.empty_like(x)
+    stride = 0 if scale.dim() == 1 else scale.shape[-1]
+    rps = rows if stride == 0 else (rows_per_sample or rows // scale.shape[0])
+    nat.check(nat.lib().kd_rmsnorm_jvp_f32(_p(_chk(x, "x")), _p(_chk(x_dot, "x_dot")), _p(_chk(scale, "scale")), stride, rps, _p(y), _p(yd), rows, d,
+                                           float(eps), _stream()), "kd_rmsnorm_jvp_f32")
+    return y, yd
+
+
+def geglu_jvp(h, h_dot):
+    """linear_geglu's gate (:89-95) on a projection [..., 2 d_ff] (value first) and its tangent -> ([..., d_ff], [..., d_ff])."""
+    d_ff = h.shape[-1] // 2
+    rows = h.numel() // h.shape[-1]
+    y = torch.empty(*h.shape[:-1], d_ff, device=h.device, dtype=torch.float32)
+    yd = torch.empty_like(y)
+    nat.check(nat.lib().kd_geglu_jvp_f32(_p(_chk(h, "h")), _p(_chk(h_dot, "h_dot")), _p(y), _p(yd), rows, d_ff, _stream()), "kd_geglu_jvp_f32")
+    return y, yd
+
+
+def qk_prep_jvp_(qkv, qkv_dot, scale_h, cos_t, sin_t, nh, eps=1e-6):
+    """``qk_prep_`` (:106-121, :187-231) in place on qkv [B, ..., 3*nh*64] and on its tangent."""
+    _qkv_dims(qkv, nh)
+    B = qkv.shape[0]
+    T = qkv.numel() // (B * 3 * nh * 64)
+    nat.check(nat.lib().kd_qk_prep_jvp_f32(_p(_chk(qkv, "qkv")), _p(_chk(qkv_dot, "qkv_dot")), _p(_chk(scale_h, "scale")), _p(_chk(cos_t, "cos")),
+                                           _p(_chk(sin_t, "sin")), B, T, nh, float(eps), _stream()), "kd_qk_prep_jvp_f32")
+    return qkv, qkv_dot
+
+
+def _attn_jvp_out(qkv, qkv_dot, nh):
+    _qkv_dims(qkv, nh)
+    if qkv_dot.shape != qkv.shape:
+        raise ValueError(f"tangent shape {tuple(qkv_dot.shape)} != primal shape {tuple(qkv.shape)}")
+    _chk(qkv, "qkv"), _chk(qkv_dot, "qkv_dot")
+    out = torch.empty(*qkv.shape[:-1], nh * 64, device=qkv.device, dtype=torch.float32)
+    return out, torch.empty_like(out)
+
+
+def attn_global_jvp(qkv, qkv_dot, nh):
+    """Dense softmax attention (:383, :392) on prepared q, k and its tangent: qkv [B, T..., 3*nh*64] -> (o, o_dot) [B, T..., nh*64]."""
+    out, od = _attn_jvp_out(qkv, qkv_dot, nh)
+    B = qkv.shape[0]
+    T = qkv.numel() // (B * 3 * nh * 64)
+    nat.check(nat.lib().kd_attn_global_jvp_f32(_p(qkv), _p(qkv_dot), _p(out), _p(od), B, T, nh, _stream()), "kd_attn_global_jvp_f32")
+    return out, od
+
+
+def attn_window_jvp(qkv, qkv_dot, nh, window_size, shift):
+    """Shifted-window attention (:253-337) and its tangent: qkv [B, H, W, 3*nh*64]."""
+    out, od = _attn_jvp_out(qkv, qkv_dot, nh)
+    B, H, W, _ = qkv.shape
+    nat.check(nat.lib().kd_attn_window_jvp_f32(_p(qkv), _p(qkv_dot), _p(out), _p(od), B, H, W, nh, window_size, shift, _stream()),
+              "kd_attn_window_jvp_f32")
+    return out, od
+
+
+def attn_na2d_jvp(qkv, qkv_dot, nh, kernel_size):
+    """Neighbourhood attention (natten na2d, :428; clamped window) and its tangent: qkv [B, H, W, 3*nh*64]."""
+    out, od = _attn_jvp_out(qkv, qkv_dot, nh)
+    B, H, W, _ = qkv.shape
+    nat.check(nat.lib().kd_attn_na2d_jvp_f32(_p(qkv), _p(qkv_dot), _p(out), _p(od), B, H, W, nh, kernel_size, _stream()), "kd_attn_na2d_jvp_f32")
+    return out, od
+
+
+def ll_div(x, denoised, denoised_dot, v, sigma):
+    """(d, d_ll): d = (x - D) / sigma (to_d, sampling.py:46) and d_ll[b] = sum_b v * (v - D_dot) / sigma_b.  sigma: [B] fp32."""
+    B = x.shape[0]
+    d = torch.empty_like(x)
+    d_ll = torch.empty(B, device=x.device, dtype=torch.float32)
+    for name, t in (("denoised", denoised), ("denoised_dot", denoised_dot), ("v", v)):
+        if _chk(t, name).shape != x.shape:
+            raise ValueError(f"ll_div: {name} shape {tuple(t.shape)} != x shape {tuple(x.shape)}")
+    if _chk(sigma, "sigma").numel() != B:
+        raise ValueError(f"ll_div: {sigma.numel()} sigmas for batch {B}")
+    nat.check(nat.lib().kd_ll_div_f32(_p(_chk(x, "x")), _p(denoised), _p(denoised_dot), _p(v), _p(sigma), _p(d), _p(d_ll), B, x.numel() // B,
+                                      _stream()), "kd_ll_div_f32")
+    return d, d_ll
+
+
+def gauss_logp(z, sigma, add=None):
+    """[B]: add[b] + sum over sample b of log N(z; 0, sigma^2) (torch.distributions.Normal(0, sigma).log_prob(z).flatten(1).sum(1))."""
+    B = z.shape[0]
+    out = torch.empty(B, device=z.device, dtype=torch.float32)
+    nat.check(nat.lib().kd_gauss_logp_f32(_p(_chk(z, "z")), float(sigma), None if add is None else _p(_chk(add, "add")), _p(out), B, z.numel() // B,
+                                          _stream()), "kd_gauss_logp_f32")
+    return out
+
+
+def _rk_terms(ks, coeffs, n):
+    if not 1 <= len(ks) <= 7 or len(ks) != len(coeffs):
+        raise ValueError(f"1 .. 7 terms with one coefficient each (got {len(ks)}, {len(coeffs)})")
+    for t in ks:
+        if _chk(t, "k").numel() != n:
+            raise ValueError(f"term has {t.numel()} elements, expected {n}")
+    ptrs = (C.c_void_p * len(ks))(*[t.data_ptr() for t in ks])
+    cf = (C.c_float * len(ks))(*[float(c) for c in coeffs])
+    return C.cast(ptrs, C.c_void_p), C.cast(cf, C.c_void_p), (ptrs, cf)
+
+
+def rk_combine(y0, ks, coeffs, out=None):
+    """out = y0 + sum_j coeffs[j] * ks[j] (y0 may be None; at most 7 terms): the stage sums of an explicit Runge-Kutta step."""
+    ref = ks[0]
+    out = torch.empty_like(ref) if out is None else out
+    kp, cp, keep = _rk_terms(ks, coeffs, ref.numel())
+    if y0 is not None and _chk(y0, "y0").numel() != ref.numel():
+        raise ValueError("rk_combine: y0 size")
+    nat.check(nat.lib().kd_rk_combine_f32(_p(_chk(out, "out")), _p(y0), kp, cp, len(ks), ref.numel(), _stream()), "kd_rk_combine_f32")
+    del keep
+    return out
+
+
+def rk_error_sq(ks, coeffs, y0, y1, atol, rtol):
+    """sum over all elements of (sum_j coeffs[j] ks[j] / (atol + rtol * max(|y0|, |y1|)))^2 as a python float (one host sync): the square
+    sum behind a Runge-Kutta error ratio.  y1 None: the scale is atol + rtol * |y0|."""
+    return float(rk_error_partial(ks, coeffs, y0, y1, atol, rtol).double().sum().item())
+
+
+def rk_error_partial(ks, coeffs, y0, y1, atol, rtol):
+    """``rk_error_sq`` left on the device: its fixed grid of partial sums (fp32 [kd_rk_error_partials()]), for a caller that gathers
+    several of them in one host read."""
+    n = _chk(y0, "y0").numel()
+    kp, cp, keep = _rk_terms(ks, coeffs, n)
+    part = torch.empty(nat.lib().kd_rk_error_partials(), device=y0.device, dtype=torch.float32)
+    nat.check(nat.lib().kd_rk_error_f32(kp, cp, len(ks), _p(y0), None if y1 is None else _p(_chk(y1, "y1")), float(atol), float(rtol), n, _p(part),
+                                        _stream()), "kd_rk_error_f32")
+    del keep
+    return part
