@@ -413,6 +413,41 @@ int kd_rk_error_partials(void);
 int kd_rk_error_f32(const float* const* k, const float* c, int nk, const float* y0, const float* y1, float atol, float rtol, long long n,
                     float* partial, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Reverse-mode derivatives (vector-Jacobian products) for gradients w.r.t. the denoiser's input (gradient guidance,
+ * k_diffusion/sampling.py:286-294's autograd form of log_likelihood), fp32 arithmetic.  The backward pass recomputes the primal on the
+ * unfused fp32 path and walks the network in reverse; its linear pieces run on kd_gemm_f32 with transposed weights, these are the others.
+ * The conditioning and the weights are held fixed.  Products are fp32 FMAs on the vector ALU; every reduction has a fixed order
+ * (bit-identical on repeat, no atomics).
+ *   kd_rmsnorm_vjp_f32 : rms_norm / AdaRMSNorm (image_transformer_v2.py:98-103, :142-166), rows x d (d % 4 == 0, scale_stride % 4 == 0),
+ *                        scale as in kd_rmsnorm_jvp_f32: r = rsqrt(mean(x^2) + eps), g_x = s * g_y * r - x * r^3 * mean(x * s * g_y)
+ *                        (+ g_add, the gradient a residual add passes through; NULL for none; g_x may be g_add).
+ *   kd_geglu_vjp_f32   : linear_geglu's gate (:89-95): h = [a | g] rows of 2 d_ff (value first), g_y rows of d_ff ->
+ *                        g_h = [g_y * gelu(g) | g_y * a * gelu'(g)], erf-GELU.
+ *   kd_qk_prep_vjp_f32 : the transpose of kd_qk_prep_f32 (:106-121, :187-231) at the UNPREPARED qkv: g_qkv (the gradient w.r.t. the
+ *                        prepared q, k) is rewritten in place, u = R^T g, g_q = c rho u - c rho^3 q (q . u) with rho = rsqrt(sum q^2 + eps),
+ *                        c = sqrt(scale_h); the v part of g_qkv is left as it is.
+ *   kd_attn_{global,window,na2d}_vjp_f32 : softmax attention (scale 1.0) on prepared q, k, geometry and limits as the _jvp_ cores: g_out
+ *                        [tokens, nh * 64] -> g_qkv [tokens, 3 * nh * 64] (every element written).  Two launches (flash-attention-2): a
+ *                        query sweep that writes g_q and the per-query log-sum-exp / rowsum(dO * O) into lse / dsum ([batch, nh, T]
+ *                        device workspace), then a key sweep over the queries that attend each key (neighbourhood: the inverse window,
+ *                        which near a border holds more than ks queries per axis) that writes g_k, g_v.
+ *   kd_precond_vjp_f32 : y = coef(g_coef) * g + coef(h_coef) * h per sample (h may be NULL), coef one of the KD_PC_* Karras scalings of
+ *                        sigma[b] (layers.py:70-74): the transposes of the preconditioning (D = F(x c_in) c_out + x c_skip). */
+enum { KD_PC_ONE = 0, KD_PC_SKIP = 1, KD_PC_OUT = 2, KD_PC_IN = 3 };
+int kd_rmsnorm_vjp_f32(const float* x, const float* g_y, const float* scale, int scale_stride, int rows_per_sample, const float* g_add, float* g_x,
+                       int rows, int d, float eps, void* stream);
+int kd_geglu_vjp_f32(const float* h, const float* g_y, float* g_h, int rows, int d_ff, void* stream);
+int kd_qk_prep_vjp_f32(const float* qkv, float* g_qkv, const float* scale_h, const float* cos_t, const float* sin_t, int batch,
+                       int tokens_per_sample, int nh, float eps, void* stream);
+int kd_attn_global_vjp_f32(const float* qkv, const float* g_out, float* g_qkv, float* lse, float* dsum, int batch, int T, int nh, void* stream);
+int kd_attn_window_vjp_f32(const float* qkv, const float* g_out, float* g_qkv, float* lse, float* dsum, int batch, int H, int W, int nh, int ws,
+                           int shift, void* stream);
+int kd_attn_na2d_vjp_f32(const float* qkv, const float* g_out, float* g_qkv, float* lse, float* dsum, int batch, int H, int W, int nh, int ks,
+                         void* stream);
+int kd_precond_vjp_f32(const float* g, int g_coef, const float* h, int h_coef, const float* sigma, float sigma_data, float* y, int batch,
+                       long long per_sample, void* stream);
+
 /* Final image conversion (k_diffusion/utils.py:27-34 to_pil_image): u8 = trunc((clamp(x,-1,1)+1)/2*255)
  * (torchvision's to_pil_image does mul(255).byte(), i.e. truncation) */
 int kd_to_uint8(const float* x, unsigned char* y, long long n, void* stream);

@@ -13,6 +13,7 @@
 // Products are plain fp32 FMAs on the VALU (no bf16 splits): the tangent carries fp32 rounding only.  Every reduction has a fixed
 // shape and order (shuffle trees, one workgroup per sample or a fixed grid of partials): no atomics, bit-identical on repeat.
 #include "kd_common.h"
+#include "deriv_f32.h"
 
 #include <cmath>
 
@@ -22,8 +23,6 @@ namespace {
 
 constexpr int JDH = 64;                 // head dim
 constexpr float NEG_INF = -__builtin_huge_valf();
-
-__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
 
 // ---- RMSNorm: one wave per row -------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rmsnorm_jvp_kernel(const float* __restrict__ x, const float* __restrict__ xd, const float* __restrict__ scale,
@@ -71,15 +70,7 @@ __global__ __launch_bounds__(256) void geglu_jvp_kernel(const float* __restrict_
   }
 }
 
-// ---- q/k preparation: 16 lanes per 64-float row, lane c owns dims [4c, 4c+4) ---------------------------------------------
-__device__ __forceinline__ f32x4 rope16(f32x4 v, int c, f32x4 cs, f32x4 sn) {
-  f32x4 up, dn;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) { up[u] = dpp_mov<DPP_ROR12>(v[u]); dn[u] = dpp_mov<DPP_ROR4>(v[u]); }
-  const f32x4 rot = (c < 4) ? (v * cs - up * sn) : (v * cs + dn * sn);
-  return c < 8 ? rot : v;
-}
-
+// ---- q/k preparation: 16 lanes per 64-float row, lane c owns dims [4c, 4c+4) (rope16: deriv_f32.h) -------------------------
 __global__ __launch_bounds__(256) void qk_prep_jvp_kernel(float* qkv, float* qkvd, const float* scale_h, const float* cos_t, const float* sin_t,
                                                           long rows_total, int tokens_per_sample, int nh, float eps) {
   const long g = ((long)blockIdx.x * 256 + threadIdx.x) >> 4;
@@ -109,7 +100,7 @@ __global__ __launch_bounds__(256) void qk_prep_jvp_kernel(float* qkv, float* qkv
   *reinterpret_cast<f32x4*>(qkvd + off) = rope16(qd, c, cs, sn);
 }
 
-// ---- attention: one template, three key-set policies -------------------------------------------------------------------
+// ---- attention: one template, three key-set policies (KeySet: deriv_f32.h) ----------------------------------------------
 // A workgroup of 256 lanes serves 16 queries of one (sample, head) -- a 16-lane group per query, lane c owning dims [4c, 4c+4) of q, qd
 // and of the accumulators -- over a key set they share: all T tokens (global), the window (shifted window; the reference's region mask is
 // a per-pair predicate), or the union of the queries' clamped neighbourhoods for a 4x4 query tile (neighbourhood; the predicate keeps each
@@ -117,7 +108,6 @@ __global__ __launch_bounds__(256) void qk_prep_jvp_kernel(float* qkv, float* qkv
 // l_j = q.k_j and their tangents ld_j = qd.k_j + q.kd_j are kept in registers, the running maximum moves once, and
 //   Z = sum e_j,  S = sum e_j ld_j,  A = sum e_j v_j,  B = sum e_j ld_j v_j,  C = sum e_j vd_j      (e_j = exp(l_j - m))
 // give o = A / Z and od = (B + C) / Z - (S / Z) o.
-enum { JVP_GLOBAL = 0, JVP_WINDOW = 1, JVP_NA = 2 };
 constexpr int JKC = 32;                          // keys per LDS chunk
 constexpr int JVP_LDS = JKC * 4 * JDH * 4;       // 32 KiB
 
@@ -125,74 +115,6 @@ struct AttnJvpArgs {
   const float* qkv; const float* qkvd; float* out; float* outd;
   int batch, nh, T, H, W, geo, shift;            // geo: window size (window) or kernel size (neighbourhood)
   int blocks_per_head;                           // query blocks per (sample, head)
-};
-
-__device__ __forceinline__ int na_start(int i, int len, int ks) { return min(max(i - ks / 2, 0), len - ks); }
-__device__ __forceinline__ int wrap(int i, int n) { return ((i % n) + n) % n; }
-
-template <int MODE>
-struct KeySet {
-  // query side
-  int qtok; bool qactive;
-  int q_a, q_b;                 // window: region id parts / neighbourhood: window start row, col
-  // key side
-  int n_keys;
-  int base_r, base_c, span_c;   // window: window origin (rows, cols of the rolled grid) / neighbourhood: halo origin and width
-  int win_top, win_left;        // window: the window is in the top row / left column of windows
-
-  __device__ void init(const AttnJvpArgs& a, int qb, int g) {
-    if (MODE == JVP_GLOBAL) {
-      const int t = qb * 16 + g;
-      qactive = t < a.T;
-      qtok = min(t, a.T - 1);
-      n_keys = a.T;
-    } else if (MODE == JVP_WINDOW) {
-      const int ws = a.geo, per_win = ws * ws / 16, nww = a.W / ws;
-      const int win = qb / per_win, s = (qb % per_win) * 16 + g;
-      const int wi = win / nww, wj = win % nww;
-      base_r = wi * ws; base_c = wj * ws;
-      win_top = wi == 0; win_left = wj == 0;
-      const int qa = s / ws, qc = s % ws;
-      qtok = wrap(base_r + qa - a.shift, a.H) * a.W + wrap(base_c + qc - a.shift, a.W);
-      q_a = win_top ? (qa < a.shift) : 0;
-      q_b = win_left ? (qc < a.shift) : 0;
-      qactive = true;
-      n_keys = ws * ws;
-    } else {
-      const int ks = a.geo, tw = (a.W + 3) / 4;
-      const int th = qb / tw, tc = qb % tw;
-      const int r0 = th * 4, c0 = tc * 4;
-      const int qr = r0 + (g >> 2), qc = c0 + (g & 3);
-      qactive = qr < a.H && qc < a.W;
-      const int qr_c = min(qr, a.H - 1), qc_c = min(qc, a.W - 1);
-      qtok = qr_c * a.W + qc_c;
-      q_a = na_start(qr_c, a.H, ks);
-      q_b = na_start(qc_c, a.W, ks);
-      base_r = na_start(r0, a.H, ks);
-      base_c = na_start(c0, a.W, ks);
-      const int r_hi = na_start(min(r0 + 3, a.H - 1), a.H, ks) + ks, c_hi = na_start(min(c0 + 3, a.W - 1), a.W, ks) + ks;
-      span_c = c_hi - base_c;
-      n_keys = (r_hi - base_r) * span_c;
-    }
-  }
-  __device__ int key_tok(const AttnJvpArgs& a, int j) const {
-    if (MODE == JVP_GLOBAL) return j;
-    if (MODE == JVP_WINDOW) {
-      const int ws = a.geo, ka = j / ws, kc = j % ws;
-      return wrap(base_r + ka - a.shift, a.H) * a.W + wrap(base_c + kc - a.shift, a.W);
-    }
-    return (base_r + j / span_c) * a.W + base_c + j % span_c;
-  }
-  __device__ bool allowed(const AttnJvpArgs& a, int j) const {
-    if (j >= n_keys) return false;
-    if (MODE == JVP_GLOBAL) return true;
-    if (MODE == JVP_WINDOW) {
-      const int ws = a.geo, ka = j / ws, kc = j % ws;
-      return (win_top ? (ka < a.shift) : 0) == q_a && (win_left ? (kc < a.shift) : 0) == q_b;
-    }
-    const int r = base_r + j / span_c, cc = base_c + j % span_c;
-    return r >= q_a && r < q_a + a.geo && cc >= q_b && cc < q_b + a.geo;
-  }
 };
 
 template <int MODE>
@@ -400,7 +322,7 @@ extern "C" int kd_qk_prep_jvp_f32(float* qkv, float* qkv_dot, const float* scale
 extern "C" int kd_attn_global_jvp_f32(const float* qkv, const float* qkv_dot, float* out, float* out_dot, int batch, int T, int nh, void* stream) {
   if (!qkv || !qkv_dot || !out || !out_dot || batch <= 0 || T <= 0 || nh <= 0) return fail(KD_EINVAL, "kd_attn_global_jvp_f32: bad arguments");
   AttnJvpArgs a{qkv, qkv_dot, out, out_dot, batch, nh, T, 1, T, 0, 0, (T + 15) / 16};
-  return launch_attn_jvp<JVP_GLOBAL>(a, "attn_global_jvp_f32", (hipStream_t)stream);
+  return launch_attn_jvp<KS_GLOBAL>(a, "attn_global_jvp_f32", (hipStream_t)stream);
 }
 
 extern "C" int kd_attn_window_jvp_f32(const float* qkv, const float* qkv_dot, float* out, float* out_dot, int batch, int H, int W, int nh, int ws,
@@ -410,7 +332,7 @@ extern "C" int kd_attn_window_jvp_f32(const float* qkv, const float* qkv_dot, fl
   if ((H % ws) || (W % ws)) return fail(KD_EINVAL, "kd_attn_window_jvp_f32: grid %dx%d not divisible by the window", H, W);
   if (shift < 0 || shift >= ws) return fail(KD_EINVAL, "kd_attn_window_jvp_f32: bad shift %d", shift);
   AttnJvpArgs a{qkv, qkv_dot, out, out_dot, batch, nh, H * W, H, W, ws, shift, (H / ws) * (W / ws) * (ws * ws / 16)};
-  return launch_attn_jvp<JVP_WINDOW>(a, "attn_window_jvp_f32", (hipStream_t)stream);
+  return launch_attn_jvp<KS_WINDOW>(a, "attn_window_jvp_f32", (hipStream_t)stream);
 }
 
 extern "C" int kd_attn_na2d_jvp_f32(const float* qkv, const float* qkv_dot, float* out, float* out_dot, int batch, int H, int W, int nh, int ks,
@@ -419,7 +341,7 @@ extern "C" int kd_attn_na2d_jvp_f32(const float* qkv, const float* qkv_dot, floa
   if (ks < 3 || ks > 13 || !(ks & 1)) return fail(KD_EINVAL, "kd_attn_na2d_jvp_f32: kernel_size %d unsupported (odd sizes 3 .. 13)", ks);
   if (H < ks || W < ks) return fail(KD_EINVAL, "kd_attn_na2d_jvp_f32: grid %dx%d smaller than the %dx%d neighbourhood", H, W, ks, ks);
   AttnJvpArgs a{qkv, qkv_dot, out, out_dot, batch, nh, H * W, H, W, ks, 0, ((H + 3) / 4) * ((W + 3) / 4)};
-  return launch_attn_jvp<JVP_NA>(a, "attn_na2d_jvp_f32", (hipStream_t)stream);
+  return launch_attn_jvp<KS_NA>(a, "attn_na2d_jvp_f32", (hipStream_t)stream);
 }
 
 extern "C" int kd_ll_div_f32(const float* x, const float* D, const float* D_dot, const float* v, const float* sigma, float* d, float* d_ll,

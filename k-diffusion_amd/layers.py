@@ -12,6 +12,39 @@ from torch import nn
 from . import ops
 
 
+class _PrecondIn(torch.autograd.Function):
+    """x * c_in (per-sample) with its transpose, the same kernel on the gradient."""
+
+    @staticmethod
+    def forward(ctx, x, sigma, sigma_data):
+        ctx.save_for_backward(sigma)
+        ctx.sigma_data = sigma_data
+        return ops.precond_in(x, sigma, sigma_data)
+
+    @staticmethod
+    def backward(ctx, grad):
+        sigma, = ctx.saved_tensors
+        return ops.precond_in(grad.contiguous(), sigma, ctx.sigma_data), None, None
+
+
+class _PrecondOut(torch.autograd.Function):
+    """f * c_out + x * c_skip (per-sample): the gradient goes to f scaled by c_out and to x scaled by c_skip."""
+
+    @staticmethod
+    def forward(ctx, f, x, sigma, sigma_data):
+        ctx.save_for_backward(sigma)
+        ctx.sigma_data = sigma_data
+        return ops.precond_out(f, x, sigma, sigma_data)
+
+    @staticmethod
+    def backward(ctx, grad):
+        sigma, = ctx.saved_tensors
+        grad = grad.contiguous()
+        gf = ops.precond_vjp(grad, ops.nat.PC_OUT, sigma, ctx.sigma_data) if ctx.needs_input_grad[0] else None
+        gx = ops.precond_vjp(grad, ops.nat.PC_SKIP, sigma, ctx.sigma_data) if ctx.needs_input_grad[1] else None
+        return gf, gx, None, None
+
+
 class Denoiser(nn.Module):
     """D(x, sigma) = F(x * c_in, sigma) * c_out + x * c_skip."""
 
@@ -48,9 +81,19 @@ class Denoiser(nn.Module):
         fused = getattr(inner, 'forward_preconditioned', None)
         if fused is not None:
             return fused(input, sigma, self.sigma_data, **kwargs)
+        if torch.is_grad_enabled() and input.requires_grad and isinstance(sigma, torch.Tensor) and sigma.requires_grad:
+            raise NotImplementedError('Denoiser: gradients w.r.t. sigma through the preconditioning are not implemented (only w.r.t. the '
+                                      'input); pass sigma.detach()')
         sigma = sigma.to(device=input.device, dtype=torch.float32).reshape(-1).expand(input.shape[0]).contiguous()
         x = input.contiguous()
-        f = inner(ops.precond_in(x, sigma, self.sigma_data), sigma, **kwargs)
+        if not torch.is_grad_enabled():
+            f = inner(ops.precond_in(x, sigma, self.sigma_data), sigma, **kwargs)
+            return ops.precond_out(f.contiguous(), x, sigma, self.sigma_data)
+        # a differentiable inner model keeps its graph through the wrapper (layers.py:88-90 is plain autograd in the reference)
+        x_in = _PrecondIn.apply(x, sigma, self.sigma_data) if x.requires_grad else ops.precond_in(x, sigma, self.sigma_data)
+        f = inner(x_in, sigma, **kwargs)
+        if f.requires_grad or x.requires_grad:
+            return _PrecondOut.apply(f.contiguous(), x, sigma, self.sigma_data)
         return ops.precond_out(f.contiguous(), x, sigma, self.sigma_data)
 
 

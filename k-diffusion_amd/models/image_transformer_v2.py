@@ -634,6 +634,35 @@ def _weak_epoch_bump(model):
 
 # ---------------------------------------------------------------------------------- the model
 
+def _wants_input_grad(x):
+    return torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad
+
+
+class _InputGrad(torch.autograd.Function):
+    """The model as an autograd node with x its only differentiable input.  Forward: ``_run`` with its launch plan (the same bits as a
+    no-grad call); saved: the inputs only (x, sigma, the conditioning), no activations.  Backward: ``vjp.backward`` recomputes the primal
+    and returns J^T grad for x."""
+
+    @staticmethod
+    def forward(ctx, x, model, sigma, aug_cond, class_cond, mapping_cond, sigma_data):
+        for name, t in (("sigma", sigma), ("aug_cond", aug_cond), ("class_cond", class_cond), ("mapping_cond", mapping_cond)):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise NotImplementedError(f"ImageTransformerDenoiserModelV2: gradients w.r.t. {name} are not implemented (the backward pass "
+                                          f"differentiates w.r.t. the input x only); pass {name}.detach()")
+        out = model._run(x, sigma, aug_cond, class_cond, mapping_cond, sigma_data)
+        ctx.model, ctx.sigma_data = model, sigma_data
+        ctx.save_for_backward(x, sigma, aug_cond, class_cond, mapping_cond)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        from . import vjp
+        x, sigma, aug_cond, class_cond, mapping_cond = ctx.saved_tensors
+        gx = vjp.backward(ctx.model, x, sigma, grad.to(torch.float32).contiguous(), aug_cond=aug_cond, class_cond=class_cond,
+                          mapping_cond=mapping_cond, sigma_data=ctx.sigma_data)
+        return gx, None, None, None, None, None, None
+
+
 class ImageTransformerDenoiserModelV2(nn.Module):
     def __init__(self, levels, mapping, in_channels, out_channels, patch_size, num_classes=0, mapping_cond_dim=0):
         super().__init__()
@@ -794,12 +823,20 @@ class ImageTransformerDenoiserModelV2(nn.Module):
 
     # ---- forward ---------------------------------------------------------------------------------
     def forward(self, x, sigma, aug_cond=None, class_cond=None, mapping_cond=None):
-        """Inner model F(x, sigma): [B, C, H, W] fp32 on a ROCm device -> [B, C, H, W]."""
+        """Inner model F(x, sigma): [B, C, H, W] fp32 on a ROCm device -> [B, C, H, W].
+
+        Under grad mode with ``x.requires_grad`` the output carries a ``grad_fn`` whose backward is J^T grad w.r.t. x (models/vjp.py);
+        the output itself is the same bits as without grad.  Gradients go to x only: the parameters get none (their ``.grad`` stays None;
+        training is out of scope), and sigma or a conditioning tensor that requires grad is refused with NotImplementedError."""
+        if _wants_input_grad(x):
+            return _InputGrad.apply(x, self, sigma, aug_cond, class_cond, mapping_cond, None)
         return self._run(x, sigma, aug_cond, class_cond, mapping_cond, None)
 
     def forward_preconditioned(self, x, sigma, sigma_data, aug_cond=None, class_cond=None, mapping_cond=None):
         """Denoiser D(x, sigma) = F(x * c_in, sigma) * c_out + x * c_skip (k_diffusion/layers.py:88-90)
-        with c_in folded into the patch gather and c_out / c_skip into the un-patch scatter."""
+        with c_in folded into the patch gather and c_out / c_skip into the un-patch scatter.  Differentiable w.r.t. x as ``forward``."""
+        if _wants_input_grad(x):
+            return _InputGrad.apply(x, self, sigma, aug_cond, class_cond, mapping_cond, sigma_data)
         return self._run(x, sigma, aug_cond, class_cond, mapping_cond, sigma_data)
 
     def forward_jvp(self, x, sigma, x_dot, aug_cond=None, class_cond=None, mapping_cond=None, sigma_data=None):

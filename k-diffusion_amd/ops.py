@@ -655,6 +655,102 @@ def attn_na2d_jvp(qkv, qkv_dot, nh, kernel_size):
     return out, od
 
 
+
+# ---- reverse-mode (vector-Jacobian) ops of the backward pass (gradients w.r.t. the input; csrc/vjp_f32.hip).  fp32 tensors only, whatever
+# KDIFF_GEMM says.  Each takes the primal input of the piece and the gradient on its output and returns the gradient on its input.
+
+def rms_norm_vjp(x, g_y, scale, rows_per_sample=None, eps=1e-6, add=None, out=None):
+    """Input gradient of rms_norm / AdaRMSNorm (:98-103, :155-166), ``scale`` as in ``rms_norm_jvp`` and held fixed.  ``add``: a gradient
+    to add to the result (what a residual add passes through); ``out`` may be ``add``."""
+    d = x.shape[-1]
+    rows = x.numel() // d
+    out = torch.empty_like(x) if out is None else out
+    stride = 0 if scale.dim() == 1 else scale.shape[-1]
+    rps = rows if stride == 0 else (rows_per_sample or rows // scale.shape[0])
+    for name, t in (("g_y", g_y), ("add", add), ("out", out)):
+        if t is not None and _chk(t, name).shape != x.shape:
+            raise ValueError(f"rms_norm_vjp: {name} shape {tuple(t.shape)} != x shape {tuple(x.shape)}")
+    nat.check(nat.lib().kd_rmsnorm_vjp_f32(_p(_chk(x, "x")), _p(g_y), _p(_chk(scale, "scale")), stride, rps, _p(add), _p(out), rows, d, float(eps),
+                                           _stream()), "kd_rmsnorm_vjp_f32")
+    return out
+
+
+def geglu_vjp(h, g_y):
+    """Gradient of linear_geglu's gate (:89-95): the projection h [..., 2 d_ff] (value first) and the gradient on its output [..., d_ff]
+    -> the gradient on h [..., 2 d_ff]."""
+    d_ff = h.shape[-1] // 2
+    rows = h.numel() // h.shape[-1]
+    if _chk(g_y, "g_y").numel() != rows * d_ff:
+        raise ValueError(f"geglu_vjp: g_y has {g_y.numel()} elements, expected {rows * d_ff}")
+    out = torch.empty_like(h)
+    nat.check(nat.lib().kd_geglu_vjp_f32(_p(_chk(h, "h")), _p(g_y), _p(out), rows, d_ff, _stream()), "kd_geglu_vjp_f32")
+    return out
+
+
+def qk_prep_vjp_(qkv, g_qkv, scale_h, cos_t, sin_t, nh, eps=1e-6):
+    """Transpose of ``qk_prep_`` (:106-121, :187-231) at the unprepared ``qkv``: ``g_qkv`` (same layout) holds the gradient w.r.t. the
+    prepared q, k and is rewritten in place with the gradient w.r.t. the unprepared ones; its v part passes through."""
+    _qkv_dims(qkv, nh)
+    if _chk(g_qkv, "g_qkv").shape != qkv.shape:
+        raise ValueError(f"qk_prep_vjp_: gradient shape {tuple(g_qkv.shape)} != qkv shape {tuple(qkv.shape)}")
+    B = qkv.shape[0]
+    T = qkv.numel() // (B * 3 * nh * 64)
+    nat.check(nat.lib().kd_qk_prep_vjp_f32(_p(_chk(qkv, "qkv")), _p(g_qkv), _p(_chk(scale_h, "scale")), _p(_chk(cos_t, "cos")), _p(_chk(sin_t, "sin")),
+                                           B, T, nh, float(eps), _stream()), "kd_qk_prep_vjp_f32")
+    return g_qkv
+
+
+def _attn_vjp_bufs(qkv, g_out, nh):
+    _qkv_dims(qkv, nh)
+    _chk(qkv, "qkv"), _chk(g_out, "g_out")
+    if g_out.shape != (*qkv.shape[:-1], nh * 64):
+        raise ValueError(f"attention gradient shape {tuple(g_out.shape)} != output shape {(*qkv.shape[:-1], nh * 64)}")
+    B = qkv.shape[0]
+    T = qkv.numel() // (B * 3 * nh * 64)
+    stats = torch.empty(2, B, nh, T, device=qkv.device, dtype=torch.float32)       # per-query log-sum-exp, rowsum(dO * O)
+    return torch.empty_like(qkv), stats[0], stats[1]
+
+
+def attn_global_vjp(qkv, g_out, nh):
+    """Gradient of dense softmax attention (:383, :392) on prepared q, k: qkv [B, T..., 3*nh*64], g_out [B, T..., nh*64] -> g_qkv."""
+    g, lse, ds = _attn_vjp_bufs(qkv, g_out, nh)
+    B = qkv.shape[0]
+    T = qkv.numel() // (B * 3 * nh * 64)
+    nat.check(nat.lib().kd_attn_global_vjp_f32(_p(qkv), _p(g_out), _p(g), _p(lse), _p(ds), B, T, nh, _stream()), "kd_attn_global_vjp_f32")
+    return g
+
+
+def attn_window_vjp(qkv, g_out, nh, window_size, shift):
+    """Gradient of shifted-window attention (:253-337): qkv [B, H, W, 3*nh*64]."""
+    g, lse, ds = _attn_vjp_bufs(qkv, g_out, nh)
+    B, H, W, _ = qkv.shape
+    nat.check(nat.lib().kd_attn_window_vjp_f32(_p(qkv), _p(g_out), _p(g), _p(lse), _p(ds), B, H, W, nh, window_size, shift, _stream()),
+              "kd_attn_window_vjp_f32")
+    return g
+
+
+def attn_na2d_vjp(qkv, g_out, nh, kernel_size):
+    """Gradient of neighbourhood attention (natten na2d, :428; clamped window): qkv [B, H, W, 3*nh*64]."""
+    g, lse, ds = _attn_vjp_bufs(qkv, g_out, nh)
+    B, H, W, _ = qkv.shape
+    nat.check(nat.lib().kd_attn_na2d_vjp_f32(_p(qkv), _p(g_out), _p(g), _p(lse), _p(ds), B, H, W, nh, kernel_size, _stream()), "kd_attn_na2d_vjp_f32")
+    return g
+
+
+def precond_vjp(g, g_coef, sigma, sigma_data, h=None, h_coef=nat.PC_ONE, out=None):
+    """coef(g_coef) * g (+ coef(h_coef) * h) per sample, coef one of the Karras scalings nat.PC_ONE / PC_SKIP / PC_OUT / PC_IN of sigma [B]
+    (layers.py:70-74): the transposes of the preconditioning D = F(x c_in) c_out + x c_skip."""
+    out = torch.empty_like(g) if out is None else out
+    B = g.shape[0]
+    for name, t in (("h", h), ("out", out)):
+        if t is not None and _chk(t, name).shape != g.shape:
+            raise ValueError(f"precond_vjp: {name} shape {tuple(t.shape)} != g shape {tuple(g.shape)}")
+    if _chk(sigma, "sigma").numel() != B:
+        raise ValueError(f"precond_vjp: {sigma.numel()} sigmas for batch {B}")
+    nat.check(nat.lib().kd_precond_vjp_f32(_p(_chk(g, "g")), int(g_coef), _p(h), int(h_coef), _p(sigma), float(sigma_data), _p(out), B, g.numel() // B,
+                                           _stream()), "kd_precond_vjp_f32")
+    return out
+
 def ll_div(x, denoised, denoised_dot, v, sigma):
     """(d, d_ll): d = (x - D) / sigma (to_d, sampling.py:46) and d_ll[b] = sum_b v * (v - D_dot) / sigma_b.  sigma: [B] fp32."""
     B = x.shape[0]
