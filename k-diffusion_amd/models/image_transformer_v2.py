@@ -30,7 +30,7 @@ import weakref
 import os
 import math
 from dataclasses import dataclass
-from typing import Optional, Union
+from typing import NamedTuple, Optional, Union
 
 import torch
 from torch import nn
@@ -44,6 +44,7 @@ D_HEAD = 64
 SCHEDULE_TABLE_MAX_BYTES = 1 << 30
 SCHEDULES_KEPT = 4            # a run of a two-stage solver hints two tables; older records (and their tensors) are dropped
 SCHEDULE_CHAINS_KEPT = 2      # conditioning workspaces kept per plan, by schedule length (least recently used dropped)
+DERIVED_KEPT = 1024  # weight-derived tensors kept per model (_derive: transposed weights, RoPE tables, ...): all dropped beyond that
 MAX_PLANS = 16     # cached launch plans (one per batch / size / conditioning kinds / device / arithmetic mode / switches) per model: least recently used beyond that
 # environment switches of the kernel routing (name, default): read in _plan_for, part of the plan key, passed to route_layer
 PLAN_SWITCHES = (("KDIFF_ATTN_BLOCK", "1"), ("KDIFF_PROJ_BLOCK", "1"), ("KDIFF_FFN_OUT", "all"), ("KDIFF_RUN_LIST", "1"))
@@ -145,10 +146,98 @@ def _rms_scale(n):
     return _Holder(scale=nn.Parameter(torch.ones(n)))
 
 
-# ---------------------------------------------------------------------------------- kernel routing
+# ---------------------------------------------------------------------------------- the hourglass's structure (every pass walks it)
 
 _ATTN_KIND = {GlobalAttentionSpec: "global", NeighborhoodAttentionSpec: "neighborhood", ShiftedWindowAttentionSpec: "shifted-window"}
 _CORE = {"global": "attn_global", "neighborhood": "attn_na2d", "shifted-window": "attn_window"}
+
+
+def attn_geometry(spec, index):
+    """(kind, core, params) of the attention of layer ``index`` (``Step.index``) of a level with attention ``spec``: ``kind`` as
+    route_layer takes it, ``core`` the name of its kernels (ops.<core>, ops.<core>_jvp, ops.<core>_vjp; kd_<core>_f32 / _bf16) and
+    ``params`` their arguments behind the head count: () / (kernel_size,) / (window_size, shift)."""
+    kind = _ATTN_KIND[type(spec)]
+    if kind == "global":
+        params = ()
+    elif kind == "neighborhood":
+        params = (spec.kernel_size,)
+    else:
+        params = (spec.window_size, spec.window_size // 2 if index % 2 == 1 else 0)          # shift: :523
+    return kind, _CORE[kind], params
+
+
+class Step(NamedTuple):
+    """One step of ``hourglass``: kind "layer" (``module`` of level ``level``, state-dict prefix ``prefix``, ``index`` its position in
+    the level with the up levels' offset already applied), or "merge" / "split" between levels ``level`` and ``level + 1``."""
+    kind: str
+    level: int
+    prefix: str = ""
+    module: Optional[nn.Module] = None
+    index: int = 0
+
+
+def hourglass(model):
+    """The network's steps in forward order (image_transformer_v2.py:721-762): down levels, each followed by its merge, the mid level,
+    then each up level behind its split.  An up level's layers count on from its down level's (:697), which sets the window shift."""
+    steps, top = [], len(model.level_specs) - 1
+    for li in range(top):
+        steps += [Step("layer", li, f"down_levels.{li}.{i}.", mod, i) for i, mod in enumerate(model.down_levels[li])]
+        steps.append(Step("merge", li))
+    steps += [Step("layer", top, f"mid_level.{i}.", mod, i) for i, mod in enumerate(model.mid_level)]
+    for li in reversed(range(top)):
+        steps.append(Step("split", li))
+        depth = model.level_specs[li].depth
+        steps += [Step("layer", li, f"up_levels.{li}.{i}.", mod, i + depth) for i, mod in enumerate(model.up_levels[li])]
+    return steps
+
+
+def _level_pos(grids, li):
+    """[h, w, 2] axial positions (y, x) of level ``li``'s tokens: cell centres of the top grid, 2x2 means below (:726, :52-54)."""
+    h0, w0 = grids[0]
+    pos = axial_rope.make_axial_pos(h0, w0).view(h0, w0, 2)
+    for _ in range(li):
+        pos = axial_rope.downscale_pos(pos)
+    return pos
+
+
+# ---------------------------------------------------------------------------------- the unfused ops path (dual and backward passes)
+
+EPS = 1e-6
+
+
+def conditioning(model, sigma, aug_cond, class_cond, mapping_cond):
+    """The mapping network's output [B, mapping width] (image_transformer_v2.py:729-740, :552-581) on ``ops`` calls."""
+    m = model
+    B = sigma.shape[0]
+    dev = sigma.device
+    ff = ops.fourier_sigma(sigma, m.time_emb.weight.detach().contiguous())
+    temb = ops.linear(ff, m.time_in_proj.weight)
+    aug = torch.zeros(B, 9, device=dev, dtype=torch.float32) if aug_cond is None else aug_cond.to(device=dev, dtype=torch.float32).reshape(B, 9).contiguous()
+    aug_proj = ops.linear(ops.fourier_features(aug, m.aug_emb.weight.detach().contiguous()), m.aug_in_proj.weight)
+    emb = ids = None
+    if m.class_emb is not None:
+        ids = class_cond.to(device=dev, dtype=torch.int64).reshape(B).contiguous()
+        lo, hi = (int(ids.min()), int(ids.max()))
+        if lo < 0 or hi >= m.class_emb.weight.shape[0]:
+            raise IndexError(f"class_cond ids must lie in [0, {m.class_emb.weight.shape[0] - 1}] (got {lo}..{hi})")
+        emb = m.class_emb.weight
+    mterm = None
+    if m.mapping_cond_in_proj is not None:
+        mterm = ops.linear(mapping_cond.to(device=dev, dtype=torch.float32).reshape(B, -1).contiguous(), m.mapping_cond_in_proj.weight)
+    c = ops.cond_sum(temb, aug_proj, emb=emb, ids=ids, c=mterm)
+    c = ops.rms_norm(c, m.mapping.in_norm.scale)
+    for blk in m.mapping.blocks:
+        h = ops.norm_linear(c, blk.norm.scale, blk.up_proj.weight, rows_per_sample=B, epi=nat.EPI_GEGLU)
+        c = ops.linear(h, blk.down_proj.weight, residual=c)
+    return ops.rms_norm(c, m.mapping.out_norm.scale)
+
+
+def ada_scale(cond, norm):
+    """AdaRMSNorm scales (:155-166): Linear(cond) + 1 -> [B, d]."""
+    return ops.linear(cond, norm.linear.weight, out_add=1.0)
+
+
+# ---------------------------------------------------------------------------------- kernel routing
 
 
 @dataclass(frozen=True)
@@ -343,8 +432,9 @@ class _Plan:
         The callers (eviction, ``_drop_plans``: rare events) run the collector once behind this for the helper objects' own cycles."""
         self.__dict__.clear()
 
-    def __init__(self, model, B, H, W, has_aug, has_class, has_mapping_cond, device, mode, switches):
-        """``mode``: the arithmetic mode (nat.PREC_*); ``switches``: the values of PLAN_SWITCHES by name (both from the plan key)."""
+    def __init__(self, model, B, H, W, grids, has_aug, has_class, has_mapping_cond, device, mode, switches):
+        """``grids``: the levels' token grids (``_token_grids``); ``mode``: the arithmetic mode (nat.PREC_*); ``switches``: the values of
+        PLAN_SWITCHES by name (both from the plan key)."""
         self.lib = nat.lib()
         m = self.model = model
         self.mode, self.switches = mode, switches
@@ -358,16 +448,7 @@ class _Plan:
         f32 = dict(device=device, dtype=torch.float32)
         act = dict(device=device, dtype=torch.bfloat16 if bf else torch.float32)   # residual stream, qkv, attention out, FF hidden
         ph, pw = m.patch_size
-        if H % ph or W % pw:
-            raise ValueError(f"input {H}x{W} not divisible by the patch size {ph}x{pw}")
         levels = self.levels = m.level_specs
-        n_lv = len(levels)
-        grids = [(H // ph, W // pw)]
-        for _ in range(n_lv - 1):
-            gh, gw = grids[-1]
-            if gh % 2 or gw % 2:
-                raise ValueError(f"token grid {gh}x{gw} cannot be merged 2x2")
-            grids.append((gh // 2, gw // 2))
         self.B, self.grids = B, grids
         self.out_shape = (B, m.out_channels, H, W)
         self.class_checked = {}                             # identities of the range-checked class_cond tensors (_plan_for) -> the tensor
@@ -412,18 +493,16 @@ class _Plan:
         L = self.launches
         self.d_patch_in = self._gemm(L, "patch_in", None, m.patch_in.proj.weight, xs[0], toks[0], levels[0].width, m.in_channels * ph * pw,
                                      a_mode=nat.A_PATCH_NCHW, grid=grids[0], patch=(ph, pw, m.in_channels))
-        for li in range(n_lv - 1):
-            for i, mod in enumerate(m.down_levels[li]):
-                self._add_layer(li, f"down_levels.{li}.{i}.", mod, i)
-            self._gemm(L, f"merges.{li}", xs[li], m.merges[li].proj.weight, xs[li + 1], toks[li + 1], levels[li + 1].width,
-                       4 * levels[li].width, a_mode=nat.A_MERGE2x2, grid=grids[li + 1])
-        for i, mod in enumerate(m.mid_level):
-            self._add_layer(n_lv - 1, f"mid_level.{i}.", mod, i)
-        for li in reversed(range(n_lv - 1)):
-            self._gemm(L, f"splits.{li}", xs[li + 1], m.splits[li].proj.weight, xs[li], toks[li + 1], 4 * levels[li].width,
-                       levels[li + 1].width, epi=nat.EPI_SPLIT_LERP, residual=xs[li], fac=m.splits[li].fac, grid=grids[li + 1])
-            for i, mod in enumerate(m.up_levels[li]):
-                self._add_layer(li, f"up_levels.{li}.{i}.", mod, i + levels[li].depth)                      # :697
+        for st in hourglass(m):
+            li = st.level
+            if st.kind == "layer":
+                self._add_layer(li, st.prefix, st.module, st.index)
+            elif st.kind == "merge":
+                self._gemm(L, f"merges.{li}", xs[li], m.merges[li].proj.weight, xs[li + 1], toks[li + 1], levels[li + 1].width,
+                           4 * levels[li].width, a_mode=nat.A_MERGE2x2, grid=grids[li + 1])
+            else:
+                self._gemm(L, f"splits.{li}", xs[li + 1], m.splits[li].proj.weight, xs[li], toks[li + 1], 4 * levels[li].width,
+                           levels[li + 1].width, epi=nat.EPI_SPLIT_LERP, residual=xs[li], fac=m.splits[li].fac, grid=grids[li + 1])
         self.d_patch_out = self._gemm(L, "patch_out", xs[0], m.patch_out.proj.weight, None, toks[0], m.out_channels * ph * pw,
                                       levels[0].width, epi=nat.EPI_UNPATCH_NCHW, norm_scale=m.out_norm.scale, scale_stride=0,
                                       rows_per_sample=grids[0][0] * grids[0][1], grid=grids[0], patch=(ph, pw, m.out_channels))
@@ -504,15 +583,15 @@ class _Plan:
         if self.precision == nat.PREC_BF16:
             # bf16 mode: the qkv epilogue evaluates the RoPE angles itself (hardware sin / cos) from the token's axial
             # position and the head's frequencies in revolutions -- two tiny tables instead of cos / sin per (token, head)
-            cos_t, sin_t = m._rope_pos_freq(li, self.grids, sa, self.device)
+            cos_t, sin_t = m._rope(li, self.grids, sa, self.device, revs=True)
         else:
-            cos_t, sin_t = m._rope_tables(li, self.grids, sa, self.device)
+            cos_t, sin_t = m._rope(li, self.grids, sa, self.device)
         self.keep += [cos_t, sin_t]
         qk = (sa.scale, cos_t, sin_t, nh)
         if self.precision == nat.PREC_SPLIT3:
             # the split3 projections of round 3 evaluate the angles like the bf16 ones (no table loads beside their LDS-DMA ring);
             # the tables stay for the round-1 kernels they fall back to (ragged shapes) and for the exact mode
-            pos_t, freq_t = m._rope_pos_freq(li, self.grids, sa, self.device)
+            pos_t, freq_t = m._rope(li, self.grids, sa, self.device, revs=True)
             self.keep += [pos_t, freq_t]
             qk += (pos_t, freq_t)
         return qk
@@ -522,7 +601,8 @@ class _Plan:
         d, d_ff, x, rps = lv.width, lv.d_ff, self.xs[li], gh * gw
         spec = lv.self_attn
         nh = d // spec.d_head if hasattr(mod, "self_attn") else 0
-        r = route_layer(self.lib, self.mode, self.B, T, rps, d, d_ff, nh, _ATTN_KIND[type(spec)] if nh else None, self.switches)
+        kind, core, params = attn_geometry(spec, index) if nh else (None, None, ())
+        r = route_layer(self.lib, self.mode, self.B, T, rps, d, d_ff, nh, kind, self.switches)
         split3 = self.precision == nat.PREC_SPLIT3
         if nh:
             sa, norm = mod.self_attn, prefix + "self_attn.norm"
@@ -541,14 +621,9 @@ class _Plan:
             else:
                 self._gemm(L, prefix + "qkv_proj", x, sa.qkv_proj.weight, self.qkv, T, 3 * d, d, table=norm, mx8=r.qkv == "mx8", **q)
             if r.core is not None:
-                if isinstance(spec, GlobalAttentionSpec):
-                    geo = (gh * gw, nh)
-                elif isinstance(spec, NeighborhoodAttentionSpec):
-                    geo = (gh, gw, nh, spec.kernel_size)
-                else:
-                    geo = (gh, gw, nh, spec.window_size, spec.window_size // 2 if index % 2 == 1 else 0)          # shift: :523
+                geo = ((rps, nh) if kind == "global" else (gh, gw, nh)) + params
                 prep = () if r.core.endswith("_bf16") else (2 if split3 else 0, None, None, None, C.c_float(1e-6), self.precision)
-                L.append(_Launch(r.core, (_ptr(self.qkv), _ptr(self.att), self.B, *geo, *prep), prefix + _CORE[_ATTN_KIND[type(spec)]]))
+                L.append(_Launch(r.core, (_ptr(self.qkv), _ptr(self.att), self.B, *geo, *prep), prefix + core))
             if not r.fuse_out:
                 self._gemm(L, prefix + "out_proj", self.att, sa.out_proj.weight, x, T, d, d, epi=nat.EPI_RESIDUAL, residual=x)
         norm, w_up, w_down = prefix + "ff.norm", mod.ff.up_proj.weight, mod.ff.down_proj.weight
@@ -708,7 +783,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
                                      for a, b in zip(levels[:-1], levels[1:])])
         self.out_norm = _rms_scale(levels[0].width)
         self.patch_out = _Holder(proj=_linear_weight(out_channels * ph * pw, levels[0].width, zero=True))
-        self._plans, self._fingerprint, self._packed, self._plans_epoch = {}, None, {}, None
+        self._plans, self._fingerprint, self._packed, self._derived, self._plans_epoch = {}, None, {}, {}, None
         self._fp_dicts, self._fp_names, self._fp_objs, self._fp_tensors, self._fp_tracked, self._fp_epoch = (), (), (), (), (), 0
         self._fp_hooked = weakref.WeakSet()
         self._fp_sized, self._fp_sizes = (), ()
@@ -729,22 +804,33 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         visit("mid_level.", self.mid_level)
         return out
 
-    def _rope_tables(self, li, grids, sa, device):
-        h0, w0 = grids[0]
-        pos = axial_rope.make_axial_pos(h0, w0).view(h0, w0, 2)
-        for _ in range(li):
-            pos = axial_rope.downscale_pos(pos)
-        cos_t, sin_t = axial_rope.rope_tables(pos, sa.pos_emb.freqs)
-        return cos_t.to(device), sin_t.to(device)
+    def _derive(self, tag, sources, build):
+        """``build()``: tensors derived from the weights ``sources`` alone, kept per model under ``tag`` and the sources' identities and
+        version counters, so an in-place edit of a source builds them again (tensors made under torch.inference_mode() carry no counter:
+        ``invalidate()``).  The entry keeps its sources alive, so their ids cannot be recycled under it.  The store goes with ``_packed``
+        whenever the weights change, and at ``invalidate()``.  (A lookup does not read ``_weights_fingerprint``: 25 - 30 us per call.)"""
+        key = (tag, *[(id(t), None if t.is_inference() else t._version) for t in sources])
+        ent = self._derived.get(key)
+        if ent is None:
+            if len(self._derived) >= DERIVED_KEPT:
+                self._derived.clear()
+            ent = self._derived[key] = (sources, build())
+        return ent[1]
 
-    def _rope_pos_freq(self, li, grids, sa, device):
-        """bf16 mode: ([tokens, 2] axial positions (y, x) of the level's grid, [nh, 8] frequencies in revolutions)."""
-        h0, w0 = grids[0]
-        pos = axial_rope.make_axial_pos(h0, w0).view(h0, w0, 2)
-        for _ in range(li):
-            pos = axial_rope.downscale_pos(pos)
-        freq = sa.pos_emb.freqs.detach().to(torch.float32).cpu() / (2.0 * math.pi)
-        return pos.reshape(-1, 2).to(torch.float32).contiguous().to(device), freq.contiguous().to(device)
+    def _rope(self, li, grids, sa, device, revs=False):
+        """AxialRoPE operands of attention ``sa`` at level ``li`` of ``grids``, evaluated on the CPU in fp32 (axial_rope): (cos, sin)
+        tables [tokens, nh, 16], or with ``revs`` ([tokens, 2] positions (y, x), [nh, 8] frequencies in revolutions) for the kernels that
+        evaluate the angles themselves."""
+        freqs = sa.pos_emb.freqs
+
+        def build():
+            pos = _level_pos(grids, li)
+            if revs:
+                freq = freqs.detach().to(torch.float32).cpu() / (2.0 * math.pi)
+                return pos.reshape(-1, 2).to(torch.float32).contiguous().to(device), freq.contiguous().to(device)
+            cos_t, sin_t = axial_rope.rope_tables(pos, freqs.detach())
+            return cos_t.to(device), sin_t.to(device)
+        return self._derive(("rope", li, grids[0], device, revs), (freqs,), build)
 
     def _drop_plans(self):
         """All cached plans go, workspaces at once (``_Plan.release``).  The device is idle first: a plan's side-stream work may still be
@@ -762,8 +848,10 @@ class ImageTransformerDenoiserModelV2(nn.Module):
     def invalidate(self):
         """Drop the plans and packed weight images at the next call.  Needed only after an IN-PLACE edit of weights that were created
         under torch.inference_mode() outside load_state_dict / .to(): such tensors carry no version counter, so the edit leaves no trace
-        (_weights_fingerprint sees everything else by itself)."""
+        (_weights_fingerprint sees everything else by itself).  The tensors the dual and backward passes derive from the weights
+        (``_derive``) go at once."""
         self._fp_epoch += 1
+        self._derived = {}
 
     def _apply(self, fn, *args, **kwargs):
         # .to() / .cuda() / .half(): the same Parameter objects with new .data (seen through their addresses) or, with
@@ -845,20 +933,49 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         from . import jvp
         return jvp.forward_jvp(self, x, sigma, x_dot, aug_cond=aug_cond, class_cond=class_cond, mapping_cond=mapping_cond, sigma_data=sigma_data)
 
-    @torch.no_grad()
-    def _run(self, x, sigma, aug_cond, class_cond, mapping_cond, sigma_data):
+    def _check_input(self, x, class_cond, mapping_cond, subject, other=None):
+        """The input contract of every pass -> (x, other tensor or None), contiguous: the conditioning this model needs is given, x is
+        [B, in_channels, H, W] fp32 on a ROCm device.  ``subject`` names the pass in the no-CPU-fallback error.  ``other``: (tensor,
+        channels, message) of the pass's second tensor (tangent, output gradient), checked to be [B, channels, H, W] fp32 on a ROCm
+        device as well; ``message`` formats (its shape, the expected shape)."""
         if class_cond is None and self.class_emb is not None:
             raise ValueError("class_cond must be specified if num_classes > 0")
         if mapping_cond is None and self.mapping_cond_in_proj is not None:
             raise ValueError("mapping_cond must be specified if mapping_cond_dim > 0")
         if x.dim() != 4 or x.shape[1] != self.in_channels:
             raise ValueError(f"expected input [B, {self.in_channels}, H, W], got {tuple(x.shape)}")
-        if not x.is_cuda:
-            raise RuntimeError("ImageTransformerDenoiserModelV2 runs on the HIP path only: move the model and inputs "
-                               "to a ROCm device (there is no CPU fallback)")
-        if x.dtype != torch.float32:
-            raise TypeError(f"fp32 inputs only (got {x.dtype})")
-        x = x.contiguous()
+        ts = (x,)
+        if other is not None:
+            t, channels, message = other
+            shape = (x.shape[0], channels, *x.shape[2:])
+            if tuple(t.shape) != shape:
+                raise ValueError(message.format(tuple(t.shape), shape))
+            ts = (x, t)
+        if not all(t.is_cuda for t in ts):
+            raise RuntimeError(f"{subject} runs on the HIP path only: move the model and inputs to a ROCm device (there is no CPU fallback)")
+        if any(t.dtype != torch.float32 for t in ts):
+            raise TypeError(f"fp32 inputs only (got {', '.join(str(t.dtype) for t in ts)})")
+        return x.contiguous(), None if other is None else ts[1].contiguous()
+
+    def _token_grids(self, x):
+        """Token grid (h, w) of every level for the input ``x``, which must be on the weights' device."""
+        if self.patch_in.proj.weight.device != x.device:
+            raise RuntimeError(f"model weights are on {self.patch_in.proj.weight.device}, input on {x.device}")
+        H, W = x.shape[2:]
+        ph, pw = self.patch_size
+        if H % ph or W % pw:
+            raise ValueError(f"input {H}x{W} not divisible by the patch size {ph}x{pw}")
+        grids = [(H // ph, W // pw)]
+        for _ in self.level_specs[1:]:
+            gh, gw = grids[-1]
+            if gh % 2 or gw % 2:
+                raise ValueError(f"token grid {gh}x{gw} cannot be merged 2x2")
+            grids.append((gh // 2, gw // 2))
+        return grids
+
+    @torch.no_grad()
+    def _run(self, x, sigma, aug_cond, class_cond, mapping_cond, sigma_data):
+        x, _ = self._check_input(x, class_cond, mapping_cond, "ImageTransformerDenoiserModelV2")
         B, _, H, W = x.shape
         plan = self._plan_for(x, aug_cond, class_cond, create=True)
         cur = torch.cuda.current_stream()
@@ -908,7 +1025,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
             if not create:
                 return None
             self._drop_plans()
-            self._fingerprint, self._packed = fp, {}
+            self._fingerprint, self._packed, self._derived = fp, {}, {}
         has_class = self.class_emb is not None
         # Kernel selection is fixed when a plan is built (route_layer): by the arithmetic mode, by the environment switches read here and by
         # library options (kd_ffn_f32_supported follows "ffn_x3").  The switches are part of the key; a change of any library option
@@ -926,8 +1043,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         if plan is not None and len(self._plans) > 1:
             self._plans[key] = self._plans.pop(key)                # most recently used last (dicts keep insertion order)
         if plan is None and create:
-            if self.patch_in.proj.weight.device != x.device:
-                raise RuntimeError(f"model weights are on {self.patch_in.proj.weight.device}, input on {x.device}")
+            grids = self._token_grids(x)
             if len(self._plans) >= MAX_PLANS:
                 # a plan owns the workspaces of its shape (~20 MB per 256 x 256 image in the fp32 modes): a caller that walks through
                 # batch sizes would otherwise keep them all.  The least recently used one goes; its side-stream work (conditioning
@@ -937,7 +1053,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
                 self._plans.pop(next(iter(self._plans))).release()
                 gc.collect()
             with torch.inference_mode(False):     # (workspaces made under inference_mode could not be written in place outside it later)
-                plan = self._plans[key] = _Plan(self, B, H, W, key[3], has_class, key[5], x.device, key[7],
+                plan = self._plans[key] = _Plan(self, B, H, W, grids, key[3], has_class, key[5], x.device, key[7],
                                                 dict(zip((name for name, _ in PLAN_SWITCHES), key[8:])))
         if plan is not None and has_class and class_cond is not None:
             # nn.Embedding raises on an out-of-range id (on every call); the HIP kernel would read past the table.  Checked whenever

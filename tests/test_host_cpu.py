@@ -1125,3 +1125,36 @@ def test_layer_routing_of_the_headline_config(KD):
             got.append(_route_code(itv2.route_layer(lib, modes[mode], int(B), int(B) * rps, rps, lv.width, lv.d_ff,
                                                     lv.width // lv.self_attn.d_head, kind, switches)))
         assert " | ".join(got) == want, key
+
+
+def test_hourglass_walk_visits_every_layer_once(KD):
+    """The one walk order of the plan, the dual pass and the backward pass: every down / mid / up layer once, under its state-dict
+    prefix, with merges and splits moving one level at a time, and up-level layers counting on from their down level's depth
+    (the reference's :697, which sets the shifted window's shift)."""
+    import json
+    from importlib import import_module
+    from tests.golden import cases
+    itv2 = import_module(KD.__name__ + ".models.image_transformer_v2")
+    raws = [cases.raw_config("tiny_sw"), cases.raw_config("tiny_na"),
+            json.load(open(os.path.join(REPO, "configs", "config_oxford_flowers_shifted_window.json")))]
+    for raw in raws:
+        model = KD.config.make_model(KD.config.load_config(raw))
+        layers = [mod for lvl in (*model.down_levels, model.mid_level, *model.up_levels) for mod in lvl]
+        steps = itv2.hourglass(model)
+        walked = [st.module for st in steps if st.kind == "layer"]
+        assert len(walked) == len(layers) and {id(m) for m in walked} == {id(m) for m in layers}
+        level, top = 0, len(model.level_specs) - 1
+        for st in steps:
+            if st.kind == "merge":
+                assert st.level == level < top
+                level += 1
+            elif st.kind == "split":
+                assert st.level == level - 1
+                level -= 1
+            else:
+                assert st.level == level and model.get_submodule(st.prefix[:-1]) is st.module
+                group, *li, i = st.prefix[:-1].split(".")
+                assert st.index == int(i) + (model.level_specs[level].depth if group == "up_levels" else 0)
+        assert level == 0
+    sw = model.level_specs[0].self_attn                                  # window 8 over the two layers of each side of level 0
+    assert [itv2.attn_geometry(sw, st.index)[2] for st in steps if st.kind == "layer" and st.level == 0] == [(8, 0), (8, 4), (8, 0), (8, 4)]

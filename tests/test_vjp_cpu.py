@@ -66,3 +66,18 @@ def test_transposed_weights_are_cached_per_model(KD):
     with torch.no_grad():
         sp.fac.fill_(0.25)
     assert torch.allclose(vjp._wt(model, sp.proj.weight, fac=sp.fac), (sp.proj.weight * 0.25).t())
+
+
+def test_invalidate_drops_the_derived_tensors(KD):
+    """A weight made under torch.inference_mode() has no version counter, so an in-place edit of it leaves no trace: invalidate() is the
+    way to say so, and it drops what the backward and dual passes derived from the weights, as it drops the plans."""
+    cfg, model = _model(KD)
+    vjp = importlib.import_module(KD.__name__ + ".models.vjp")
+    with torch.inference_mode():
+        w = torch.randn(8, 4)
+    t = vjp._wt(model, w)
+    assert torch.equal(t, w.t()) and vjp._wt(model, w) is t
+    with torch.inference_mode():
+        w.mul_(2.0)
+    model.invalidate()
+    assert torch.equal(vjp._wt(model, w), w.t())
