@@ -448,6 +448,41 @@ int kd_attn_na2d_vjp_f32(const float* qkv, const float* g_out, float* g_qkv, flo
 int kd_precond_vjp_f32(const float* g, int g_coef, const float* h, int h_coef, const float* sigma, float sigma_data, float* y, int batch,
                        long long per_sample, void* stream);
 
+/* Parameter gradients of the HDiT denoiser and its training loss (csrc/wgrad_f32.hip; models/vjp.py, layers.Denoiser.loss).  fp32 arithmetic,
+ * fixed reduction orders through caller-provided workspaces, no atomics: bit-identical on repeat.
+ *   kd_wgrad_f32       : dW[N, K] (+)= alpha * sum_m G[m, n] * A[m, k] over M rows (alpha: a device scalar or NULL; accumulate: add to dW).
+ *                        g_mode / a_mode (KD_WG_*, one operand at most gathered) read the rows through the token merge (fine NHWC grid of
+ *                        2gh x 2gw x chan, ph = pw = 2) or the NCHW patch gather (image chan x gh*ph x gw*pw); gathered columns are ordered
+ *                        (py, px, channel).  A's prologue: a_geglu (A holds [value | gate] rows of 2K, the operand is value * gelu(gate)),
+ *                        row_scale[m], col_scale[(m / rows_per_sample) * col_stride + k].  The rows are cut into nchunk chunks of chunk_rows
+ *                        (chunk_rows * nchunk >= M); ws holds nchunk * N * K floats.  split3: bf16 hi / lo operands, 3 MFMAs per product, fp32
+ *                        accumulate (the backward pass's rule under split3 / bf16 / fp8); 0: fp32 FMAs (exact).
+ *   kd_row_rrms_f32    : rrms[r] = rsqrt(mean(x[r, :]^2) + eps).
+ *   kd_colsum_f32      : out[s, j] (+)= sum over rows r of segment s (rows_per_seg rows each) of a[r, j] * (b[r, j] - b2[r, j]) * row_scale[r];
+ *                        b, b2, row_scale may be NULL.  ws holds rows / 64 (rounded up per segment) * cols floats.
+ *   kd_attn_scale_grad_f32 : out[h] (+)= sum of colsum's q and k columns of head h ([3, nh, 64] layout) / (2 scale[h]).
+ *   kd_class_emb_grad_f32  : out[c, :] (+)= sum over b ascending with ids[b] == c of g[b, :].
+ *   kd_loss_prep_f32   : noised = input + noise * sigma[b], x_in = noised * c_in (layers.py:78-81).
+ *   kd_loss_f32        : losses[b] = mean((f - target)^2) * c_weight, target = (input - c_skip noised) / c_out (layers.py:82-84); weighting
+ *                        one of KD_LW_* (KD_LW_GIVEN: c_weight[b] from the caller).
+ *   kd_loss_vjp_f32    : g_f = g_loss[b] * c_weight * 2 (f - target) / per_sample. */
+enum { KD_WG_PLAIN = 0, KD_WG_MERGE2x2 = 1, KD_WG_PATCH_NCHW = 2 };
+enum { KD_LW_KARRAS = 0, KD_LW_SOFT_MIN_SNR = 1, KD_LW_SNR = 2, KD_LW_GIVEN = 3 };
+int kd_wgrad_f32(const float* G, int g_mode, const float* A, int a_mode, int a_geglu, long long M, int N, int K, int gh, int gw, int ph, int pw,
+                 int chan, const float* row_scale, const float* col_scale, int col_stride, int rows_per_sample, const float* alpha, int accumulate,
+                 int split3, int chunk_rows, int nchunk, float* ws, float* dW, void* stream);
+int kd_row_rrms_f32(const float* x, float* rrms, long long rows, int d, float eps, void* stream);
+int kd_colsum_f32(const float* a, const float* b, const float* b2, const float* row_scale, long long rows, int cols, long long rows_per_seg,
+                  int accumulate, float* ws, float* out, void* stream);
+int kd_attn_scale_grad_f32(const float* colsum, const float* scale, int nh, int accumulate, float* out, void* stream);
+int kd_class_emb_grad_f32(const float* g, const long long* ids, int batch, int d, int n_cls, int accumulate, float* out, void* stream);
+int kd_loss_prep_f32(const float* input, const float* noise, const float* sigma, float sigma_data, float* noised, float* x_in, int batch,
+                     long long per_sample, void* stream);
+int kd_loss_f32(const float* f, const float* input, const float* noised, const float* sigma, float sigma_data, int weighting, const float* c_weight,
+                float* losses, int batch, long long per_sample, void* stream);
+int kd_loss_vjp_f32(const float* f, const float* input, const float* noised, const float* sigma, float sigma_data, int weighting,
+                    const float* c_weight, const float* g_loss, float* g_f, int batch, long long per_sample, void* stream);
+
 /* Final image conversion (k_diffusion/utils.py:27-34 to_pil_image): u8 = trunc((clamp(x,-1,1)+1)/2*255)
  * (torchvision's to_pil_image does mul(255).byte(), i.e. truncation) */
 int kd_to_uint8(const float* x, unsigned char* y, long long n, void* stream);

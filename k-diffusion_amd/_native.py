@@ -14,6 +14,8 @@ A_PLAIN, A_MERGE2x2, A_PATCH_NCHW = 0, 1, 2
 EPI_STORE, EPI_RESIDUAL, EPI_GEGLU, EPI_SPLIT_LERP, EPI_UNPATCH_NCHW, EPI_QKV = 0, 1, 2, 3, 4, 5
 PREC_EXACT, PREC_SPLIT3, PREC_BF16 = 0, 1, 2
 PC_ONE, PC_SKIP, PC_OUT, PC_IN = 0, 1, 2, 3          # kd_precond_vjp_f32's Karras scalings (KD_PC_*)
+WG_PLAIN, WG_MERGE2x2, WG_PATCH_NCHW = 0, 1, 2      # kd_wgrad_f32's operand gathers (KD_WG_*)
+LW_KARRAS, LW_SOFT_MIN_SNR, LW_SNR, LW_GIVEN = 0, 1, 2, 3   # kd_loss_f32's weightings (KD_LW_*)
 # PREC_FP8 is a mode of the NETWORK, not a KdGemm.precision value: the bf16 mode with the AdaRMSNorm -> wide projections of the K = 256 / 512
 # levels on the block-scaled fp8 matrix instruction (kd_gemm_mx8); every descriptor of such a plan says KD_PREC_BF16
 PREC_FP8 = 3
@@ -150,6 +152,14 @@ SIGNATURES = {
     "kd_attn_window_vjp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "kd_attn_na2d_vjp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "kd_precond_vjp_f32": [_vp, _i, _vp, _i, _vp, _f, _vp, _i, _ll, _vp],
+    "kd_wgrad_f32": [_vp, _i, _vp, _i, _i, _ll, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "kd_row_rrms_f32": [_vp, _vp, _ll, _i, _f, _vp],
+    "kd_colsum_f32": [_vp, _vp, _vp, _vp, _ll, _i, _ll, _i, _vp, _vp, _vp],
+    "kd_attn_scale_grad_f32": [_vp, _vp, _i, _i, _vp, _vp],
+    "kd_class_emb_grad_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "kd_loss_prep_f32": [_vp, _vp, _vp, _f, _vp, _vp, _i, _ll, _vp],
+    "kd_loss_f32": [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _i, _ll, _vp],
+    "kd_loss_vjp_f32": [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _i, _ll, _vp],
     "kd_prof_enable": [_i],
     "kd_prof_count": [],
     "kd_prof_get": [_i, C.c_char_p, _i, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double)],

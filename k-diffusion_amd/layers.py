@@ -4,7 +4,9 @@
 (``inner_model``, ``sigma_data``, ``weighting``, ``scales``) and ``forward(input, sigma, **kwargs)``.
 With the native HDiT inner model the three preconditioning passes (x * c_in, F * c_out, + x * c_skip)
 disappear into the patch-in / patch-out GEMMs; with a foreign inner model they run as two HIP
-elementwise kernels around it.  The training-time ``loss`` methods are out of scope.
+elementwise kernels around it.  ``Denoiser.loss`` is the reference's training objective (layers.py:76-86) on HIP kernels: with the
+native inner model its backward fills the parameters' ``.grad`` through the model's reverse walk (models/vjp.py); a foreign inner model
+keeps its own autograd graph.  The variance and simple losses and the DCT ``scales`` weighting are out of scope.
 """
 import torch
 from torch import nn
@@ -45,6 +47,27 @@ class _PrecondOut(torch.autograd.Function):
         return gf, gx, None, None
 
 
+class _Loss(torch.autograd.Function):
+    """Per-sample losses mean((f - target)^2) * c_weight from the model output f (csrc/wgrad_f32.hip: kd_loss_f32 / kd_loss_vjp_f32);
+    f is the only differentiable input."""
+
+    @staticmethod
+    def forward(ctx, f, input, noised, sigma, sigma_data, weighting, c_weight):
+        f = f.contiguous()
+        ctx.save_for_backward(f, input, noised, sigma, c_weight)
+        ctx.sigma_data, ctx.weighting = sigma_data, weighting
+        return ops.loss(f, input, noised, sigma, sigma_data, weighting, c_weight)
+
+    @staticmethod
+    def backward(ctx, grad):
+        f, input, noised, sigma, c_weight = ctx.saved_tensors
+        g = ops.loss_vjp(f, input, noised, sigma, ctx.sigma_data, ctx.weighting, grad.to(torch.float32).contiguous(), c_weight)
+        return g, None, None, None, None, None, None
+
+
+_WEIGHTINGS = {'karras': ops.nat.LW_KARRAS, 'soft-min-snr': ops.nat.LW_SOFT_MIN_SNR, 'snr': ops.nat.LW_SNR}
+
+
 class Denoiser(nn.Module):
     """D(x, sigma) = F(x * c_in, sigma) * c_out + x * c_skip."""
 
@@ -62,8 +85,30 @@ class Denoiser(nn.Module):
         var = sigma ** 2 + self.sigma_data ** 2
         return self.sigma_data ** 2 / var, sigma * self.sigma_data / var ** 0.5, 1 / var ** 0.5
 
-    def loss(self, *args, **kwargs):
-        raise NotImplementedError('training losses are outside this package\'s scope (sampling hot path only)')
+    def loss(self, input, noise, sigma, **kwargs):
+        """Per-sample training losses [B] (layers.py:76-86): mean((F(noised c_in, sigma) - target)^2) * c_weight with noised = input + noise
+        sigma and target = (input - c_skip noised) / c_out.  Backward over any scalar of them fills ``.grad`` of the inner model's
+        parameters that require grad.  input, noise, sigma and the conditioning get no gradient."""
+        if self.scales != 1:
+            raise NotImplementedError(f'Denoiser.loss: the DCT frequency weighting (scales={self.scales}) is not implemented; use scales=1')
+        for name, t in (('input', input), ('noise', noise), ('sigma', sigma), *kwargs.items()):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise NotImplementedError(f'Denoiser.loss: gradients w.r.t. {name} are not implemented (the loss differentiates w.r.t. the '
+                                          f'model parameters only); pass {name}.detach()')
+        x, noise = input.contiguous(), noise.contiguous()
+        B = x.shape[0]
+        sigma = sigma.to(device=x.device, dtype=torch.float32).reshape(-1).expand(B).contiguous()
+        if callable(self.weighting):
+            code, c_weight = ops.nat.LW_GIVEN, self.weighting(sigma).detach().to(device=x.device, dtype=torch.float32).reshape(B).contiguous()
+        else:
+            code, c_weight = _WEIGHTINGS[self.weighting], None
+        noised, x_in = ops.loss_prep(x, noise, sigma, self.sigma_data)
+        inner = self.inner_model
+        native = getattr(inner, 'loss_forward', None)
+        f = native(x_in, sigma, **kwargs) if native is not None else inner(x_in, sigma, **kwargs)
+        if torch.is_grad_enabled() and f.requires_grad:
+            return _Loss.apply(f, x, noised, sigma, self.sigma_data, code, c_weight)
+        return ops.loss(f.contiguous(), x, noised, sigma, self.sigma_data, code, c_weight)
 
     def prefetch_schedule(self, x_like, sigma_table, **kwargs):
         """Solver-loop hint (see ImageTransformerDenoiserModelV2.prefetch_schedule); a no-op for foreign inner models."""
@@ -120,9 +165,15 @@ class DenoiserWithVariance(Denoiser):
     overrides ``loss`` only (the model's log-variance output is a training quantity): ``forward`` / ``get_scalings`` -- the sampling path --
     are ``Denoiser``'s, as here."""
 
+    def loss(self, *args, **kwargs):
+        raise NotImplementedError('DenoiserWithVariance.loss (the log-variance objective) is not implemented')
+
 
 class SimpleLossDenoiser(Denoiser):
     """``loss_config == 'simple'`` (config.py:229-230; layers.py:104-111): again only ``loss`` differs in the reference."""
+
+    def loss(self, *args, **kwargs):
+        raise NotImplementedError('SimpleLossDenoiser.loss (the simple objective) is not implemented')
 
 
 class FourierFeatures(nn.Module):

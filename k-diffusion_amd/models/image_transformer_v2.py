@@ -205,15 +205,18 @@ def _level_pos(grids, li):
 EPS = 1e-6
 
 
-def conditioning(model, sigma, aug_cond, class_cond, mapping_cond):
-    """The mapping network's output [B, mapping width] (image_transformer_v2.py:729-740, :552-581) on ``ops`` calls."""
+def conditioning(model, sigma, aug_cond, class_cond, mapping_cond, keep=None):
+    """The mapping network's output [B, mapping width] (image_transformer_v2.py:729-740, :552-581) on ``ops`` calls.  ``keep``: a dict
+    that receives what the reverse of the chain needs (models/vjp.py): the Fourier features, the class ids, the mapping_cond rows, the
+    norms' inputs."""
     m = model
     B = sigma.shape[0]
     dev = sigma.device
     ff = ops.fourier_sigma(sigma, m.time_emb.weight.detach().contiguous())
     temb = ops.linear(ff, m.time_in_proj.weight)
     aug = torch.zeros(B, 9, device=dev, dtype=torch.float32) if aug_cond is None else aug_cond.to(device=dev, dtype=torch.float32).reshape(B, 9).contiguous()
-    aug_proj = ops.linear(ops.fourier_features(aug, m.aug_emb.weight.detach().contiguous()), m.aug_in_proj.weight)
+    aug_ff = ops.fourier_features(aug, m.aug_emb.weight.detach().contiguous())
+    aug_proj = ops.linear(aug_ff, m.aug_in_proj.weight)
     emb = ids = None
     if m.class_emb is not None:
         ids = class_cond.to(device=dev, dtype=torch.int64).reshape(B).contiguous()
@@ -223,12 +226,20 @@ def conditioning(model, sigma, aug_cond, class_cond, mapping_cond):
         emb = m.class_emb.weight
     mterm = None
     if m.mapping_cond_in_proj is not None:
-        mterm = ops.linear(mapping_cond.to(device=dev, dtype=torch.float32).reshape(B, -1).contiguous(), m.mapping_cond_in_proj.weight)
+        mrows = mapping_cond.to(device=dev, dtype=torch.float32).reshape(B, -1).contiguous()
+        mterm = ops.linear(mrows, m.mapping_cond_in_proj.weight)
     c = ops.cond_sum(temb, aug_proj, emb=emb, ids=ids, c=mterm)
+    if keep is not None:
+        keep.update(time_ff=ff, aug_ff=aug_ff, ids=ids, mapping_rows=mrows if mterm is not None else None, blocks=[])
+    c_sum = c
     c = ops.rms_norm(c, m.mapping.in_norm.scale)
     for blk in m.mapping.blocks:
+        if keep is not None:
+            keep["blocks"].append(c)
         h = ops.norm_linear(c, blk.norm.scale, blk.up_proj.weight, rows_per_sample=B, epi=nat.EPI_GEGLU)
         c = ops.linear(h, blk.down_proj.weight, residual=c)
+    if keep is not None:
+        keep.update(c_sum=c_sum, c_last=c)
     return ops.rms_norm(c, m.mapping.out_norm.scale)
 
 
@@ -738,6 +749,30 @@ class _InputGrad(torch.autograd.Function):
         return gx, None, None, None, None, None, None
 
 
+class _ParamGrad(torch.autograd.Function):
+    """The inner model as an autograd node whose differentiable inputs are its parameters (``Denoiser.loss`` only).  Forward: the fp32
+    ``ops``-path primal (``vjp.primal``); saved: the inputs, no activations.  Backward: ``vjp.backward`` with the parameters autograd asks
+    for; the rest cost nothing."""
+
+    @staticmethod
+    def forward(ctx, x, model, sigma, aug_cond, class_cond, mapping_cond, *params):
+        from . import vjp
+        out = vjp.primal(model, x, sigma, aug_cond, class_cond, mapping_cond)
+        ctx.model, ctx.params = model, params
+        ctx.save_for_backward(x, sigma, aug_cond, class_cond, mapping_cond)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        from . import vjp
+        x, sigma, aug_cond, class_cond, mapping_cond = ctx.saved_tensors
+        need = ctx.needs_input_grad[6:]
+        want = [p for p, n in zip(ctx.params, need) if n]
+        _, grads = vjp.backward(ctx.model, x, sigma, grad.to(torch.float32).contiguous(), aug_cond=aug_cond, class_cond=class_cond,
+                                mapping_cond=mapping_cond, params=want)
+        return (None,) * 6 + tuple(grads.get(id(p)) if n else None for p, n in zip(ctx.params, need))
+
+
 class ImageTransformerDenoiserModelV2(nn.Module):
     def __init__(self, levels, mapping, in_channels, out_channels, patch_size, num_classes=0, mapping_cond_dim=0):
         super().__init__()
@@ -906,8 +941,46 @@ class ImageTransformerDenoiserModelV2(nn.Module):
             self._fp_tensors, self._fp_tracked = tuple(uniq), tuple(not t.is_inference() for t in uniq)
         return (self._fp_epoch, *[(t.data_ptr(), t._version if tr else 0) for t, tr in zip(self._fp_tensors, self._fp_tracked)])
 
+    def _param_tags(self, name):
+        """The reference's parameter tags (image_transformer_v2.py:59-84): "wd" on the weights of the projections, "mapping" on the mapping
+        network and the AdaRMSNorm projections (:159-160, :680)."""
+        tags = set()
+        if name.endswith(".weight") and not name.startswith(("time_in_proj.", "aug_in_proj.", "class_emb.", "mapping_cond_in_proj.")):
+            tags.add("wd")
+        if name.startswith("mapping.") or name.endswith(".norm.linear.weight"):
+            tags.add("mapping")
+        return tags
+
     def param_groups(self, base_lr=5e-4, mapping_lr_scale=1 / 3):
-        raise NotImplementedError("training is outside this package's scope (sampling hot path only)")
+        """The reference's four AdamW groups (image_transformer_v2.py:708-719): weight-decayed and not, each at ``base_lr`` or, for the
+        mapping network and the AdaRMSNorm projections, at ``base_lr * mapping_lr_scale``."""
+        groups = {(wd, mp): [] for mp in (False, True) for wd in (True, False)}
+        for name, p in self.named_parameters():
+            tags = self._param_tags(name)
+            groups[("wd" in tags, "mapping" in tags)].append(p)
+        return [
+            {"params": groups[(True, False)], "lr": base_lr},
+            {"params": groups[(False, False)], "lr": base_lr, "weight_decay": 0.0},
+            {"params": groups[(True, True)], "lr": base_lr * mapping_lr_scale},
+            {"params": groups[(False, True)], "lr": base_lr * mapping_lr_scale, "weight_decay": 0.0},
+        ]
+
+    def loss_forward(self, x, sigma, aug_cond=None, class_cond=None, mapping_cond=None):
+        """F(x, sigma) for ``Denoiser.loss``: the fp32 ``ops``-path primal, in every arithmetic mode.  Under grad mode the output carries a
+        ``grad_fn`` whose backward fills the ``.grad`` of every parameter that requires grad (models/vjp.py); x, sigma and the conditioning
+        get none."""
+        if self.training:
+            drop = [f"levels[{i}].dropout = {lv.dropout}" for i, lv in enumerate(self.level_specs) if lv.dropout > 0]
+            if self.mapping_spec.dropout > 0:
+                drop.append(f"mapping dropout = {self.mapping_spec.dropout}")
+            if drop:
+                raise NotImplementedError(f"ImageTransformerDenoiserModelV2: dropout is not implemented ({', '.join(drop)}); call model.eval() "
+                                          f"for the dropout-free objective")
+        params = [p for p in self.parameters() if p.requires_grad] if torch.is_grad_enabled() else []
+        if params:
+            return _ParamGrad.apply(x, self, sigma, aug_cond, class_cond, mapping_cond, *params)
+        from . import vjp
+        return vjp.primal(self, x, sigma, aug_cond, class_cond, mapping_cond)
 
     # ---- forward ---------------------------------------------------------------------------------
     def forward(self, x, sigma, aug_cond=None, class_cond=None, mapping_cond=None):
@@ -915,7 +988,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
 
         Under grad mode with ``x.requires_grad`` the output carries a ``grad_fn`` whose backward is J^T grad w.r.t. x (models/vjp.py);
         the output itself is the same bits as without grad.  Gradients go to x only: the parameters get none (their ``.grad`` stays None;
-        training is out of scope), and sigma or a conditioning tensor that requires grad is refused with NotImplementedError."""
+        parameter gradients go through ``Denoiser.loss``, see ``loss_forward``), and sigma or a conditioning tensor that requires grad is refused with NotImplementedError."""
         if _wants_input_grad(x):
             return _InputGrad.apply(x, self, sigma, aug_cond, class_cond, mapping_cond, None)
         return self._run(x, sigma, aug_cond, class_cond, mapping_cond, None)

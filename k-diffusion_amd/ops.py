@@ -751,6 +751,170 @@ def precond_vjp(g, g_coef, sigma, sigma_data, h=None, h_coef=nat.PC_ONE, out=Non
                                            _stream()), "kd_precond_vjp_f32")
     return out
 
+
+# ---- parameter gradients and the training loss (csrc/wgrad_f32.hip; models/vjp.py, layers.Denoiser.loss).  fp32 arithmetic in every KDIFF_GEMM
+# mode; every sum runs in a fixed order through a workspace (no atomics), so repeat calls give the same bits.
+
+WGRAD_BLOCKS = 1024          # workgroups a weight-gradient GEMM aims at (row chunks x output tiles); the chunking is a function of the shape
+
+
+def wgrad_chunks(M, N, K):
+    """(chunk_rows, nchunk) of ``kd_wgrad_f32``: a fixed function of the shape, so that the order of the sum is too."""
+    tiles = -(-N // 64) * -(-K // 64)
+    nchunk = max(1, min(-(-WGRAD_BLOCKS // tiles), -(-M // 64), 65535))
+    chunk = -(-M // nchunk)
+    chunk = -(-chunk // 32) * 32
+    return chunk, -(-M // chunk)
+
+
+def wgrad(G, A, *, N=None, K=None, out=None, accumulate=False, gather=None, gather_geom=None, geglu=False, row_scale=None, col_scale=None,
+          rows_per_sample=None, alpha=None, precision=None):
+    """Weight gradient of a projection: dW[N, K] (+)= alpha * sum_m G[m, n] * A[m, k] over the stored rows m of G and A.
+
+    ``gather``: None, ("g" | "a", nat.WG_MERGE2x2 | nat.WG_PATCH_NCHW) -- that operand is read through the 2x2 token merge of a fine NHWC
+    grid or the patch gather of an NCHW image; ``gather_geom`` = (gh, gw, ph, pw, chan) of its coarse rows.  A's prologue: ``geglu`` (A
+    holds [value | gate] rows; the operand is value * gelu(gate)), ``row_scale`` [M] and ``col_scale`` ([K] shared or [B, K] per sample of
+    ``rows_per_sample`` rows).  ``alpha``: a one-element device tensor multiplying the result.  Arithmetic: the backward pass's rule --
+    split3 on the matrix cores under KDIFF_GEMM split3 / bf16 / fp8, fp32 FMAs under exact (``precision`` overrides)."""
+    g_mode = a_mode = nat.WG_PLAIN
+    gh = gw = ph = pw = chan = 0
+    if gather is not None:
+        which, mode = gather
+        gh, gw, ph, pw, chan = gather_geom
+        if which == "g":
+            g_mode = mode
+        else:
+            a_mode = mode
+    if g_mode == nat.WG_PLAIN:
+        N = G.shape[-1] if N is None else N
+        M = G.numel() // N
+    if a_mode == nat.WG_PLAIN:
+        K = (A.shape[-1] // 2 if geglu else A.shape[-1]) if K is None else K
+        M = A.numel() // (2 * K if geglu else K)
+    if g_mode != nat.WG_PLAIN:
+        N = ph * pw * chan
+    if a_mode != nat.WG_PLAIN:
+        K = ph * pw * chan
+    if g_mode == nat.WG_PLAIN and G.numel() != M * N:
+        raise ValueError(f"wgrad: G has {G.numel()} elements, expected {M} x {N}")
+    if a_mode == nat.WG_PLAIN and A.numel() != M * (2 * K if geglu else K):
+        raise ValueError(f"wgrad: A has {A.numel()} elements, expected {M} rows of {2 * K if geglu else K}")
+    if gather is not None:
+        gathered = G if g_mode != nat.WG_PLAIN else A
+        if gathered.numel() != M * ph * pw * chan or M % (gh * gw):
+            raise ValueError(f"wgrad: gathered operand has {gathered.numel()} elements for {M} rows of {ph * pw * chan}")
+    col_stride = 0
+    if col_scale is not None:
+        _chk(col_scale, "col_scale")
+        col_stride = 0 if col_scale.dim() == 1 else K
+        if col_scale.shape[-1] != K:
+            raise ValueError(f"wgrad: col_scale has {col_scale.shape[-1]} columns, expected {K}")
+        if col_stride and rows_per_sample is None:
+            rows_per_sample = M // col_scale.shape[0]
+    if row_scale is not None and _chk(row_scale, "row_scale").numel() != M:
+        raise ValueError(f"wgrad: row_scale has {row_scale.numel()} elements for {M} rows")
+    if out is None:
+        if accumulate:
+            raise ValueError("wgrad: accumulate needs out")
+        out = torch.empty(N, K, device=G.device, dtype=torch.float32)
+    elif _chk(out, "out").shape != (N, K):
+        raise ValueError(f"wgrad: out shape {tuple(out.shape)} != {(N, K)}")
+    split3 = (_prec_of(G) if precision is None else precision) != nat.PREC_EXACT
+    chunk, nchunk = wgrad_chunks(M, N, K)
+    ws = torch.empty(nchunk * N * K, device=G.device, dtype=torch.float32)
+    nat.check(nat.lib().kd_wgrad_f32(_p(_chk(G, "G")), g_mode, _p(_chk(A, "A")), a_mode, int(bool(geglu)), M, N, K, gh, gw, ph, pw, chan,
+                                     _p(row_scale), _p(col_scale), col_stride, int(rows_per_sample or 1), _p(None if alpha is None else _chk(alpha, "alpha")),
+                                     int(bool(accumulate)), int(split3), chunk, nchunk, _p(ws), _p(out), _stream()), "kd_wgrad_f32")
+    return out
+
+
+def row_rrms(x, eps=1e-6):
+    """rsqrt(mean(x^2) + eps) per row of x [..., d] -> [rows]."""
+    d = x.shape[-1]
+    rows = x.numel() // d
+    out = torch.empty(rows, device=x.device, dtype=torch.float32)
+    nat.check(nat.lib().kd_row_rrms_f32(_p(_chk(x, "x")), _p(out), rows, d, float(eps), _stream()), "kd_row_rrms_f32")
+    return out
+
+
+def colsum(a, b=None, b2=None, row_scale=None, rows_per_seg=None, out=None, accumulate=False):
+    """out[s, j] (+)= sum over the rows r of segment s of a[r, j] * (b[r, j] - b2[r, j]) * row_scale[r] (b, b2, row_scale optional);
+    a [..., cols] -> [rows / rows_per_seg, cols] (one segment by default)."""
+    cols = a.shape[-1]
+    rows = a.numel() // cols
+    rps = rows if rows_per_seg is None else rows_per_seg
+    for name, t in (("b", b), ("b2", b2)):
+        if t is not None and _chk(t, name).numel() != a.numel():
+            raise ValueError(f"colsum: {name} has {t.numel()} elements, a has {a.numel()}")
+    if row_scale is not None and _chk(row_scale, "row_scale").numel() != rows:
+        raise ValueError(f"colsum: row_scale has {row_scale.numel()} elements for {rows} rows")
+    if rows % rps:
+        raise ValueError(f"colsum: {rows} rows are not segments of {rps}")
+    nseg = rows // rps
+    if out is None:
+        if accumulate:
+            raise ValueError("colsum: accumulate needs out")
+        out = torch.empty(nseg, cols, device=a.device, dtype=torch.float32)
+    elif _chk(out, "out").numel() != nseg * cols:
+        raise ValueError(f"colsum: out has {out.numel()} elements, expected {nseg * cols}")
+    ws = torch.empty(nseg * (-(-rps // 64)) * cols, device=a.device, dtype=torch.float32)
+    nat.check(nat.lib().kd_colsum_f32(_p(_chk(a, "a")), _p(b), _p(b2), _p(row_scale), rows, cols, rps, int(bool(accumulate)), _p(ws), _p(out),
+                                      _stream()), "kd_colsum_f32")
+    return out
+
+
+def attn_scale_grad(colsums, scale_h, nh, out=None, accumulate=False):
+    """Gradient of the cosine-sim scale (:106-114) from ``colsum(g_prep, prep)`` over the tokens of a [.., 3 * nh * 64] qkv."""
+    if _chk(colsums, "colsums").numel() != 3 * nh * 64:
+        raise ValueError(f"attn_scale_grad: {colsums.numel()} column sums for {nh} heads")
+    out = torch.empty(nh, device=colsums.device, dtype=torch.float32) if out is None else out
+    nat.check(nat.lib().kd_attn_scale_grad_f32(_p(colsums), _p(_chk(scale_h, "scale")), nh, int(bool(accumulate)), _p(_chk(out, "out")), _stream()),
+              "kd_attn_scale_grad_f32")
+    return out
+
+
+def class_emb_grad(g, ids, n_cls, out=None, accumulate=False):
+    """Gradient of the class embedding table [n_cls, d] from the gradient g [B, d] on the looked-up rows; samples added in ascending order."""
+    B, d = g.shape
+    if _chk(ids, "ids", torch.int64).numel() != B:
+        raise ValueError(f"class_emb_grad: {ids.numel()} ids for batch {B}")
+    out = torch.empty(n_cls, d, device=g.device, dtype=torch.float32) if out is None else out
+    nat.check(nat.lib().kd_class_emb_grad_f32(_p(_chk(g, "g")), _p(ids), B, d, n_cls, int(bool(accumulate)), _p(_chk(out, "out")), _stream()),
+              "kd_class_emb_grad_f32")
+    return out
+
+
+def loss_prep(input, noise, sigma, sigma_data):
+    """(noised, noised * c_in): the model input of Denoiser.loss (layers.py:78-81).  sigma: [B]."""
+    B = input.shape[0]
+    if _chk(noise, "noise").shape != _chk(input, "input").shape:
+        raise ValueError(f"loss: noise shape {tuple(noise.shape)} != input shape {tuple(input.shape)}")
+    noised, x_in = torch.empty_like(input), torch.empty_like(input)
+    nat.check(nat.lib().kd_loss_prep_f32(_p(input), _p(noise), _p(_chk(sigma, "sigma")), float(sigma_data), _p(noised), _p(x_in), B, input.numel() // B,
+                                         _stream()), "kd_loss_prep_f32")
+    return noised, x_in
+
+
+def loss(f, input, noised, sigma, sigma_data, weighting, c_weight=None):
+    """Per-sample losses [B] = mean((f - target)^2) * c_weight, target = (input - c_skip noised) / c_out (layers.py:82-85)."""
+    B = input.shape[0]
+    if _chk(f, "f").shape != input.shape:
+        raise ValueError(f"loss: model output shape {tuple(f.shape)} != input shape {tuple(input.shape)}")
+    out = torch.empty(B, device=f.device, dtype=torch.float32)
+    nat.check(nat.lib().kd_loss_f32(_p(f), _p(_chk(input, "input")), _p(_chk(noised, "noised")), _p(_chk(sigma, "sigma")), float(sigma_data), int(weighting),
+                                    _p(None if c_weight is None else _chk(c_weight, "c_weight")), _p(out), B, input.numel() // B, _stream()), "kd_loss_f32")
+    return out
+
+
+def loss_vjp(f, input, noised, sigma, sigma_data, weighting, g_loss, c_weight=None):
+    """Gradient of ``loss`` w.r.t. the model output f from the gradient g_loss [B] on the losses."""
+    B = input.shape[0]
+    out = torch.empty_like(f)
+    nat.check(nat.lib().kd_loss_vjp_f32(_p(_chk(f, "f")), _p(_chk(input, "input")), _p(_chk(noised, "noised")), _p(_chk(sigma, "sigma")), float(sigma_data),
+                                        int(weighting), _p(None if c_weight is None else _chk(c_weight, "c_weight")), _p(_chk(g_loss, "g_loss")), _p(out),
+                                        B, input.numel() // B, _stream()), "kd_loss_vjp_f32")
+    return out
+
 def ll_div(x, denoised, denoised_dot, v, sigma):
     """(d, d_ll): d = (x - D) / sigma (to_d, sampling.py:46) and d_ll[b] = sum_b v * (v - D_dot) / sigma_b.  sigma: [B] fp32."""
     B = x.shape[0]
