@@ -483,6 +483,43 @@ int kd_loss_f32(const float* f, const float* input, const float* noised, const f
 int kd_loss_vjp_f32(const float* f, const float* input, const float* noised, const float* sigma, float sigma_data, int weighting,
                     const float* c_weight, const float* g_loss, float* g_f, int batch, long long per_sample, void* stream);
 
+/* Sample-quality metrics (k_diffusion/evaluation.py:93-161; csrc/metrics_f32.hip).  fp32-grade arithmetic: the Gram tiles follow the backward
+ * pass's rule (split3 = 1: bf16 hi / lo operands, 3 MFMAs per product, fp32 accumulate; 0: fp32 FMAs).  Every sum has a fixed order (fp64
+ * workspace, no atomics): repeat calls give the same bits.  Matrices are row-major fp32; batch items sx / sy elements apart.
+ *   kd_mmd_poly_f32     : out[b] (+)= scale * squared_mmd(X[b], Y[b]) with k(x, y) = (x . y / d + 1)^3, X [m, d], Y [n, d] (fewer than 2
+ *                         rows give the reference's nan / inf); the
+ *                         kernel matrices are never written.  ws holds batch * (tm (tm + 1) / 2 + tn (tn + 1) / 2 + tm tn) doubles, tm / tn =
+ *                         m / n rounded up to 64-row tiles.
+ *   kd_poly_kernel_f32  : K[b] = (X[b] Y[b]^T / d + 1)^3, [m, n] per batch item.
+ *   kd_mmd_mats_f32     : out[b] = squared_mmd from kernel matrices kxx [m, m], kyy [n, n], kxy [m, n] (diagonals of kxx, kyy dropped); ws
+ *                         holds batch * 3 * ceil(max(m m, n n, m n) / 4096) doubles.
+ *   kd_jacobi_sweep_f64 : one sweep of one-sided Jacobi on the rows of B [batch, n, n] (fp64; n - 1 rounds, n even, of n / 2 disjoint row
+ *                         pairs, round robin; a pair whose |cos| exceeds tol is rotated to orthogonal, and so are the rows of Vt if given).
+ *                         conv holds batch * ceil(n / 2) doubles; off[0] = the largest |cos| the sweep met.
+ *   kd_sym_lower_f64    : B = the symmetric matrices of a's lower triangles (a fp32, or fp64 if a_f64) + diag_add I (fp64); Vt = I if not NULL.
+ *   kd_row_sqrt_norm_f64: s[r] = sqrt(||B[r, :]||).
+ *   kd_gemm_tn_f64      : C[b] = G[b]^T diag(row_scale[b]) A[b] (G [M, N], A [M, K], row_scale [M] or NULL) in fp64, to C64 or rounded to C32.
+ *   kd_center_f32       : mean = colsum / rows, xc = x - mean in fp64 (mean may be NULL).
+ *   kd_transpose_f64    : out[b] = a[b]^T, [batch, n, n].
+ *   kd_sqrtm_vjp_div_f64: out[b, i, j] = m[b, i, j] / (s[b, i] + s[b, j]).
+ *   kd_f32_to_f64       : out = (double)a.
+ *   kd_fid_finish_f32   : out = |mean_x - mean_y|^2 + tr cov_x + tr cov_y - 2 sum sq (fp64 covariances and sums). */
+int kd_mmd_poly_f32(const float* X, long long sx, long long m, const float* Y, long long sy, long long n, int d, int batch, int split3, double* ws,
+                    float scale, int accumulate, float* out, void* stream);
+int kd_poly_kernel_f32(const float* X, long long sx, long long m, const float* Y, long long sy, long long n, int d, int batch, int split3, float* K,
+                       void* stream);
+int kd_mmd_mats_f32(const float* kxx, const float* kyy, const float* kxy, long long m, long long n, int batch, double* ws, float* out, void* stream);
+int kd_jacobi_sweep_f64(double* B, double* Vt, int batch, int n, double tol, double* conv, double* off, void* stream);
+int kd_sym_lower_f64(const void* a, int a_f64, double* B, double* Vt, int batch, int n, double diag_add, void* stream);
+int kd_row_sqrt_norm_f64(const double* B, long long rows, int n, double* s, void* stream);
+int kd_gemm_tn_f64(const double* G, const double* A, const double* row_scale, int batch, int M, int N, int K, double* C64, float* C32, void* stream);
+int kd_center_f32(const float* x, const float* colsum, long long rows, int d, double* xc, float* mean, void* stream);
+int kd_transpose_f64(const double* a, double* out, int batch, int n, void* stream);
+int kd_sqrtm_vjp_div_f64(const double* m, const double* s, int batch, int n, double* out, void* stream);
+int kd_f32_to_f64(const float* a, double* out, long long n, void* stream);
+int kd_fid_finish_f32(const float* mean_x, const float* mean_y, const double* cov_x, const double* cov_y, const double* sq, int d, float* out,
+                      void* stream);
+
 /* Final image conversion (k_diffusion/utils.py:27-34 to_pil_image): u8 = trunc((clamp(x,-1,1)+1)/2*255)
  * (torchvision's to_pil_image does mul(255).byte(), i.e. truncation) */
 int kd_to_uint8(const float* x, unsigned char* y, long long n, void* stream);

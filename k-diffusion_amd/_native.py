@@ -160,6 +160,18 @@ SIGNATURES = {
     "kd_loss_prep_f32": [_vp, _vp, _vp, _f, _vp, _vp, _i, _ll, _vp],
     "kd_loss_f32": [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _i, _ll, _vp],
     "kd_loss_vjp_f32": [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _i, _ll, _vp],
+    "kd_mmd_poly_f32": [_vp, _ll, _ll, _vp, _ll, _ll, _i, _i, _i, _vp, _f, _i, _vp, _vp],
+    "kd_poly_kernel_f32": [_vp, _ll, _ll, _vp, _ll, _ll, _i, _i, _i, _vp, _vp],
+    "kd_mmd_mats_f32": [_vp, _vp, _vp, _ll, _ll, _i, _vp, _vp, _vp],
+    "kd_jacobi_sweep_f64": [_vp, _vp, _i, _i, _d, _vp, _vp, _vp],
+    "kd_sym_lower_f64": [_vp, _i, _vp, _vp, _i, _i, _d, _vp],
+    "kd_row_sqrt_norm_f64": [_vp, _ll, _i, _vp, _vp],
+    "kd_gemm_tn_f64": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "kd_center_f32": [_vp, _vp, _ll, _i, _vp, _vp, _vp],
+    "kd_transpose_f64": [_vp, _vp, _i, _i, _vp],
+    "kd_sqrtm_vjp_div_f64": [_vp, _vp, _i, _i, _vp, _vp],
+    "kd_f32_to_f64": [_vp, _vp, _ll, _vp],
+    "kd_fid_finish_f32": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
     "kd_prof_enable": [_i],
     "kd_prof_count": [],
     "kd_prof_get": [_i, C.c_char_p, _i, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double)],

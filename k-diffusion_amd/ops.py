@@ -978,3 +978,175 @@ def rk_error_partial(ks, coeffs, y0, y1, atol, rtol):
                                         _stream()), "kd_rk_error_f32")
     del keep
     return part
+
+
+# ---- sample-quality metrics (csrc/metrics_f32.hip; evaluation.polynomial_kernel / squared_mmd / kid).  The Gram tiles follow the backward pass's
+# rule (split3 unless exact); every sum runs in a fixed order through an fp64 workspace, so repeat calls give the same bits.
+
+def _batch3(t, name):
+    """[..., r, d] -> a contiguous [B, r, d] view and B."""
+    _chk(t, name)
+    r, d = t.shape[-2], t.shape[-1]
+    b = t.numel() // max(1, r * d)
+    return t.reshape(b, r, d), b
+
+
+def _split3_of(x, precision):
+    return (_prec_of(x) if precision is None else precision) != nat.PREC_EXACT
+
+
+def mmd_poly(x, y, out=None, scale=1.0, accumulate=False, precision=None):
+    """out[b] (+)= scale * squared MMD of x[b] [m, d] and y[b] [n, d] with the polynomial kernel (x . y / d + 1)^3, the kernel matrices never
+    written.  x, y: [m, d] / [n, d] or [B, m, d] / [B, n, d]; out: [B] (or one element)."""
+    x3, b = _batch3(x, "x")
+    y3, by = _batch3(y, "y")
+    m, d = x3.shape[1], x3.shape[2]
+    n = y3.shape[1]
+    if by != b or y3.shape[2] != d:
+        raise ValueError(f"mmd_poly: x {tuple(x.shape)} and y {tuple(y.shape)} do not pair up")
+    if out is None:
+        if accumulate:
+            raise ValueError("mmd_poly: accumulate needs out")
+        out = torch.empty(b, device=x.device, dtype=torch.float32)
+    elif _chk(out, "out").numel() != b:
+        raise ValueError(f"mmd_poly: out has {out.numel()} elements for {b} batch items")
+    tm, tn = -(-m // 64), -(-n // 64)
+    ws = torch.empty(max(1, b * (tm * (tm + 1) // 2 + tn * (tn + 1) // 2 + tm * tn)), device=x.device, dtype=torch.float64)
+    nat.check(nat.lib().kd_mmd_poly_f32(_p(x3), m * d, m, _p(y3), n * d, n, d, b, int(_split3_of(x, precision)), _p(ws), float(scale),
+                                        int(bool(accumulate)), _p(out), _stream()), "kd_mmd_poly_f32")
+    return out
+
+
+def poly_kernel(x, y, precision=None):
+    """(x y^T / d + 1)^3 of x [B, m, d] and y [B, n, d] (or [m, d] / [n, d]) -> [B, m, n] (or [m, n])."""
+    x3, b = _batch3(x, "x")
+    y3, by = _batch3(y, "y")
+    m, d = x3.shape[1], x3.shape[2]
+    n = y3.shape[1]
+    if by != b or y3.shape[2] != d:
+        raise ValueError(f"poly_kernel: x {tuple(x.shape)} and y {tuple(y.shape)} do not pair up")
+    out = torch.empty(*x.shape[:-2], m, n, device=x.device, dtype=torch.float32)
+    if out.numel():
+        nat.check(nat.lib().kd_poly_kernel_f32(_p(x3), m * d, m, _p(y3), n * d, n, d, b, int(_split3_of(x, precision)), _p(out), _stream()),
+                  "kd_poly_kernel_f32")
+    return out
+
+
+def mmd_mats(kxx, kyy, kxy):
+    """Squared MMD from kernel matrices kxx [B, m, m], kyy [B, n, n], kxy [B, m, n] (diagonals of kxx and kyy dropped) -> [B]."""
+    a, b = _batch3(kxx, "kxx")
+    c, bc = _batch3(kyy, "kyy")
+    e, be = _batch3(kxy, "kxy")
+    m, n = a.shape[1], c.shape[1]
+    if bc != b or be != b or a.shape[2] != m or c.shape[2] != n or e.shape[1:] != (m, n):
+        raise ValueError(f"mmd_mats: kernel matrices {tuple(kxx.shape)}, {tuple(kyy.shape)}, {tuple(kxy.shape)} do not pair up")
+    out = torch.empty(b, device=kxx.device, dtype=torch.float32)
+    ws = torch.empty(max(1, b * 3 * (-(-max(m * m, n * n, m * n) // 4096))), device=kxx.device, dtype=torch.float64)
+    nat.check(nat.lib().kd_mmd_mats_f32(_p(a), _p(c), _p(e), m, n, b, _p(ws), _p(out), _stream()), "kd_mmd_mats_f32")
+    return out
+
+
+# the eigensolver of sqrtm_eig / fid: one-sided Jacobi in fp64 (csrc/metrics_f32.hip), products of its factors on kd_gemm_tn_f64
+
+JACOBI_MAX_SWEEPS = 60
+jacobi_stats = {"sweeps": 0, "off": []}        # the last solve: its sweep count and the largest |cos| of each sweep (benchmarks read it)
+
+
+def _f64(*shape, device):
+    return torch.empty(*shape, device=device, dtype=torch.float64)
+
+
+def jacobi_tol(n):
+    """Rotation / convergence threshold on |cos| of two rows: a few fp64 ulps grown with sqrt(n), as in one-sided Jacobi SVD codes."""
+    return 8.0 * math.sqrt(max(n, 1)) * 2.0 ** -52
+
+
+def jacobi_rows(B, Vt=None):
+    """One-sided Jacobi, in place, on the fp64 rows of B [batch, n, n] (and Vt, if given): afterwards the rows of B are mutually orthogonal,
+    B = A V with row i of norm |lambda_i| (sigma_i), and Vt = V^T (when it started as I).  The convergence test reads one value per sweep."""
+    b, n = B.shape[0], B.shape[-1]
+    lib = nat.lib()
+    conv, off = _f64(b * ((n + 1) // 2), device=B.device), _f64(1, device=B.device)
+    tol, offs = jacobi_tol(n), []
+    while len(offs) < JACOBI_MAX_SWEEPS:
+        nat.check(lib.kd_jacobi_sweep_f64(_p(B), _p(Vt), b, n, tol, _p(conv), _p(off), _stream()), "kd_jacobi_sweep_f64")
+        offs.append(off.item())
+        if not offs[-1] > tol:
+            break
+    jacobi_stats.update(sweeps=len(offs), off=offs)
+    return B, Vt
+
+
+def sym_lower_f64(a, vectors=False, diag_add=0.0):
+    """(B, Vt): the fp64 symmetric matrices of the lower triangles of a [batch, n, n] (fp32 or fp64) plus diag_add I, and Vt = I (if
+    ``vectors``)."""
+    b, n = a.shape[0], a.shape[-1]
+    B = _f64(b, n, n, device=a.device)
+    Vt = _f64(b, n, n, device=a.device) if vectors else None
+    a64 = a.dtype == torch.float64
+    nat.check(nat.lib().kd_sym_lower_f64(_p(_chk(a, "a", a.dtype if a64 else torch.float32)), int(a64), _p(B), _p(Vt), b, n, float(diag_add),
+                                         _stream()), "kd_sym_lower_f64")
+    return B, Vt
+
+
+def row_sqrt_norm_f64(B):
+    """sqrt(||row||) of every row of B [batch, n, n] -> [batch, n] (fp64)."""
+    n = B.shape[-1]
+    out = _f64(*B.shape[:-1], device=B.device)
+    nat.check(nat.lib().kd_row_sqrt_norm_f64(_p(_chk(B, "B", torch.float64)), B.numel() // n, n, _p(out), _stream()), "kd_row_sqrt_norm_f64")
+    return out
+
+
+def gemm_tn_f64(G, A, row_scale=None, out32=False):
+    """G[b]^T diag(row_scale[b]) A[b] in fp64 for G [batch, M, N], A [batch, M, K] -> [batch, N, K] (fp64, or rounded to fp32)."""
+    b, M, N = G.shape
+    K = A.shape[-1]
+    if A.shape[:2] != (b, M) or (row_scale is not None and row_scale.shape != (b, M)):
+        raise ValueError(f"gemm_tn_f64: G {tuple(G.shape)}, A {tuple(A.shape)} do not pair up")
+    out = torch.empty(b, N, K, device=G.device, dtype=torch.float32 if out32 else torch.float64)
+    nat.check(nat.lib().kd_gemm_tn_f64(_p(_chk(G, "G", torch.float64)), _p(_chk(A, "A", torch.float64)),
+                                       _p(None if row_scale is None else _chk(row_scale, "row_scale", torch.float64)), b, M, N, K,
+                                       None if out32 else _p(out), _p(out) if out32 else None, _stream()), "kd_gemm_tn_f64")
+    return out
+
+
+def center(x):
+    """(x - mean in fp64, mean) of x [rows, d] over its rows; the column sums from ``colsum``."""
+    rows, d = x.shape
+    s = colsum(x)
+    xc = _f64(rows, d, device=x.device)
+    mean = torch.empty(d, device=x.device, dtype=torch.float32)
+    nat.check(nat.lib().kd_center_f32(_p(_chk(x, "x")), _p(s), rows, d, _p(xc), _p(mean), _stream()), "kd_center_f32")
+    return xc, mean
+
+
+def transpose_f64(a):
+    """a[b]^T for a [batch, n, n] (fp64)."""
+    out = torch.empty_like(a)
+    nat.check(nat.lib().kd_transpose_f64(_p(_chk(a, "a", torch.float64)), _p(out), a.shape[0], a.shape[-1], _stream()), "kd_transpose_f64")
+    return out
+
+
+def sqrtm_vjp_div_f64(m, s):
+    """m[b, i, j] / (s[b, i] + s[b, j]) for m [batch, n, n], s [batch, n] (fp64)."""
+    out = torch.empty_like(m)
+    nat.check(nat.lib().kd_sqrtm_vjp_div_f64(_p(_chk(m, "m", torch.float64)), _p(_chk(s, "s", torch.float64)), m.shape[0], m.shape[-1], _p(out),
+                                             _stream()), "kd_sqrtm_vjp_div_f64")
+    return out
+
+
+def to_f64(a):
+    out = torch.empty(a.shape, device=a.device, dtype=torch.float64)
+    if a.numel():
+        nat.check(nat.lib().kd_f32_to_f64(_p(_chk(a, "a")), _p(out), a.numel(), _stream()), "kd_f32_to_f64")
+    return out
+
+
+def fid_finish(mean_x, mean_y, cov_x, cov_y, sq):
+    """|mean_x - mean_y|^2 + tr cov_x + tr cov_y - 2 sum(sq) -> a 0-dim fp32 tensor (fp64 covariances and sums)."""
+    d = mean_x.numel()
+    out = torch.empty((), device=mean_x.device, dtype=torch.float32)
+    nat.check(nat.lib().kd_fid_finish_f32(_p(_chk(mean_x, "mean_x")), _p(_chk(mean_y, "mean_y")), _p(_chk(cov_x, "cov_x", torch.float64)),
+                                          _p(_chk(cov_y, "cov_y", torch.float64)), _p(_chk(sq, "sq", torch.float64)), d, _p(out), _stream()),
+              "kd_fid_finish_f32")
+    return out
