@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Cost of a training step's gradients (``Denoiser.loss`` + backward into every parameter, models/vjp.py) against one ``forward`` of the same
-denoiser, and the peak device memory of each.  Synthetic weights (synth.py), ``eval()``, fp32 split3 arithmetic by default.
+denoiser, and the peak device memory of each.  Synthetic weights (synth.py), ``eval()``, fp32 split3 arithmetic by default; with
+``--dropout`` the training step runs in training mode with ``model.enable_dropout()`` at the config's rates (``--dropout-rate`` sets them).
 
-    python benchmarks/train_bench.py [--config configs/config_oxford_flowers.json] [--batches 1 8 32] [--iters 3]
+    python benchmarks/train_bench.py [--config configs/config_oxford_flowers.json] [--batches 1 8 32] [--iters 3] [--dropout] [--dropout-rate 0 0 0.1]
 
 Prints one JSON line per batch size ({"batch", "forward_ms", "train_ms", "ratio", "forward_peak_mib", "train_peak_mib"}).  Times are host
 clocks around work that ends in a device synchronise, after one warm-up call of every shape; the peaks are torch.cuda.max_memory_allocated
@@ -46,13 +47,22 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 32])
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--sigma", type=float, default=2.0)
+    ap.add_argument("--dropout", action="store_true", help="train in training mode with model.enable_dropout() at the config's dropout rates "
+                                                             "(the forward still runs in eval())")
+    ap.add_argument("--dropout-rate", type=float, nargs="+", default=None, help="per-level dropout rates (one value: every level) in place "
+                                                                                 "of the config's")
     args = ap.parse_args()
     os.environ.setdefault("KDIFF_GEMM", "split3")
-    cfg = K.config.load_config(json.load(open(args.config)))
+    raw = json.load(open(args.config))
+    if args.dropout_rate is not None:
+        raw["model"]["dropout_rate"] = args.dropout_rate[0] if len(args.dropout_rate) == 1 else args.dropout_rate
+    cfg = K.config.load_config(raw)
     mc = cfg["model"]
     model = K.config.make_model(cfg).eval()
     model.load_state_dict(K.synth.synth_state_dict(model.state_dict(), seed=1))
     model = model.to("cuda")
+    if args.dropout:
+        model.enable_dropout()
     den = K.Denoiser(model, mc["sigma_data"])
     nc = cfg.get("dataset", {}).get("num_classes", 0)
     shape = (mc["input_channels"], *mc["input_size"])
@@ -64,15 +74,18 @@ def main():
         kw = {"class_cond": torch.arange(B, device="cuda") % nc} if nc else {}
 
         def fwd():
+            model.eval()
             with torch.no_grad():
                 return den(x, sig, **kw)
 
         def train():
+            model.train(args.dropout)
             model.zero_grad(set_to_none=False)
             den.loss(x, noise, sig, **kw).mean().backward()
         t_f, t_t = timed(fwd, args.iters), timed(train, args.iters)
         m_f, m_t = peak_mib(fwd), peak_mib(train)
-        print(json.dumps({"config": os.path.basename(args.config), "mode": os.environ["KDIFF_GEMM"], "batch": B, "forward_ms": round(t_f, 3),
+        print(json.dumps({"config": os.path.basename(args.config), "mode": os.environ["KDIFF_GEMM"], "batch": B,
+                          "dropout": mc["dropout_rate"] if args.dropout else None, "forward_ms": round(t_f, 3),
                           "train_ms": round(t_t, 3), "ratio": round(t_t / t_f, 2), "forward_peak_mib": round(m_f, 1),
                           "train_peak_mib": round(m_t, 1)}), flush=True)
 

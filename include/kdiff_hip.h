@@ -483,6 +483,30 @@ int kd_loss_f32(const float* f, const float* input, const float* noised, const f
 int kd_loss_vjp_f32(const float* f, const float* input, const float* noised, const float* sigma, float sigma_data, int weighting,
                     const float* c_weight, const float* g_loss, float* g_f, int batch, long long per_sample, void* stream);
 
+/* Dropout of the training loss (the reference's nn.Dropout at image_transformer_v2.py:394, :441, :474 (attention output, after the head
+ * merge, before out_proj), :491 (FF hidden, after GEGLU, before down_proj), :564 (mapping block, GEGLU output before down_proj); csrc/dropout_f32.hip,
+ * models/vjp.py).  No mask is stored: the primal, the backward's recomputation and the reverse walk regenerate the same bits.
+ * Mask contract:
+ *   key       one int64 per loss call, drawn on the device and read through a pointer (the kernels never sync with the host);
+ *   site s    2^62 | (2 i) for the attention output and 2^62 | (2 i + 1) for the FF hidden of the layer at position i of
+ *             image_transformer_v2.hourglass(model); 2^62 | 2^32 | k for mapping block k (image_transformer_v2.dropout_sites);
+ *   element e the row-major index in the site's tensor: [B, h, w, nh * 64] (attention), [B, h, w, d_ff] (FF), [B, mapping d_ff];
+ *   mask      w = word e & 3 of philox4x32_10(key, counter (e >> 2, s)) (csrc/philox.h, the generator of kd_brownian_f32 / kd_randn_f32,
+ *             whose counters never set bit 62 of the second half); keep iff w >= threshold, threshold = floor(p 2^32); y = x * m with
+ *             m = keep ? scale : 0 and scale = (float)(1 / (1 - p)) computed in double (NaN and Inf stay NaN at dropped elements).
+ *   kd_dropout_f32        : y = x * m over n elements (y may be x).  Also the transpose: the gradient through the site.
+ *   kd_geglu_vjp_drop_f32 : kd_geglu_vjp_f32 with g_y * m in place of g_y: the same bits as kd_dropout_f32 on g_y followed by kd_geglu_vjp_f32.
+ *   kd_wgrad_drop_f32     : kd_wgrad_f32 with A's plain [M, K] operand (after its GEGLU prologue) times m, element e = m K + k: dW_down =
+ *                           G^T (mask * geglu(U)) without a masked hidden in memory.  bits: (M K + 31) / 32 words of device workspace that
+ *                           receive the mask (bit j of word w: element 32 w + j) ahead of the GEMM.  threshold 0: kd_wgrad_f32's bits. */
+int kd_dropout_f32(const float* x, float* y, long long n, const long long* key, unsigned long long site, unsigned threshold, float scale, void* stream);
+int kd_geglu_vjp_drop_f32(const float* h, const float* g_y, float* g_h, int rows, int d_ff, const long long* key, unsigned long long site,
+                          unsigned threshold, float scale, void* stream);
+int kd_wgrad_drop_f32(const float* G, int g_mode, const float* A, int a_mode, int a_geglu, long long M, int N, int K, int gh, int gw, int ph, int pw,
+                      int chan, const float* row_scale, const float* col_scale, int col_stride, int rows_per_sample, const float* alpha, int accumulate,
+                      int split3, int chunk_rows, int nchunk, float* ws, float* dW, const long long* key, unsigned long long site,
+                      unsigned threshold, float scale, unsigned* bits, void* stream);
+
 /* Sample-quality metrics (k_diffusion/evaluation.py:93-161; csrc/metrics_f32.hip).  fp32-grade arithmetic: the Gram tiles follow the backward
  * pass's rule (split3 = 1: bf16 hi / lo operands, 3 MFMAs per product, fp32 accumulate; 0: fp32 FMAs).  Every sum has a fixed order (fp64
  * workspace, no atomics): repeat calls give the same bits.  Matrices are row-major fp32; batch items sx / sy elements apart.

@@ -83,6 +83,7 @@ class KdCall(C.Structure):
 
 
 _vp, _i, _f, _ll, _d = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_double
+_u, _ull = C.c_uint, C.c_ulonglong
 
 # name -> argtypes; every symbol declared in include/kdiff_hip.h
 SIGNATURES = {
@@ -147,12 +148,16 @@ SIGNATURES = {
     "kd_rk_error_f32": [_vp, _vp, _i, _vp, _vp, _f, _f, _ll, _vp, _vp],
     "kd_rmsnorm_vjp_f32": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp],
     "kd_geglu_vjp_f32": [_vp, _vp, _vp, _i, _i, _vp],
+    "kd_geglu_vjp_drop_f32": [_vp, _vp, _vp, _i, _i, _vp, _ull, _u, _f, _vp],
     "kd_qk_prep_vjp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "kd_attn_global_vjp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "kd_attn_window_vjp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "kd_attn_na2d_vjp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "kd_precond_vjp_f32": [_vp, _i, _vp, _i, _vp, _f, _vp, _i, _ll, _vp],
     "kd_wgrad_f32": [_vp, _i, _vp, _i, _i, _ll, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "kd_wgrad_drop_f32": [_vp, _i, _vp, _i, _i, _ll, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp,
+                          _vp, _ull, _u, _f, _vp, _vp],
+    "kd_dropout_f32": [_vp, _vp, _ll, _vp, _ull, _u, _f, _vp],
     "kd_row_rrms_f32": [_vp, _vp, _ll, _i, _f, _vp],
     "kd_colsum_f32": [_vp, _vp, _vp, _vp, _ll, _i, _ll, _i, _vp, _vp, _vp],
     "kd_attn_scale_grad_f32": [_vp, _vp, _i, _i, _vp, _vp],

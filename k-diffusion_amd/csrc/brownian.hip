@@ -17,24 +17,9 @@
 // End points repeat between queries (every sigma_i is an end point of 2-4 queries), so the cached
 // entry point lets the caller keep W(t) tensors and skip their descents.
 #include "kd_common.h"
+#include "philox.h"
 
 namespace kd {
-
-struct Philox4 { unsigned x0, x1, x2, x3; };
-
-__device__ __forceinline__ Philox4 philox4x32_10(unsigned long long key, unsigned long long elem, unsigned long long node) {
-  unsigned c0 = (unsigned)elem, c1 = (unsigned)(elem >> 32), c2 = (unsigned)node, c3 = (unsigned)(node >> 32);
-  unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return {c0, c1, c2, c3};
-}
 
 // Box-Muller on hardware transcendentals: radius from a word mapped to (0, 1], cosine of `rev` revolutions
 __device__ __forceinline__ float bm_radius(unsigned w) {

@@ -4,7 +4,7 @@
 // below needs a rule of its own:
 //
 //   kd_rmsnorm_vjp_f32       rms_norm / AdaRMSNorm (image_transformer_v2.py:98-103, :142-166): input gradient, scale held fixed
-//   kd_geglu_vjp_f32         linear_geglu's gate (:89-95), erf-GELU
+//   kd_geglu_vjp_f32         linear_geglu's gate (:89-95), erf-GELU (kd_geglu_vjp_drop_f32: with the hidden's dropout mask on g_y)
 //   kd_qk_prep_vjp_f32       scale_for_cosine_sim (:106-121) + axial RoPE (:187-231), scale held fixed
 //   kd_attn_*_vjp_f32        softmax attention: global (:383,:392), neighbourhood (:428), shifted window (:253-337)
 //   kd_precond_vjp_f32       the Karras preconditioning's per-sample scalings (k_diffusion/layers.py:70-74, :88-90) on a gradient
@@ -13,6 +13,7 @@
 // atomics, bit-identical on repeat.
 #include "kd_common.h"
 #include "deriv_f32.h"
+#include "philox.h"
 
 #include <cmath>
 
@@ -55,16 +56,33 @@ __global__ __launch_bounds__(256) void rmsnorm_vjp_kernel(const float* __restric
 }
 
 // ---- GEGLU: y = a * gelu(g)  =>  ga = gy gelu(g), gg = gy a gelu'(g) ------------------------------------------------------
+__device__ __forceinline__ void geglu_vjp_elem(const float* __restrict__ h, float gyi, float* gh, long i, int d_ff) {
+  const long row = i / d_ff;
+  const int j = (int)(i - row * d_ff);
+  const long ia = row * 2 * d_ff + j, ig = ia + d_ff;
+  const float a = h[ia], g = h[ig];
+  const float cdf = 0.5f * (1.0f + erff(g * 0.70710678118654752440f));
+  const float dgelu = cdf + g * (0.39894228040143267794f * expf(-0.5f * g * g));
+  gh[ia] = gyi * (g * cdf);
+  gh[ig] = gyi * a * dgelu;
+}
+
 __global__ __launch_bounds__(256) void geglu_vjp_kernel(const float* __restrict__ h, const float* __restrict__ gy, float* gh, long n, int d_ff) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const long row = i / d_ff;
-    const int j = (int)(i - row * d_ff);
-    const long ia = row * 2 * d_ff + j, ig = ia + d_ff;
-    const float a = h[ia], g = h[ig], gyi = gy[i];
-    const float cdf = 0.5f * (1.0f + erff(g * 0.70710678118654752440f));
-    const float dgelu = cdf + g * (0.39894228040143267794f * expf(-0.5f * g * g));
-    gh[ia] = gyi * (g * cdf);
-    gh[ig] = gyi * a * dgelu;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) geglu_vjp_elem(h, gy[i], gh, i, d_ff);
+}
+
+// the same with the dropout mask of the hidden activation on gy (dropout_f32.hip's contract): one Philox block per 4 elements per lane
+__global__ __launch_bounds__(256) void geglu_vjp_drop_kernel(const float* __restrict__ h, const float* __restrict__ gy, float* gh, long n, int d_ff,
+                                                             const long long* __restrict__ key_ptr, unsigned long long site, unsigned threshold,
+                                                             float scale) {
+  const unsigned long long key = (unsigned long long)key_ptr[0];
+  const long quads = (n + 3) >> 2;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < quads; q += (long)gridDim.x * 256) {
+    const Philox4 r = philox4x32_10(key, (unsigned long long)q, site);
+    for (int k = 0; k < 4 && 4 * q + k < n; ++k) {
+      const long i = 4 * q + k;
+      geglu_vjp_elem(h, gy[i] * (philox_word(r, k) >= threshold ? scale : 0.0f), gh, i, d_ff);
+    }
   }
 }
 
@@ -353,6 +371,16 @@ extern "C" int kd_geglu_vjp_f32(const float* h, const float* g_y, float* g_h, in
   LaunchScope prof("geglu_vjp_f32", 0, 20.0 * n, s);
   hipLaunchKernelGGL(geglu_vjp_kernel, dim3(vjp_grid(n)), dim3(256), 0, s, h, g_y, g_h, n, d_ff);
   return check_launch("kd_geglu_vjp_f32");
+}
+
+extern "C" int kd_geglu_vjp_drop_f32(const float* h, const float* g_y, float* g_h, int rows, int d_ff, const long long* key, unsigned long long site,
+                                     unsigned threshold, float scale, void* stream) {
+  if (!h || !g_y || !g_h || !key || rows <= 0 || d_ff <= 0) return fail(KD_EINVAL, "kd_geglu_vjp_drop_f32: bad arguments");
+  const long n = (long)rows * d_ff;
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope prof("geglu_vjp_drop_f32", 0, 20.0 * n, s);
+  hipLaunchKernelGGL(geglu_vjp_drop_kernel, dim3(vjp_grid((n + 3) >> 2)), dim3(256), 0, s, h, g_y, g_h, n, d_ff, key, site, threshold, scale);
+  return check_launch("kd_geglu_vjp_drop_f32");
 }
 
 extern "C" int kd_qk_prep_vjp_f32(const float* qkv, float* g_qkv, const float* scale_h, const float* cos_t, const float* sin_t, int batch,

@@ -6,6 +6,9 @@
 //                         the staging pass, 3 bf16 MFMAs per product (hi hi, hi lo, lo hi), fp32 accumulate; exact: fp32 FMAs.  Either operand may be read through the 2x2 token-merge or the NCHW patch gather; A may be
 //                         scaled per row (RMSNorm rrms) and per (sample, column) (AdaRMSNorm scale) or be the GEGLU of [value | gate]
 //                         rows, so normalised rows are never written to memory just to be read back.
+//   kd_wgrad_drop_f32     the same with A's plain rows under a dropout mask (the FF hidden's dW_down = G^T (mask * geglu(U))): the
+//                         site's mask is first written as bits (dropout_f32.hip) and the prologue multiplies by
+//                         scale or 0 from one cached word per element.
 //   kd_row_rrms_f32       rrms[r] = rsqrt(mean(x[r]^2) + eps), the RMSNorm statistic the operand prologue and the scale gradients use
 //   kd_colsum_f32         out[s, j] (+)= sum over the rows r of segment s of a[r, j] * (b[r, j] - b2[r, j]) * rs[r]: AdaRMSNorm / RMSNorm
 //                         scale gradients, the TokenSplit fac, the attention scale's per-column terms
@@ -34,6 +37,8 @@ struct WgOperand {
   const float* row_scale;
   const float* col_scale;
   int col_stride;        // 0: one shared row of col_scale; else per sample (rows_per_sample rows each)
+  const unsigned* bits;  // A only, DROP kernels: the dropout mask of the plain [M, cols] operand (dropout_f32.hip), kept elements times drop_scale
+  float drop_scale;
 };
 
 struct WgGeom {
@@ -45,6 +50,7 @@ struct WgGeom {
 __device__ __forceinline__ float gelu_erf(float g) { return g * 0.5f * (1.0f + erff(g * 0.70710678118654752440f)); }
 
 // the operand's element (m, k); m < M and k < cols are checked by the caller
+template <bool DROP>
 __device__ __forceinline__ float wg_load(const WgOperand& o, const WgGeom& q, long m, int k) {
   float v;
   if (o.mode == WG_PLAIN) {
@@ -53,6 +59,10 @@ __device__ __forceinline__ float wg_load(const WgOperand& o, const WgGeom& q, lo
       v = r[k] * gelu_erf(r[o.cols + k]);
     } else {
       v = o.p[m * o.cols + k];
+    }
+    if (DROP) {
+      const long e = m * o.cols + k;
+      v *= ((o.bits[e >> 5] >> (e & 31)) & 1u) ? o.drop_scale : 0.0f;
     }
   } else {
     const long per = (long)q.gh * q.gw;
@@ -74,6 +84,7 @@ __device__ __forceinline__ float wg_load(const WgOperand& o, const WgGeom& q, lo
 // ---- weight gradient: 64 (n) x 64 (k) output tile per workgroup, 16 rows of m per LDS step, 4 x 4 products per lane ---------------
 constexpr int WT = 64, WR = 16;
 
+template <bool DROP>
 __global__ __launch_bounds__(256) void wgrad_partial_kernel(WgOperand G, WgOperand A, WgGeom q, long M, int N, int K, int chunk_rows,
                                                             float* __restrict__ ws) {
   __shared__ float gs[WR][WT];
@@ -94,8 +105,8 @@ __global__ __launch_bounds__(256) void wgrad_partial_kernel(WgOperand G, WgOpera
       const int r = e / WT, c = e % WT;
       const long m = m0 + r;
       const bool in_m = m < m_end;
-      gs[r][c] = (in_m && n0 + c < N) ? wg_load(G, q, m, n0 + c) : 0.f;
-      as[r][c] = (in_m && k0 + c < K) ? wg_load(A, q, m, k0 + c) : 0.f;
+      gs[r][c] = (in_m && n0 + c < N) ? wg_load<false>(G, q, m, n0 + c) : 0.f;
+      as[r][c] = (in_m && k0 + c < K) ? wg_load<DROP>(A, q, m, k0 + c) : 0.f;
     }
     __syncthreads();
 #pragma unroll
@@ -132,12 +143,13 @@ __global__ __launch_bounds__(256) void wgrad_partial_kernel(WgOperand G, WgOpera
 // the current panel's MFMAs.  MFMA 32x32x16 bf16: src0 = G^T (row n), src1 = A (column k), accumulated over m in a fixed order.
 constexpr int XR = 32, XS = 40;                    // rows of m per step; image row stride in bf16 (80 bytes)
 
+template <bool DROP>
 __device__ __forceinline__ void x3_load(const WgOperand& o, const WgGeom& q, long m0, long m_end, int col, int cols, float (&v)[8]) {
   const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const long m = m0 + g * 8 + i;
-    v[i] = (m < m_end && col + c < cols) ? wg_load(o, q, m, col + c) : 0.f;
+    v[i] = (m < m_end && col + c < cols) ? wg_load<DROP>(o, q, m, col + c) : 0.f;
   }
 }
 
@@ -153,6 +165,7 @@ __device__ __forceinline__ b16::bf16x8 x3_frag(const b16::u16* img, int row, int
   return __builtin_bit_cast(b16::bf16x8, *reinterpret_cast<const b16::u32x4*>(img + row * XS + k8));
 }
 
+template <bool DROP>
 __global__ __launch_bounds__(256) void wgrad_x3_partial_kernel(WgOperand G, WgOperand A, WgGeom q, long M, int N, int K, int chunk_rows,
                                                                float* __restrict__ ws) {
   __shared__ __attribute__((aligned(16))) b16::u16 img[4][WT * XS];     // G^T hi, G^T lo, A^T hi, A^T lo
@@ -166,15 +179,15 @@ __global__ __launch_bounds__(256) void wgrad_x3_partial_kernel(WgOperand G, WgOp
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   float gv[8], av[8];
-  x3_load(G, q, m_begin, m_end, n0, N, gv);
-  x3_load(A, q, m_begin, m_end, k0, K, av);
+  x3_load<false>(G, q, m_begin, m_end, n0, N, gv);
+  x3_load<DROP>(A, q, m_begin, m_end, k0, K, av);
   for (long m0 = m_begin; m0 < m_end; m0 += XR) {
     x3_stage(gv, img[0], img[1]);
     x3_stage(av, img[2], img[3]);
     __syncthreads();
     if (m0 + XR < m_end) {
-      x3_load(G, q, m0 + XR, m_end, n0, N, gv);
-      x3_load(A, q, m0 + XR, m_end, k0, K, av);
+      x3_load<false>(G, q, m0 + XR, m_end, n0, N, gv);
+      x3_load<DROP>(A, q, m0 + XR, m_end, k0, K, av);
     }
 #pragma unroll
     for (int ks = 0; ks < XR / 16; ++ks) {
@@ -351,37 +364,69 @@ unsigned grid_of(long n) { return (unsigned)std::min<long>((n + 255) / 256, 8192
 
 using namespace kd;
 
-extern "C" int kd_wgrad_f32(const float* G, int g_mode, const float* A, int a_mode, int a_geglu, long long M, int N, int K, int gh, int gw, int ph,
-                            int pw, int chan, const float* row_scale, const float* col_scale, int col_stride, int rows_per_sample,
-                            const float* alpha, int accumulate, int split3, int chunk_rows, int nchunk, float* ws, float* dW, void* stream) {
+namespace kd {
+int launch_dropout_bits(unsigned* bits, long long n, const long long* key, unsigned long long site, unsigned threshold, hipStream_t s);  // dropout_f32.hip
+}
+
+static int wgrad(const char* what, const float* G, int g_mode, const float* A, int a_mode, int a_geglu, long long M, int N, int K, int gh, int gw, int ph,
+                 int pw, int chan, const float* row_scale, const float* col_scale, int col_stride, int rows_per_sample, const float* alpha,
+                 int accumulate, int split3, int chunk_rows, int nchunk, float* ws, float* dW, const unsigned* bits, float drop_scale, hipStream_t s) {
   if (!G || !A || !dW || !ws || M <= 0 || N <= 0 || K <= 0 || chunk_rows <= 0 || nchunk <= 0 || nchunk > 65535)
-    return fail(KD_EINVAL, "kd_wgrad_f32: bad arguments");
-  if ((long long)chunk_rows * nchunk < M) return fail(KD_EINVAL, "kd_wgrad_f32: %d chunks of %d rows do not cover %lld rows", nchunk, chunk_rows, M);
+    return fail(KD_EINVAL, "%s: bad arguments", what);
+  if ((long long)chunk_rows * nchunk < M) return fail(KD_EINVAL, "%s: %d chunks of %d rows do not cover %lld rows", what, nchunk, chunk_rows, M);
   if (g_mode < WG_PLAIN || g_mode > WG_PATCH_NCHW || a_mode < WG_PLAIN || a_mode > WG_PATCH_NCHW || (g_mode && a_mode))
-    return fail(KD_EINVAL, "kd_wgrad_f32: bad gather modes %d / %d (one operand at most is gathered)", g_mode, a_mode);
-  if (a_geglu && a_mode != WG_PLAIN) return fail(KD_EINVAL, "kd_wgrad_f32: the GEGLU prologue reads plain rows");
+    return fail(KD_EINVAL, "%s: bad gather modes %d / %d (one operand at most is gathered)", what, g_mode, a_mode);
+  if (a_geglu && a_mode != WG_PLAIN) return fail(KD_EINVAL, "%s: the GEGLU prologue reads plain rows", what);
+  if (bits && a_mode != WG_PLAIN) return fail(KD_EINVAL, "%s: the dropout mask applies to plain A rows", what);
   if (g_mode || a_mode) {
     if (gh <= 0 || gw <= 0 || ph <= 0 || pw <= 0 || chan <= 0 || M % ((long long)gh * gw))
-      return fail(KD_EINVAL, "kd_wgrad_f32: bad gather geometry");
-    if ((g_mode ? N : K) != ph * pw * chan) return fail(KD_EINVAL, "kd_wgrad_f32: gathered operand has %d columns, expected %d", g_mode ? N : K, ph * pw * chan);
+      return fail(KD_EINVAL, "%s: bad gather geometry", what);
+    if ((g_mode ? N : K) != ph * pw * chan) return fail(KD_EINVAL, "%s: gathered operand has %d columns, expected %d", what, g_mode ? N : K, ph * pw * chan);
   }
-  if (col_scale && (rows_per_sample <= 0 || col_stride < 0)) return fail(KD_EINVAL, "kd_wgrad_f32: bad column scale layout");
-  WgOperand go{G, g_mode, N, 0, nullptr, nullptr, 0};
-  WgOperand ao{A, a_mode, K, a_geglu, row_scale, col_scale, col_stride};
+  if (col_scale && (rows_per_sample <= 0 || col_stride < 0)) return fail(KD_EINVAL, "%s: bad column scale layout", what);
+  WgOperand go{G, g_mode, N, 0, nullptr, nullptr, 0, nullptr, 0.f};
+  WgOperand ao{A, a_mode, K, a_geglu, row_scale, col_scale, col_stride, bits, drop_scale};
   WgGeom q{gh, gw, ph, pw, chan, rows_per_sample > 0 ? rows_per_sample : 1};
-  hipStream_t s = (hipStream_t)stream;
   {
-    LaunchScope prof(split3 ? "wgrad_x3_f32" : "wgrad_f32", 2.0 * (double)M * N * K, 4.0 * (double)M * (N + K), s);
+    LaunchScope prof(bits ? (split3 ? "wgrad_x3_drop_f32" : "wgrad_drop_f32") : (split3 ? "wgrad_x3_f32" : "wgrad_f32"), 2.0 * (double)M * N * K,
+                     4.0 * (double)M * (N + K), s);
     const dim3 grid((unsigned)((N + WT - 1) / WT), (unsigned)((K + WT - 1) / WT), (unsigned)nchunk);
-    if (split3) hipLaunchKernelGGL(wgrad_x3_partial_kernel, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
-    else hipLaunchKernelGGL(wgrad_partial_kernel, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
+    if (bits) {
+      if (split3) hipLaunchKernelGGL(wgrad_x3_partial_kernel<true>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
+      else hipLaunchKernelGGL(wgrad_partial_kernel<true>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
+    } else {
+      if (split3) hipLaunchKernelGGL(wgrad_x3_partial_kernel<false>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
+      else hipLaunchKernelGGL(wgrad_partial_kernel<false>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
+    }
   }
-  const int e = check_launch("kd_wgrad_f32");
+  const int e = check_launch(what);
   if (e) return e;
   const long n = (long)N * K;
   LaunchScope prof("wgrad_reduce_f32", 0, (double)n * nchunk, s);
   hipLaunchKernelGGL(chunk_reduce_kernel, dim3(grid_of(n)), dim3(256), 0, s, ws, nchunk, n, alpha, accumulate, dW);
-  return check_launch("kd_wgrad_f32 (reduce)");
+  return check_launch(what);
+}
+
+extern "C" int kd_wgrad_f32(const float* G, int g_mode, const float* A, int a_mode, int a_geglu, long long M, int N, int K, int gh, int gw, int ph,
+                            int pw, int chan, const float* row_scale, const float* col_scale, int col_stride, int rows_per_sample,
+                            const float* alpha, int accumulate, int split3, int chunk_rows, int nchunk, float* ws, float* dW, void* stream) {
+  return wgrad("kd_wgrad_f32", G, g_mode, A, a_mode, a_geglu, M, N, K, gh, gw, ph, pw, chan, row_scale, col_scale, col_stride, rows_per_sample, alpha,
+               accumulate, split3, chunk_rows, nchunk, ws, dW, nullptr, 0.f, (hipStream_t)stream);
+}
+
+extern "C" int kd_wgrad_drop_f32(const float* G, int g_mode, const float* A, int a_mode, int a_geglu, long long M, int N, int K, int gh, int gw,
+                                 int ph, int pw, int chan, const float* row_scale, const float* col_scale, int col_stride, int rows_per_sample,
+                                 const float* alpha, int accumulate, int split3, int chunk_rows, int nchunk, float* ws, float* dW,
+                                 const long long* key, unsigned long long site, unsigned threshold, float scale, unsigned* bits, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (threshold == 0)          // nothing dropped: kd_wgrad_f32's kernels and bits
+    return wgrad("kd_wgrad_drop_f32", G, g_mode, A, a_mode, a_geglu, M, N, K, gh, gw, ph, pw, chan, row_scale, col_scale, col_stride, rows_per_sample,
+                 alpha, accumulate, split3, chunk_rows, nchunk, ws, dW, nullptr, 0.f, s);
+  if (!key || !bits || a_mode != WG_PLAIN || M <= 0 || K <= 0) return fail(KD_EINVAL, "kd_wgrad_drop_f32: bad dropout arguments");
+  const int e = launch_dropout_bits(bits, M * (long long)K, key, site, threshold, s);
+  if (e) return e;
+  return wgrad("kd_wgrad_drop_f32", G, g_mode, A, a_mode, a_geglu, M, N, K, gh, gw, ph, pw, chan, row_scale, col_scale, col_stride, rows_per_sample,
+               alpha, accumulate, split3, chunk_rows, nchunk, ws, dW, bits, scale, s);
 }
 
 extern "C" int kd_row_rrms_f32(const float* x, float* rrms, long long rows, int d, float eps, void* stream) {

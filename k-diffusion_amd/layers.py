@@ -6,7 +6,9 @@ With the native HDiT inner model the three preconditioning passes (x * c_in, F *
 disappear into the patch-in / patch-out GEMMs; with a foreign inner model they run as two HIP
 elementwise kernels around it.  ``Denoiser.loss`` is the reference's training objective (layers.py:76-86) on HIP kernels: with the
 native inner model its backward fills the parameters' ``.grad`` through the model's reverse walk (models/vjp.py); a foreign inner model
-keeps its own autograd graph.  The variance and simple losses and the DCT ``scales`` weighting are out of scope.
+keeps its own autograd graph.  The model's dropout applies to the loss in training mode after ``model.enable_dropout()``; without it,
+training mode with a dropout rate raises (``model.eval()`` gives the dropout-free objective).  The variance and simple losses and the DCT
+``scales`` weighting are out of scope.
 """
 import torch
 from torch import nn

@@ -191,6 +191,35 @@ def hourglass(model):
     return steps
 
 
+DROPOUT_SITE = 1 << 62          # the bit every dropout site id carries (include/kdiff_hip.h, mask contract)
+
+
+def dropout_sites(model):
+    """The model's dropout sites with a rate > 0, in forward order: (site id, step or mapping block, kind, p).  kind "attn": the attention
+    output after the head merge, before out_proj (image_transformer_v2.py:394, :441, :474), site 2^62 | 2 i; "ff": the FF hidden after
+    GEGLU, before down_proj (:491), site 2^62 | (2 i + 1) -- i the position of the layer's ``Step`` in ``hourglass(model)``, p its level's
+    rate; "mapping": mapping block k's GEGLU output before down_proj (:564), site 2^62 | 2^32 | k, p the mapping dropout rate."""
+    out = []
+    for i, st in enumerate(hourglass(model)):
+        p = model.level_specs[st.level].dropout if st.kind == "layer" else 0.0
+        if p > 0:
+            if hasattr(st.module, "self_attn"):
+                out.append((DROPOUT_SITE | 2 * i, st, "attn", p))
+            out.append((DROPOUT_SITE | (2 * i + 1), st, "ff", p))
+    p = model.mapping_spec.dropout
+    if p > 0:
+        out += [(DROPOUT_SITE | 1 << 32 | k, k, "mapping", p) for k in range(len(model.mapping.blocks))]
+    return out
+
+
+def dropout_table(model, key):
+    """{(layer prefix, "attn" | "ff") or ("mapping", block): (key, site, p)} of one loss call's dropout (``ops.dropout``'s arguments), for
+    the primal and backward walks; {} without a key."""
+    if key is None:
+        return {}
+    return {(("mapping", where) if kind == "mapping" else (where.prefix, kind)): (key, site, p) for site, where, kind, p in dropout_sites(model)}
+
+
 def _level_pos(grids, li):
     """[h, w, 2] axial positions (y, x) of level ``li``'s tokens: cell centres of the top grid, 2x2 means below (:726, :52-54)."""
     h0, w0 = grids[0]
@@ -205,10 +234,10 @@ def _level_pos(grids, li):
 EPS = 1e-6
 
 
-def conditioning(model, sigma, aug_cond, class_cond, mapping_cond, keep=None):
+def conditioning(model, sigma, aug_cond, class_cond, mapping_cond, keep=None, drop=None):
     """The mapping network's output [B, mapping width] (image_transformer_v2.py:729-740, :552-581) on ``ops`` calls.  ``keep``: a dict
     that receives what the reverse of the chain needs (models/vjp.py): the Fourier features, the class ids, the mapping_cond rows, the
-    norms' inputs."""
+    norms' inputs.  ``drop``: a ``dropout_table`` whose mapping sites mask the blocks' GEGLU outputs (the training loss)."""
     m = model
     B = sigma.shape[0]
     dev = sigma.device
@@ -233,10 +262,13 @@ def conditioning(model, sigma, aug_cond, class_cond, mapping_cond, keep=None):
         keep.update(time_ff=ff, aug_ff=aug_ff, ids=ids, mapping_rows=mrows if mterm is not None else None, blocks=[])
     c_sum = c
     c = ops.rms_norm(c, m.mapping.in_norm.scale)
-    for blk in m.mapping.blocks:
+    for k, blk in enumerate(m.mapping.blocks):
         if keep is not None:
             keep["blocks"].append(c)
         h = ops.norm_linear(c, blk.norm.scale, blk.up_proj.weight, rows_per_sample=B, epi=nat.EPI_GEGLU)
+        dr = drop.get(("mapping", k)) if drop else None
+        if dr is not None:
+            ops.dropout(h, *dr, out=h)
         c = ops.linear(h, blk.down_proj.weight, residual=c)
     if keep is not None:
         keep.update(c_sum=c_sum, c_last=c)
@@ -755,22 +787,22 @@ class _ParamGrad(torch.autograd.Function):
     for; the rest cost nothing."""
 
     @staticmethod
-    def forward(ctx, x, model, sigma, aug_cond, class_cond, mapping_cond, *params):
+    def forward(ctx, x, model, sigma, aug_cond, class_cond, mapping_cond, key, *params):
         from . import vjp
-        out = vjp.primal(model, x, sigma, aug_cond, class_cond, mapping_cond)
+        out = vjp.primal(model, x, sigma, aug_cond, class_cond, mapping_cond, dropout=key)
         ctx.model, ctx.params = model, params
-        ctx.save_for_backward(x, sigma, aug_cond, class_cond, mapping_cond)
+        ctx.save_for_backward(x, sigma, aug_cond, class_cond, mapping_cond, key)     # the key: the recomputation draws the same masks
         return out
 
     @staticmethod
     def backward(ctx, grad):
         from . import vjp
-        x, sigma, aug_cond, class_cond, mapping_cond = ctx.saved_tensors
-        need = ctx.needs_input_grad[6:]
+        x, sigma, aug_cond, class_cond, mapping_cond, key = ctx.saved_tensors
+        need = ctx.needs_input_grad[7:]
         want = [p for p, n in zip(ctx.params, need) if n]
         _, grads = vjp.backward(ctx.model, x, sigma, grad.to(torch.float32).contiguous(), aug_cond=aug_cond, class_cond=class_cond,
-                                mapping_cond=mapping_cond, params=want)
-        return (None,) * 6 + tuple(grads.get(id(p)) if n else None for p, n in zip(ctx.params, need))
+                                mapping_cond=mapping_cond, params=want, dropout=key)
+        return (None,) * 7 + tuple(grads.get(id(p)) if n else None for p, n in zip(ctx.params, need))
 
 
 class ImageTransformerDenoiserModelV2(nn.Module):
@@ -822,6 +854,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         self._fp_dicts, self._fp_names, self._fp_objs, self._fp_tensors, self._fp_tracked, self._fp_epoch = (), (), (), (), (), 0
         self._fp_hooked = weakref.WeakSet()
         self._fp_sized, self._fp_sizes = (), ()
+        self._dropout_on, self._dropout_gen = False, None
 
     # ---- bookkeeping ---------------------------------------------------------------------------
     def _ada_norm_modules(self):
@@ -965,22 +998,52 @@ class ImageTransformerDenoiserModelV2(nn.Module):
             {"params": groups[(False, True)], "lr": base_lr * mapping_lr_scale, "weight_decay": 0.0},
         ]
 
+    def _dropout_rates(self):
+        return [(f"levels[{i}].dropout", lv.dropout) for i, lv in enumerate(self.level_specs)] + [("mapping dropout", self.mapping_spec.dropout)]
+
+    def enable_dropout(self, generator=None):
+        """Opt in to dropout in the training loss: from now on ``loss_forward`` (``Denoiser.loss``) of the model in training mode applies
+        the config's dropout rates, on masks of this project's counter-based generator (include/kdiff_hip.h, mask contract) -- not torch's
+        dropout RNG stream.  Each such call draws one int64 key from ``generator`` (a torch.Generator on the model's device; None: the
+        default generator of the input's device, so torch.manual_seed governs it), as the reference's train.py draws its seeds; the
+        backward pass regenerates the same masks from it.  While enabled, in training mode with a rate > 0, ``forward``,
+        ``forward_preconditioned`` and ``forward_jvp`` raise (they have no dropout): call model.eval() for them.  The setting is not part of
+        the state_dict.  Returns the model."""
+        bad = [f"{name} = {p}" for name, p in self._dropout_rates() if not 0.0 <= p < 1.0]
+        if bad:
+            raise ValueError(f"ImageTransformerDenoiserModelV2.enable_dropout: dropout rates must lie in [0, 1) ({', '.join(bad)})")
+        if generator is not None and not isinstance(generator, torch.Generator):
+            raise TypeError(f"enable_dropout: generator must be a torch.Generator or None (got {type(generator)})")
+        self._dropout_on, self._dropout_gen = True, generator
+        return self
+
+    def _dropout_applies(self):
+        return self.training and any(p > 0 for _, p in self._dropout_rates())
+
+    def _refuse_when_dropping(self, what):
+        if self._dropout_on and self._dropout_applies():
+            raise NotImplementedError(f"ImageTransformerDenoiserModelV2.{what}: dropout is enabled and the model is in training mode, and this "
+                                      f"pass has no dropout; call model.eval() first (dropout applies to loss_forward / Denoiser.loss only)")
+
     def loss_forward(self, x, sigma, aug_cond=None, class_cond=None, mapping_cond=None):
         """F(x, sigma) for ``Denoiser.loss``: the fp32 ``ops``-path primal, in every arithmetic mode.  Under grad mode the output carries a
         ``grad_fn`` whose backward fills the ``.grad`` of every parameter that requires grad (models/vjp.py); x, sigma and the conditioning
-        get none."""
-        if self.training:
-            drop = [f"levels[{i}].dropout = {lv.dropout}" for i, lv in enumerate(self.level_specs) if lv.dropout > 0]
-            if self.mapping_spec.dropout > 0:
-                drop.append(f"mapping dropout = {self.mapping_spec.dropout}")
-            if drop:
-                raise NotImplementedError(f"ImageTransformerDenoiserModelV2: dropout is not implemented ({', '.join(drop)}); call model.eval() "
+        get none.  In training mode with a dropout rate > 0 the config's dropout applies once ``enable_dropout`` was called (one key drawn
+        per call); without it the call raises."""
+        key = None
+        if self._dropout_applies():
+            if not self._dropout_on:
+                drop = [f"{name} = {p}" for name, p in self._dropout_rates() if p > 0]
+                raise NotImplementedError(f"ImageTransformerDenoiserModelV2: dropout in training mode needs model.enable_dropout() "
+                                          f"({', '.join(drop)}; masks from this project's counter-based generator); or call model.eval() "
                                           f"for the dropout-free objective")
+            if isinstance(x, torch.Tensor) and x.is_cuda:        # (on the CPU the primal refuses the call below)
+                key = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device=x.device, generator=self._dropout_gen)
         params = [p for p in self.parameters() if p.requires_grad] if torch.is_grad_enabled() else []
         if params:
-            return _ParamGrad.apply(x, self, sigma, aug_cond, class_cond, mapping_cond, *params)
+            return _ParamGrad.apply(x, self, sigma, aug_cond, class_cond, mapping_cond, key, *params)
         from . import vjp
-        return vjp.primal(self, x, sigma, aug_cond, class_cond, mapping_cond)
+        return vjp.primal(self, x, sigma, aug_cond, class_cond, mapping_cond, dropout=key)
 
     # ---- forward ---------------------------------------------------------------------------------
     def forward(self, x, sigma, aug_cond=None, class_cond=None, mapping_cond=None):
@@ -989,6 +1052,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         Under grad mode with ``x.requires_grad`` the output carries a ``grad_fn`` whose backward is J^T grad w.r.t. x (models/vjp.py);
         the output itself is the same bits as without grad.  Gradients go to x only: the parameters get none (their ``.grad`` stays None;
         parameter gradients go through ``Denoiser.loss``, see ``loss_forward``), and sigma or a conditioning tensor that requires grad is refused with NotImplementedError."""
+        self._refuse_when_dropping("forward")
         if _wants_input_grad(x):
             return _InputGrad.apply(x, self, sigma, aug_cond, class_cond, mapping_cond, None)
         return self._run(x, sigma, aug_cond, class_cond, mapping_cond, None)
@@ -996,6 +1060,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
     def forward_preconditioned(self, x, sigma, sigma_data, aug_cond=None, class_cond=None, mapping_cond=None):
         """Denoiser D(x, sigma) = F(x * c_in, sigma) * c_out + x * c_skip (k_diffusion/layers.py:88-90)
         with c_in folded into the patch gather and c_out / c_skip into the un-patch scatter.  Differentiable w.r.t. x as ``forward``."""
+        self._refuse_when_dropping("forward_preconditioned")
         if _wants_input_grad(x):
             return _InputGrad.apply(x, self, sigma, aug_cond, class_cond, mapping_cond, sigma_data)
         return self._run(x, sigma, aug_cond, class_cond, mapping_cond, sigma_data)
@@ -1003,6 +1068,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
     def forward_jvp(self, x, sigma, x_dot, aug_cond=None, class_cond=None, mapping_cond=None, sigma_data=None):
         """Dual pass (forward-mode JVP, models/jvp.py): (F(x, sigma), J_F x_dot) with the conditioning held fixed, or with ``sigma_data``
         the same for the Karras denoiser D(x) = F(x c_in) c_out + x c_skip.  fp32 in every arithmetic mode; no launch plan involved."""
+        self._refuse_when_dropping("forward_jvp")
         from . import jvp
         return jvp.forward_jvp(self, x, sigma, x_dot, aug_cond=aug_cond, class_cond=class_cond, mapping_cond=mapping_cond, sigma_data=sigma_data)
 

@@ -22,6 +22,10 @@ layer (its norm, qkv, q/k preparation and the attention statistics) as it gets t
     preconditioning's per-sample c_in / c_out / c_skip on ``ops.precond_vjp``; the residual adds pass the gradient through.
   - the nonlinear pieces have HIP rules of their own (csrc/vjp_f32.hip): RMSNorm / AdaRMSNorm, GEGLU, the cosine-sim scale + RoPE of q, k, and
     the three attention geometries (flash-attention-2's query and key sweeps; the neighbourhood's key sweep runs over its inverse window).
+Dropout (``dropout``: the training loss's key, ``enable_dropout``): the primal masks the attention output and the FF / mapping hidden at
+``itv2.dropout_sites`` in place; the reverse walk masks the gradient through each site again (dropout is its own transpose: ``ops.dropout``
+on g W_out^T, the GEGLU VJP's g_h inside its kernel) and the weight gradient behind it (dW_out reads the masked o, dW_down masks its GEGLU
+prologue).  No mask is stored: every kernel regenerates the bits from (key, site, element).
 Arithmetic: fp32 in every KDIFF_GEMM mode, as the dual pass (split3 GEMMs under ``split3`` / ``bf16`` / ``fp8``, exact fp32 under
 ``exact``).  No launch plan is built, read or evicted.
 """
@@ -47,9 +51,10 @@ def _split_consts(model, sp, B, device):
     return model._derive(("split", B, device), (sp.fac,), build)
 
 
-def _attn_fwd(model, st, grids, x, cond, keep):
+def _attn_fwd(model, st, grids, x, cond, keep, drop=None):
     """The self-attention sublayer (:466-476) of layer step ``st`` from its input x: returns x + out_proj(attn), and with ``keep`` what
-    its reverse needs (the AdaRMSNorm scale, the unprepared and the prepared qkv, the RoPE tables)."""
+    its reverse needs (the AdaRMSNorm scale, the unprepared and the prepared qkv, the RoPE tables, the attention output as out_proj read
+    it).  ``drop``: the loss call's ``itv2.dropout_table``."""
     spec = model.level_specs[st.level].self_attn
     sa = st.module.self_attn
     B, gh, gw, d = x.shape
@@ -61,16 +66,22 @@ def _attn_fwd(model, st, grids, x, cond, keep):
     ops.qk_prep_(prep, sa.scale.detach().contiguous(), cos_t, sin_t, nh, itv2.EPS)
     _, core, params = itv2.attn_geometry(spec, st.index)
     o = getattr(ops, core)(prep, nh, *params)
+    dr = drop.get((st.prefix, "attn")) if drop else None
+    if dr is not None:
+        ops.dropout(o, *dr, out=o)
     x = ops.linear(o, sa.out_proj.weight, residual=x)
     return x, ((s, qkv, prep, cos_t, sin_t, o) if keep else None)
 
 
-def _layer_fwd(model, st, grids, x, cond):
+def _layer_fwd(model, st, grids, x, cond, drop=None):
     if hasattr(st.module, "self_attn"):
-        x, _ = _attn_fwd(model, st, grids, x, cond, keep=False)
+        x, _ = _attn_fwd(model, st, grids, x, cond, keep=False, drop=drop)
     ff = st.module.ff
     rps = x.shape[1] * x.shape[2]
     h = ops.norm_linear(x, itv2.ada_scale(cond, ff.norm), ff.up_proj.weight, rows_per_sample=rps, epi=ops.nat.EPI_GEGLU)
+    dr = drop.get((st.prefix, "ff")) if drop else None
+    if dr is not None:
+        ops.dropout(h, *dr, out=h)
     return ops.linear(h, ff.down_proj.weight, residual=x)
 
 
@@ -106,23 +117,25 @@ class _Sink:
             self.dcond = ops.linear(ds, _wt(model, norm.linear.weight), residual=self.dcond)
 
 
-def _layer_vjp(model, st, grids, x, g, cond, sink=None):
+def _layer_vjp(model, st, grids, x, g, cond, sink=None, drop=None):
     """Gradient w.r.t. the input x of layer step ``st`` from the gradient g on its output; the layer's insides are recomputed from x.  With
-    ``sink`` the layer's parameter gradients go there too."""
+    ``sink`` the layer's parameter gradients go there too.  ``drop``: the loss call's ``itv2.dropout_table`` -- each mask applies again to
+    the gradient through its site (dropout is its own transpose) and to the operand of the weight gradient behind it."""
     B, gh, gw, d = x.shape
     rps = gh * gw
     has_attn = hasattr(st.module, "self_attn")
     if has_attn:
-        xf, (s_a, qkv, prep, cos_t, sin_t, o) = _attn_fwd(model, st, grids, x, cond, keep=True)
+        xf, (s_a, qkv, prep, cos_t, sin_t, o) = _attn_fwd(model, st, grids, x, cond, keep=True, drop=drop)
     else:
         xf = x
     ff = st.module.ff
+    d_ff = drop.get((st.prefix, "ff")) if drop else None
     s_f = itv2.ada_scale(cond, ff.norm)
     u = ops.norm_linear(xf, s_f, ff.up_proj.weight, rows_per_sample=rps)           # [value | gate] rows (linear_geglu, :89-95)
-    gu = ops.geglu_vjp(u, ops.linear(g, _wt(model, ff.down_proj.weight)))
+    gu = ops.geglu_vjp(u, ops.linear(g, _wt(model, ff.down_proj.weight)), dropout=d_ff)      # g_h = mask (g W_down^T) into the GEGLU VJP
     gy = ops.linear(gu, _wt(model, ff.up_proj.weight))
     if sink is not None:
-        sink.put(ff.down_proj.weight, lambda: ops.wgrad(g, u, geglu=True))
+        sink.put(ff.down_proj.weight, lambda: ops.wgrad(g, u, geglu=True, dropout=d_ff))      # g^T (mask geglu(u))
         r = ops.row_rrms(xf, itv2.EPS) if sink.wants(ff.up_proj.weight, ff.norm.linear.weight) or sink.chain else None
         sink.put(ff.up_proj.weight, lambda: ops.wgrad(gu, xf, row_scale=r, col_scale=s_f, rows_per_sample=rps))
         sink.ada(model, ff.norm, gy, xf, r, rps)
@@ -133,8 +146,11 @@ def _layer_vjp(model, st, grids, x, g, cond, sink=None):
     spec = model.level_specs[st.level].self_attn
     nh = d // spec.d_head
     go = ops.linear(g, _wt(model, sa.out_proj.weight))
+    d_attn = drop.get((st.prefix, "attn")) if drop else None
+    if d_attn is not None:
+        ops.dropout(go, *d_attn, out=go)
     if sink is not None:
-        sink.put(sa.out_proj.weight, lambda: ops.wgrad(g, o))
+        sink.put(sa.out_proj.weight, lambda: ops.wgrad(g, o))                           # o: already masked by the recomputation
     _, core, params = itv2.attn_geometry(spec, st.index)
     gq = getattr(ops, core + "_vjp")(prep, go, nh, *params)
     scale = sa.scale.detach().contiguous()
@@ -149,9 +165,10 @@ def _layer_vjp(model, st, grids, x, g, cond, sink=None):
     return ops.rms_norm_vjp(x, gy, s_a, rows_per_sample=rps, add=g)
 
 
-def _mapping_vjp(m, keep, sink):
+def _mapping_vjp(m, keep, sink, drop=None):
     """The conditioning chain in reverse (image_transformer_v2.py:729-740, :552-581) from d cond on its output: the mapping network's
-    norms and blocks, then the projections of the Fourier features and mapping_cond, and the class embedding."""
+    norms and blocks (their GEGLU outputs under ``drop``'s mapping sites), then the projections of the Fourier features and mapping_cond,
+    and the class embedding."""
     mp = m.mapping
     dc = sink.dcond
     B = dc.shape[0]
@@ -159,13 +176,14 @@ def _mapping_vjp(m, keep, sink):
     if sink.wants(mp.out_norm.scale):
         sink.put(mp.out_norm.scale, lambda: ops.colsum(dc, c, row_scale=ops.row_rrms(c, itv2.EPS)).reshape(-1))
     dc = ops.rms_norm_vjp(c, dc, mp.out_norm.scale.detach().contiguous())
-    for blk, c in reversed(list(zip(mp.blocks, keep["blocks"]))):
+    for k, blk, c in reversed(list(zip(range(len(mp.blocks)), mp.blocks, keep["blocks"]))):
+        dk = drop.get(("mapping", k)) if drop else None
         nscale = blk.norm.scale.detach().contiguous()
         u = ops.norm_linear(c, blk.norm.scale, blk.up_proj.weight, rows_per_sample=B)
-        gu = ops.geglu_vjp(u, ops.linear(dc, _wt(m, blk.down_proj.weight)))
+        gu = ops.geglu_vjp(u, ops.linear(dc, _wt(m, blk.down_proj.weight)), dropout=dk)
         gy = ops.linear(gu, _wt(m, blk.up_proj.weight))
         r = ops.row_rrms(c, itv2.EPS)
-        sink.put(blk.down_proj.weight, lambda: ops.wgrad(dc, u, geglu=True))
+        sink.put(blk.down_proj.weight, lambda: ops.wgrad(dc, u, geglu=True, dropout=dk))
         sink.put(blk.up_proj.weight, lambda: ops.wgrad(gu, c, row_scale=r, col_scale=nscale))
         sink.put(blk.norm.scale, lambda: ops.colsum(gy, c, row_scale=r).reshape(-1))
         dc = ops.rms_norm_vjp(c, gy, nscale, add=dc)
@@ -180,7 +198,7 @@ def _mapping_vjp(m, keep, sink):
         sink.put(m.class_emb.weight, lambda: ops.class_emb_grad(dc, keep["ids"], m.class_emb.weight.shape[0]))
 
 
-def _primal(m, x, grids, cond, pre, prec):
+def _primal(m, x, grids, cond, pre, prec, drop=None):
     """The fp32 ``ops``-path primal up to the output norm (image_transformer_v2.py:721-758): (h, every layer's input, every merge's input,
     every split's input)."""
     acts, skips, merge_in, split_in = [], [], [], []
@@ -188,7 +206,7 @@ def _primal(m, x, grids, cond, pre, prec):
     for st in itv2.hourglass(m):
         if st.kind == "layer":
             acts.append(h)
-            h = _layer_fwd(m, st, grids, h, cond)
+            h = _layer_fwd(m, st, grids, h, cond, drop)
         elif st.kind == "merge":
             skips.append(h)
             merge_in.append(h)
@@ -201,23 +219,26 @@ def _primal(m, x, grids, cond, pre, prec):
 
 
 @torch.no_grad()
-def primal(model, x, sigma, aug_cond=None, class_cond=None, mapping_cond=None):
-    """F(x, sigma) of the inner model on the fp32 ``ops`` path (what ``backward`` recomputes; no launch plan is built, read or evicted)."""
+def primal(model, x, sigma, aug_cond=None, class_cond=None, mapping_cond=None, dropout=None):
+    """F(x, sigma) of the inner model on the fp32 ``ops`` path (what ``backward`` recomputes; no launch plan is built, read or evicted).
+    ``dropout``: the loss call's key (a one-element int64 device tensor) -- the model's dropout sites (``itv2.dropout_sites``) mask their
+    tensors; None: no dropout."""
     m = model
     x, _ = m._check_input(x, class_cond, mapping_cond, "the training loss")
     grids = m._token_grids(x)
     B = x.shape[0]
     sigma = sigma.to(device=x.device, dtype=torch.float32).reshape(-1).expand(B).contiguous()
-    cond = itv2.conditioning(m, sigma, aug_cond, class_cond, mapping_cond)
-    h, *_ = _primal(m, x, grids, cond, {}, ops._prec_of(x))
+    drop = itv2.dropout_table(m, dropout)
+    cond = itv2.conditioning(m, sigma, aug_cond, class_cond, mapping_cond, drop=drop)
+    h, *_ = _primal(m, x, grids, cond, {}, ops._prec_of(x), drop)
     return ops.patch_out(h, m.out_norm.scale.detach().contiguous(), m.patch_out.proj.weight, m.patch_size, m.out_channels)
 
 
 @torch.no_grad()
-def backward(model, x, sigma, grad_out, aug_cond=None, class_cond=None, mapping_cond=None, sigma_data=None, params=None):
+def backward(model, x, sigma, grad_out, aug_cond=None, class_cond=None, mapping_cond=None, sigma_data=None, params=None, dropout=None):
     """J^T grad_out w.r.t. x of the inner model F (``sigma_data`` None) or of the Karras denoiser around it (``sigma_data`` given).  With
     ``params`` (a list of the model's parameters; inner model only): (J^T grad_out, {id(p): gradient of p}) -- the input gradient is the
-    same bits as without."""
+    same bits as without.  ``dropout``: the key ``primal`` ran with (the same masks are regenerated), or None."""
     m = model
     x, grad_out = m._check_input(x, class_cond, mapping_cond, "the backward pass",
                                  (grad_out, m.out_channels, "gradient shape {} != output shape {}"))
@@ -229,12 +250,13 @@ def backward(model, x, sigma, grad_out, aug_cond=None, class_cond=None, mapping_
     prec = ops._prec_of(x)
     pre = dict(sigma=sigma, sigma_data=float(sigma_data)) if sigma_data is not None else {}
     keep = {} if params is not None else None
-    cond = itv2.conditioning(m, sigma, aug_cond, class_cond, mapping_cond, keep=keep)
+    drop = itv2.dropout_table(m, dropout)
+    cond = itv2.conditioning(m, sigma, aug_cond, class_cond, mapping_cond, keep=keep, drop=drop)
     sink = _Sink(m, params, cond) if params is not None else None
     steps = itv2.hourglass(m)
 
     # primal, keeping every layer's input (image_transformer_v2.py:721-762)
-    h, acts, merge_in, split_in = _primal(m, x, grids, cond, pre, prec)
+    h, acts, merge_in, split_in = _primal(m, x, grids, cond, pre, prec, drop)
 
     # reverse walk
     g_img = ops.precond_vjp(grad_out, ops.nat.PC_OUT, sigma, sigma_data) if sigma_data is not None else grad_out
@@ -252,7 +274,7 @@ def backward(model, x, sigma, grad_out, aug_cond=None, class_cond=None, mapping_
     g_skips = []
     for st in reversed(steps):
         if st.kind == "layer":
-            g = _layer_vjp(m, st, grids, acts.pop(), g, cond, sink)
+            g = _layer_vjp(m, st, grids, acts.pop(), g, cond, sink, drop)
         elif st.kind == "split":
             sp = m.splits[st.level]
             xs = split_in.pop()
@@ -282,7 +304,7 @@ def backward(model, x, sigma, grad_out, aug_cond=None, class_cond=None, mapping_
         ph, pw = m.patch_size
         sink.put(m.patch_in.proj.weight, lambda: ops.wgrad(g, x, gather=("a", ops.nat.WG_PATCH_NCHW), gather_geom=(gh, gw, ph, pw, m.in_channels)))
         if sink.chain:
-            _mapping_vjp(m, keep, sink)
+            _mapping_vjp(m, keep, sink, drop)
     g = ops.patch_out(g, None, _wt(m, m.patch_in.proj.weight), m.patch_size, m.in_channels)   # patch-in^T: the un-patch
     if sigma_data is not None:
         g = ops.precond_vjp(g, ops.nat.PC_IN, sigma, sigma_data, h=grad_out, h_coef=ops.nat.PC_SKIP)

@@ -675,15 +675,20 @@ def rms_norm_vjp(x, g_y, scale, rows_per_sample=None, eps=1e-6, add=None, out=No
     return out
 
 
-def geglu_vjp(h, g_y):
+def geglu_vjp(h, g_y, dropout=None):
     """Gradient of linear_geglu's gate (:89-95): the projection h [..., 2 d_ff] (value first) and the gradient on its output [..., d_ff]
-    -> the gradient on h [..., 2 d_ff]."""
+    -> the gradient on h [..., 2 d_ff].  ``dropout`` = (key, site, p): the output went through ``dropout`` at that site, so g_y is masked
+    first, inside the kernel (the same bits as ``dropout`` on g_y, then this)."""
     d_ff = h.shape[-1] // 2
     rows = h.numel() // h.shape[-1]
     if _chk(g_y, "g_y").numel() != rows * d_ff:
         raise ValueError(f"geglu_vjp: g_y has {g_y.numel()} elements, expected {rows * d_ff}")
     out = torch.empty_like(h)
-    nat.check(nat.lib().kd_geglu_vjp_f32(_p(_chk(h, "h")), _p(g_y), _p(out), rows, d_ff, _stream()), "kd_geglu_vjp_f32")
+    drop = _dropout_args(dropout)
+    if drop is None:
+        nat.check(nat.lib().kd_geglu_vjp_f32(_p(_chk(h, "h")), _p(g_y), _p(out), rows, d_ff, _stream()), "kd_geglu_vjp_f32")
+    else:
+        nat.check(nat.lib().kd_geglu_vjp_drop_f32(_p(_chk(h, "h")), _p(g_y), _p(out), rows, d_ff, *drop, _stream()), "kd_geglu_vjp_drop_f32")
     return out
 
 
@@ -758,6 +763,43 @@ def precond_vjp(g, g_coef, sigma, sigma_data, h=None, h_coef=nat.PC_ONE, out=Non
 WGRAD_BLOCKS = 1024          # workgroups a weight-gradient GEMM aims at (row chunks x output tiles); the chunking is a function of the shape
 
 
+DROPOUT_SITE = 1 << 62                # include/kdiff_hip.h: every dropout site id has this bit; the Brownian / randn counters never do
+
+
+def _dropout_args(dropout):
+    """(key pointer, site, threshold, scale) of the kernels' mask contract for ``dropout`` = (key, site, p), or None when nothing is
+    dropped (None or p == 0).  key: a one-element int64 device tensor; p in [0, 1)."""
+    if dropout is None:
+        return None
+    key, site, p = dropout
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout rate {p} outside [0, 1)")
+    if p == 0.0:
+        return None
+    if _chk(key, "key", torch.int64).numel() != 1:
+        raise ValueError(f"dropout: the key is one int64 (got {key.numel()} elements)")
+    if not 0 <= int(site) < 1 << 64:
+        raise ValueError(f"dropout: site {site} is not a 64-bit unsigned id")
+    return _p(key), int(site), math.floor(p * 2.0 ** 32), 1.0 / (1.0 - p)
+
+
+def dropout(x, key, site, p, out=None):
+    """The training loss's dropout at one site (include/kdiff_hip.h, mask contract): out = x * m, m = scale or 0 from the counter-based
+    mask of (key, site, element).  ``out`` may be ``x`` (in place).  p == 0 launches nothing (returns x, or out holding a copy of x)."""
+    if out is not None and _chk(out, "out").shape != _chk(x, "x").shape:
+        raise ValueError(f"dropout: out shape {tuple(out.shape)} != {tuple(x.shape)}")
+    drop = _dropout_args((key, site, p))
+    if drop is None:
+        if out is None or out is x:
+            return x
+        return out.copy_(x)
+    out = torch.empty_like(_chk(x, "x")) if out is None else out
+    if x.numel():
+        nat.check(nat.lib().kd_dropout_f32(_p(x), _p(out), x.numel(), *drop, _stream()), "kd_dropout_f32")
+    return out
+
+
 def wgrad_chunks(M, N, K):
     """(chunk_rows, nchunk) of ``kd_wgrad_f32``: a fixed function of the shape, so that the order of the sum is too."""
     tiles = -(-N // 64) * -(-K // 64)
@@ -768,14 +810,16 @@ def wgrad_chunks(M, N, K):
 
 
 def wgrad(G, A, *, N=None, K=None, out=None, accumulate=False, gather=None, gather_geom=None, geglu=False, row_scale=None, col_scale=None,
-          rows_per_sample=None, alpha=None, precision=None):
+          rows_per_sample=None, alpha=None, precision=None, dropout=None):
     """Weight gradient of a projection: dW[N, K] (+)= alpha * sum_m G[m, n] * A[m, k] over the stored rows m of G and A.
 
     ``gather``: None, ("g" | "a", nat.WG_MERGE2x2 | nat.WG_PATCH_NCHW) -- that operand is read through the 2x2 token merge of a fine NHWC
     grid or the patch gather of an NCHW image; ``gather_geom`` = (gh, gw, ph, pw, chan) of its coarse rows.  A's prologue: ``geglu`` (A
     holds [value | gate] rows; the operand is value * gelu(gate)), ``row_scale`` [M] and ``col_scale`` ([K] shared or [B, K] per sample of
     ``rows_per_sample`` rows).  ``alpha``: a one-element device tensor multiplying the result.  Arithmetic: the backward pass's rule --
-    split3 on the matrix cores under KDIFF_GEMM split3 / bf16 / fp8, fp32 FMAs under exact (``precision`` overrides)."""
+    split3 on the matrix cores under KDIFF_GEMM split3 / bf16 / fp8, fp32 FMAs under exact (``precision`` overrides).  ``dropout`` =
+    (key, site, p): A's plain [M, K] operand (after the GEGLU prologue) is masked as ``dropout`` masks that site; p == 0 is the plain
+    call."""
     g_mode = a_mode = nat.WG_PLAIN
     gh = gw = ph = pw = chan = 0
     if gather is not None:
@@ -822,9 +866,17 @@ def wgrad(G, A, *, N=None, K=None, out=None, accumulate=False, gather=None, gath
     split3 = (_prec_of(G) if precision is None else precision) != nat.PREC_EXACT
     chunk, nchunk = wgrad_chunks(M, N, K)
     ws = torch.empty(nchunk * N * K, device=G.device, dtype=torch.float32)
-    nat.check(nat.lib().kd_wgrad_f32(_p(_chk(G, "G")), g_mode, _p(_chk(A, "A")), a_mode, int(bool(geglu)), M, N, K, gh, gw, ph, pw, chan,
-                                     _p(row_scale), _p(col_scale), col_stride, int(rows_per_sample or 1), _p(None if alpha is None else _chk(alpha, "alpha")),
-                                     int(bool(accumulate)), int(split3), chunk, nchunk, _p(ws), _p(out), _stream()), "kd_wgrad_f32")
+    args = (_p(_chk(G, "G")), g_mode, _p(_chk(A, "A")), a_mode, int(bool(geglu)), M, N, K, gh, gw, ph, pw, chan, _p(row_scale), _p(col_scale),
+            col_stride, int(rows_per_sample or 1), _p(None if alpha is None else _chk(alpha, "alpha")), int(bool(accumulate)), int(split3), chunk,
+            nchunk, _p(ws), _p(out))
+    drop = _dropout_args(dropout)
+    if drop is None:
+        nat.check(nat.lib().kd_wgrad_f32(*args, _stream()), "kd_wgrad_f32")
+    else:
+        if a_mode != nat.WG_PLAIN:
+            raise ValueError("wgrad: the dropout mask applies to plain A rows")
+        bits = torch.empty((M * K + 31) // 32, device=G.device, dtype=torch.int32)
+        nat.check(nat.lib().kd_wgrad_drop_f32(*args, *drop, _p(bits), _stream()), "kd_wgrad_drop_f32")
     return out
 
 
