@@ -49,6 +49,7 @@ const char* kd_last_error(void);
  *                  kernel, 2 = every eligible shape) "x3r_lw" (1; 0 = staging requests inside the compute waves' K loop instead of loader waves)
  *                  "x3r_split" (1; 0 = TokenSplit + lerp on the round-1 tile kernel) "ffn_x3" (1; 0 = kd_ffn_f32_supported answers no) "ffn_x3_half" (1; 0 = one workgroup per CU
  *                  at K = 128) "attn_x3" (1; 0 = the round-1 attention cores also for split-stored operands)
+ *                  "attn_ffn_x3" (1; 0 = kd_attn_ffn_f32_supported answers no)
  *                  "x3_min_rows" (512) "x3r_min_rows" (128) "ffn_x3_min_panels_256" (7/8 of the CUs): row counts from which the throughput
  *                  kernels are chosen / advised
  *                  "x3s_max_rows" (4096; 0 = off) the few-rows latency form of the KD_PREC_SPLIT3 projections (gemm_x3s.hip: 32 rows x one
@@ -182,6 +183,13 @@ int kd_ffn_bf16(const KdFfn* desc, void* stream);
  * (option "ffn_x3_half" = 0: the one-workgroup form; same results). */
 int kd_ffn_f32_supported(int M, int K, int d_ff);
 int kd_ffn_f32(const KdFfn* desc, void* stream);
+/* Neighbourhood attention core + out projection + residual + feed-forward block in ONE launch (KD_PREC_SPLIT3; csrc/attn_ffn_x3.hip):
+ * what kd_attn_na2d_f32(qkv, att, ..., prep = 2) followed by kd_ffn_f32(desc with attn = att, Wp_out) computes, bit for bit, without the
+ * attention rows' round trip through HBM (desc->attn is not read).  Kernel size 7, 2 heads of 64 (K == 128), H % 8 == 0, W % 16 == 0,
+ * desc->M == batch H W, desc->rows_per_sample == H W; kd_attn_ffn_f32_supported says whether a shape is taken (and kd_ffn_f32_supported's
+ * answer for the block; option "attn_ffn_x3" = 0 answers no). */
+int kd_attn_ffn_f32_supported(int batch, int H, int W, int nh, int ks, int K, int d_ff);
+int kd_attn_ffn_f32(const float* qkv, const KdFfn* desc, int batch, int H, int W, int nh, int ks, void* stream);
 
 /* One-off packing of a weight for KD_PREC_SPLIT3 (weights are static during sampling): W [N or 2N (geglu == 1), K]
  * fp32 -> `out`, kd_packed_weight_bytes(N, K, geglu) bytes: [n-tile][k-step][hi|lo][128 rows][32 bf16] in the
@@ -575,11 +583,12 @@ int kd_prof_clock_buffer(void* dev_ptr);
  *   KD_OP_ATTN_WINDOW_F32 : p as above; i = batch, H, W, nh, ws, shift, prep, precision        KD_OP_ATTN_NA2D_F32 : i = batch, H, W, nh, ks, prep, precision
  *   KD_OP_ATTN_GLOBAL_BF16 : p = qkv, out; i = batch, T, nh      KD_OP_ATTN_WINDOW_BF16 : i = batch, H, W, nh, ws, shift      KD_OP_ATTN_NA2D_BF16 : i = batch, H, W, nh, ks
  *   KD_OP_NORM_SPLIT_F32 : p = x, scale, hi, lo; i = scale_stride, rows_per_sample, M, K; f = eps
- *   KD_OP_ATTN_BLOCK_BF16 / KD_OP_PROJ_BLOCK_BF16 / KD_OP_GEMM_MX8 : p[0] = const KdGemm* */
+ *   KD_OP_ATTN_BLOCK_BF16 / KD_OP_PROJ_BLOCK_BF16 / KD_OP_GEMM_MX8 : p[0] = const KdGemm*
+ *   KD_OP_ATTN_FFN_F32 : p = qkv, const KdFfn*; i = batch, H, W, nh, ks */
 enum { KD_OP_GEMM_F32 = 0, KD_OP_GEMM_BF16 = 1, KD_OP_FFN_F32 = 2, KD_OP_FFN_BF16 = 3,
        KD_OP_ATTN_GLOBAL_F32 = 4, KD_OP_ATTN_WINDOW_F32 = 5, KD_OP_ATTN_NA2D_F32 = 6,
        KD_OP_ATTN_GLOBAL_BF16 = 7, KD_OP_ATTN_WINDOW_BF16 = 8, KD_OP_ATTN_NA2D_BF16 = 9, KD_OP_NORM_SPLIT_F32 = 10,
-       KD_OP_ATTN_BLOCK_BF16 = 11, KD_OP_PROJ_BLOCK_BF16 = 12, KD_OP_GEMM_MX8 = 13 };
+       KD_OP_ATTN_BLOCK_BF16 = 11, KD_OP_PROJ_BLOCK_BF16 = 12, KD_OP_GEMM_MX8 = 13, KD_OP_ATTN_FFN_F32 = 14 };
 typedef struct {
   int op;             /* KD_OP_* */
   float f;

@@ -99,6 +99,8 @@ SIGNATURES = {
     "kd_ffn_bf16": [_vp, _vp],
     "kd_ffn_f32_supported": [_i, _i, _i],
     "kd_ffn_f32": [_vp, _vp],
+    "kd_attn_ffn_f32_supported": [_i, _i, _i, _i, _i, _i, _i],
+    "kd_attn_ffn_f32": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
     "kd_attn_global_bf16": [_vp, _vp, _i, _i, _i, _vp],
     "kd_attn_window_bf16": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "kd_attn_na2d_bf16": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -188,7 +190,7 @@ SIGNATURES = {
 # entry points a kd_run_list entry can name (include/kdiff_hip.h: KD_OP_*)
 RUN_LIST_OPS = {"kd_gemm_f32": 0, "kd_gemm_bf16": 1, "kd_ffn_f32": 2, "kd_ffn_bf16": 3, "kd_attn_global_f32": 4, "kd_attn_window_f32": 5,
                 "kd_attn_na2d_f32": 6, "kd_attn_global_bf16": 7, "kd_attn_window_bf16": 8, "kd_attn_na2d_bf16": 9, "kd_norm_split_f32": 10,
-                "kd_attn_block_bf16": 11, "kd_proj_block_bf16": 12, "kd_gemm_mx8": 13}
+                "kd_attn_block_bf16": 11, "kd_proj_block_bf16": 12, "kd_gemm_mx8": 13, "kd_attn_ffn_f32": 14}
 
 
 def encode_call(call, name, args):

@@ -6,6 +6,10 @@ sound while the COMPILER keeps nothing of its own there and spills nothing (a sp
 counted vmcnt waits).  This script compiles the file to assembly and fails the build if, in any gemm_x3_astat_kernel<32, *>, an AccVGPR
 or a scratch access appears outside an ;;#ASMSTART / ;;#ASMEND block (also every ffn_x3_kernel of ffn_x3.hip).
 
+attn_ffn_x3.hip's attn_ffn_x3h_kernel runs the attention core in front of the feed-forward block: there the compiler may use AccVGPRs
+of its own until the `kd_phase_b` marker (nothing of the block is live yet) and is held to the rule from the marker on; scratch is
+refused everywhere, and the kernel must fit two workgroups per CU: at most 256 registers per lane (ArchVGPRs + AccVGPRs).
+
     python check_x3_agpr.py gemm_x3.hip
 """
 import os
@@ -31,9 +35,17 @@ def main(src):
         body = txt[st:en].split(".end_amdhsa_kernel")[0]
         if not re.search(r"\.vgpr_spill_count:\s*0", txt[st:]) and "vgpr_spill_count" in txt[st:en]:
             raise SystemExit(f"check_x3_agpr: {name}: spills")
-        inasm, n_mfma = False, 0
+        fused = "attn_ffn_x3h" in name
+        if fused:
+            if "kd_phase_b" not in body:
+                raise SystemExit(f"check_x3_agpr: {name}: no kd_phase_b marker")
+            m = re.search(r"\.amdhsa_next_free_vgpr\s+(\d+)", txt[st:])
+            if not m or int(m.group(1)) > 256:
+                raise SystemExit(f"check_x3_agpr: {name}: {m.group(1) if m else '?'} registers per lane: no two workgroups per CU")
+        inasm, n_mfma, held = False, 0, not fused
         for line in body.split("\n"):
             t = line.strip()
+            held |= "kd_phase_b" in t
             if ";;#ASMSTART" in t:
                 inasm = True
             elif ";;#ASMEND" in t:
@@ -42,7 +54,7 @@ def main(src):
                 continue
             elif inasm:
                 n_mfma += "v_mfma" in t
-            elif re.search(r"\ba\[?\d", t) or "accvgpr" in t or "scratch_" in t:
+            elif "scratch_" in t or (held and (re.search(r"\ba\[?\d", t) or "accvgpr" in t)):
                 raise SystemExit(f"check_x3_agpr: {name}: the compiler touches an AccVGPR / scratch outside the kernel's asm: {t}")
         if n_mfma == 0:
             raise SystemExit(f"check_x3_agpr: {name}: no asm MFMA found (did the kernel change?)")

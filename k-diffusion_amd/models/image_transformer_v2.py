@@ -47,7 +47,7 @@ SCHEDULE_CHAINS_KEPT = 2      # conditioning workspaces kept per plan, by schedu
 DERIVED_KEPT = 1024  # weight-derived tensors kept per model (_derive: transposed weights, RoPE tables, ...): all dropped beyond that
 MAX_PLANS = 16     # cached launch plans (one per batch / size / conditioning kinds / device / arithmetic mode / switches) per model: least recently used beyond that
 # environment switches of the kernel routing (name, default): read in _plan_for, part of the plan key, passed to route_layer
-PLAN_SWITCHES = (("KDIFF_ATTN_BLOCK", "1"), ("KDIFF_PROJ_BLOCK", "1"), ("KDIFF_FFN_OUT", "all"), ("KDIFF_RUN_LIST", "1"))
+PLAN_SWITCHES = (("KDIFF_ATTN_BLOCK", "1"), ("KDIFF_PROJ_BLOCK", "1"), ("KDIFF_FFN_OUT", "all"), ("KDIFF_RUN_LIST", "1"), ("KDIFF_ATTN_FFN", "1"))
 CLASS_IDS_KEPT = 4            # range-checked class_cond tensors remembered per plan (cond / uncond pairs of a guidance wrapper)
 
 
@@ -288,13 +288,15 @@ class LayerRoute:
     """The kernels of one layer (``route_layer``).  qkv: "attn_block" (projection + attention core in one launch), "proj_block",
     "mx8", "split" (kd_norm_split_f32 planes, then the GEMM), "plain" or None (no attention); core: the attention core's entry point
     (None: none, or inside the attention block); fuse_out: the out projection runs inside the FF kernel; ff: "kd_ffn_f32" /
-    "kd_ffn_bf16" (one kernel) or "pair", whose up projection is routed like qkv (``up``) and whose down projection may be fp8."""
+    "kd_ffn_bf16" (one kernel) or "pair", whose up projection is routed like qkv (``up``) and whose down projection may be fp8;
+    fuse_core: ``core`` and ``ff`` (with its fused out projection) run as ONE launch, kd_attn_ffn_f32."""
     qkv: Optional[str]
     core: Optional[str]
     fuse_out: bool
     ff: str
     up: Optional[str] = None
     down_mx8: bool = False
+    fuse_core: bool = False
 
 
 def _prepass(mode, width):
@@ -310,10 +312,12 @@ def _mx8_ok(lib, mode, M, N, K, epi):
     return mode == nat.PREC_FP8 and M >= lib.kd_get_option(b"mx8_min_rows", 4096) and bool(lib.kd_gemm_mx8_supported(M, N, K, epi, 1))
 
 
-def route_layer(lib, mode, B, T, rps, d, d_ff, nh, attn, switches):
+def route_layer(lib, mode, B, T, rps, d, d_ff, nh, attn, switches, grid=None, kernel_size=None):
     """The kernels of a layer of width ``d`` over ``T`` = B x ``rps`` tokens in arithmetic mode ``mode`` (nat.PREC_*, PREC_FP8 included):
     ``attn`` is "global" / "neighborhood" / "shifted-window", or None for a layer without attention (``nh`` heads); ``switches`` maps
-    the names of PLAN_SWITCHES to the plan's values.  Asks only host-side predicates of the library (``lib``): no tensors, no device."""
+    the names of PLAN_SWITCHES to the plan's values; ``grid``: the level's token grid and ``kernel_size``: the neighbourhood's, where the
+    caller knows them (without them no layer takes a form that depends on them).  Asks only host-side predicates of the library (``lib``):
+    no tensors, no device."""
     bf = mode in (nat.PREC_BF16, nat.PREC_FP8)
     proj_block = bf and switches["KDIFF_PROJ_BLOCK"] != "0"
     ffn_x3 = mode == nat.PREC_SPLIT3 and bool(lib.kd_ffn_f32_supported(T, d, d_ff))      # (library option ffn_x3)
@@ -355,7 +359,13 @@ def route_layer(lib, mode, B, T, rps, d, d_ff, nh, attn, switches):
     if ffn_x3 or ffn_bf:
         # the whole FeedForwardBlock (:487-493) in one kernel (csrc/ffn_x3.hip, csrc/ffn_bf16.hip): the d_ff-wide hidden activation stays
         # on the chip
-        return LayerRoute(qkv, core, fuse_out, "kd_ffn_f32" if ffn_x3 else "kd_ffn_bf16")
+        # split3, neighbourhood core followed by the width-128 FF kernel with its fused out projection (level 0 of the 256 x 256 configs):
+        # both in ONE launch on the core's query tiles (csrc/attn_ffn_x3.hip: the attention rows never cross HBM; same bits).
+        # KDIFF_ATTN_FFN=0: the two launches
+        fuse_core = bool(ffn_x3 and fuse_out and attn == "neighborhood" and core == "kd_attn_na2d_f32" and grid is not None
+                         and kernel_size is not None and switches.get("KDIFF_ATTN_FFN", "1") != "0"
+                         and lib.kd_attn_ffn_f32_supported(B, grid[0], grid[1], nh, kernel_size, d, d_ff))
+        return LayerRoute(qkv, core, fuse_out, "kd_ffn_f32" if ffn_x3 else "kd_ffn_bf16", fuse_core=fuse_core)
     if _prepass(mode, d) and d_ff % 64 == 0:
         return LayerRoute(qkv, core, fuse_out, "pair", "split")
     # fp8 mode: the hidden activation leaves the GEGLU epilogue as e4m3 rows + one power-of-two scale per (row, 32 features) -- in
@@ -645,7 +655,8 @@ class _Plan:
         spec = lv.self_attn
         nh = d // spec.d_head if hasattr(mod, "self_attn") else 0
         kind, core, params = attn_geometry(spec, index) if nh else (None, None, ())
-        r = route_layer(self.lib, self.mode, self.B, T, rps, d, d_ff, nh, kind, self.switches)
+        r = route_layer(self.lib, self.mode, self.B, T, rps, d, d_ff, nh, kind, self.switches, grid=(gh, gw),
+                        kernel_size=params[0] if kind == "neighborhood" else None)
         split3 = self.precision == nat.PREC_SPLIT3
         if nh:
             sa, norm = mod.self_attn, prefix + "self_attn.norm"
@@ -663,7 +674,7 @@ class _Plan:
                 self._gemm(L, prefix + "qkv_proj(block)", x, sa.qkv_proj.weight, self.qkv, T, 3 * d, d, table=norm, entry="kd_proj_block_bf16", **q)
             else:
                 self._gemm(L, prefix + "qkv_proj", x, sa.qkv_proj.weight, self.qkv, T, 3 * d, d, table=norm, mx8=r.qkv == "mx8", **q)
-            if r.core is not None:
+            if r.core is not None and not r.fuse_core:
                 geo = ((rps, nh) if kind == "global" else (gh, gw, nh)) + params
                 prep = () if r.core.endswith("_bf16") else (2 if split3 else 0, None, None, None, C.c_float(1e-6), self.precision)
                 L.append(_Launch(r.core, (_ptr(self.qkv), _ptr(self.att), self.B, *geo, *prep), prefix + core))
@@ -676,7 +687,10 @@ class _Plan:
             fd = ops.ffn(x, None, w_up, w_down, out=x, scale_stride=self.scale_width, rows_per_sample=rps, attn=self.att if r.fuse_out else None,
                          w_out=mod.self_attn.out_proj.weight if r.fuse_out else None, launch=False, pack=self.model._packed_image)
             self.norm_descs.append((fd, self.table_offsets[norm]))
-            L.append(_Launch(r.ff, (fd,), prefix + "ff"))
+            if r.fuse_core:
+                L.append(_Launch("kd_attn_ffn_f32", (_ptr(self.qkv), fd, self.B, gh, gw, nh, *params), prefix + core + "+ff"))
+            else:
+                L.append(_Launch(r.ff, (fd,), prefix + "ff"))
             return
         hid8 = None
         if r.up == "split":

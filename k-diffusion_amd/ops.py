@@ -353,6 +353,23 @@ def ffn(x, norm_scale, w_up, w_down, out=None, scale_stride=None, rows_per_sampl
     return out
 
 
+def attn_ffn_supported(batch, H, W, nh, kernel_size, K, d_ff):
+    """Does the one-launch form of neighbourhood attention core + out projection + feed-forward block (``attn_ffn``) take this shape?"""
+    return bool(nat.lib().kd_attn_ffn_f32_supported(int(batch), int(H), int(W), int(nh), int(kernel_size), int(K), int(d_ff)))
+
+
+def attn_ffn(qkv, nh, kernel_size, x, norm_scale, w_up, w_down, w_out, out=None, eps=1e-6):
+    """``ffn(x, ..., attn=attn_na2d(qkv, nh, kernel_size, prep="packed"), w_out=w_out)`` in ONE launch (fp32-parity split3 mode; the same
+    bits): qkv fp32 [B, H, W, 3 nh 64] stored split by the qkv projection, x fp32 [B, H, W, K]; the attention rows never reach HBM.
+    A shape ``attn_ffn_supported`` refuses is an error."""
+    B, H, W = qkv.shape[0], qkv.shape[1], qkv.shape[2]
+    out = torch.empty_like(x) if out is None else out
+    d = ffn(x, norm_scale, w_up, w_down, out=out, rows_per_sample=H * W, eps=eps, attn=x, w_out=w_out, launch=False)
+    d.attn = None
+    nat.check(nat.lib().kd_attn_ffn_f32(_p(_chk(qkv, "qkv")), C.byref(d), B, H, W, nh, kernel_size, _stream()), "kd_attn_ffn_f32")
+    return out
+
+
 def fourier_sigma(sigma, weight, out=None):
     half = weight.shape[0]
     out = torch.empty(sigma.shape[0], 2 * half, device=sigma.device, dtype=torch.float32) if out is None else out
