@@ -709,6 +709,85 @@ static void run_probes() {
   }
 }
 
+
+// The fused training step (csrc/optim_f32.hip): kd_mt_sqnorm_f32 + kd_mt_adamw_ema_f32 over three tensors (sizes around the vector width and the
+// chunk size) against an fp64 restatement of clip_grad_norm_ + AdamW + the EMA lerp, then the pass timed on 64 Mi elements (44 B per element).
+static void run_optim_case() {
+  if (!want("optim")) return;
+  const std::vector<size_t> sizes = {5, (size_t)KD_MT_CHUNK + 1, (size_t)1 << 20};
+  const KdAdamGroup grp = {2e-3, 1e-2, 0.9, 0.99, 1e-8, 1 - 0.9, 1 - 0.99};
+  std::vector<std::vector<float>> hp, hg, hm, hv, he;
+  std::vector<DevBuf<float>*> dp, dg, dm, dv, de;
+  std::vector<KdMtTensor> table;
+  std::vector<int> chunks;
+  double sq = 0;
+  for (size_t t = 0; t < sizes.size(); ++t) {
+    const size_t n = sizes[t];
+    hp.push_back(randn(n)); hg.push_back(randn(n, 0.01f)); hm.push_back(randn(n, 0.01f)); he.push_back(randn(n));
+    std::vector<float> v = randn(n, 0.01f);
+    for (auto& x : v) x = x * x;
+    hv.push_back(v);
+    for (float g : hg[t]) sq += (double)g * g;
+    DevBuf<float>* bufs[5];
+    const std::vector<float>* src[5] = {&hp[t], &hg[t], &hm[t], &hv[t], &he[t]};
+    for (int i = 0; i < 5; ++i) { bufs[i] = new DevBuf<float>(n); bufs[i]->up(*src[i]); }
+    dp.push_back(bufs[0]); dg.push_back(bufs[1]); dm.push_back(bufs[2]); dv.push_back(bufs[3]); de.push_back(bufs[4]);
+    table.push_back(KdMtTensor{bufs[0]->p, bufs[1]->p, bufs[2]->p, bufs[3]->p, bufs[4]->p, (long long)n, 0, 0});
+    for (size_t c = 0; c * KD_MT_CHUNK < n; ++c) { chunks.push_back((int)t); chunks.push_back((int)c); }
+  }
+  const int n_chunks = (int)chunks.size() / 2;
+  DevBuf<KdMtTensor> dtab(table.size());
+  dtab.up(table);
+  DevBuf<int> dch(chunks.size());
+  dch.up(chunks);
+  DevBuf<double> ws(n_chunks);
+  DevBuf<float> pair(2);
+  const double decay = 0.37;
+  if (kd_mt_sqnorm_f32(dtab.p, dch.p, n_chunks, 1.0f, ws.p, pair.p, 0) != 0 ||
+      kd_mt_adamw_ema_f32(dtab.p, dch.p, n_chunks, &grp, 1, pair.p, decay, 1, 1, 0) != 0) {
+    printf("optim: FAILED to launch: %s\n", kd_last_error());
+    ++g_fail;
+    return;
+  }
+  HIPCHK(hipDeviceSynchronize());
+  const double norm = sqrt(sq), clip = std::min(1.0, 1.0 / (norm + 1e-6));
+  double err = 0, gmax = 0;
+  for (size_t t = 0; t < sizes.size(); ++t) {
+    const std::vector<float> gp = dp[t]->down(), ge = de[t]->down(), gg = dg[t]->down();
+    for (size_t i = 0; i < sizes[t]; ++i) {
+      const double g = hg[t][i] * clip;
+      const double m = hm[t][i] + (1 - grp.beta1) * (g - hm[t][i]), v = hv[t][i] * grp.beta2 + (1 - grp.beta2) * g * g;
+      const double p = hp[t][i] * (1 - grp.lr * grp.wd) - grp.lr / grp.bc1 * m / (sqrt(v) / sqrt(grp.bc2) + grp.eps);
+      const double e = he[t][i] + (1 - decay) * (p - he[t][i]);
+      err = std::max(err, std::max(fabs(gp[i] - p), fabs(ge[i] - e)));
+      gmax = std::max(gmax, (double)fabs(gg[i]));
+    }
+  }
+  const float got_norm = pair.down()[0];
+  const bool ok = err < 1e-5 && gmax == 0 && fabs(got_norm - norm) <= 1e-6 * norm;
+  printf("optim clip+adamw+ema+zero, 3 tensors: max |err| %.2e, norm %.6f (fp64 %.6f), grads zeroed %s: %s\n", err, got_norm, norm,
+         gmax == 0 ? "yes" : "NO", ok ? "ok" : "FAILED");
+  if (!ok) ++g_fail;
+  for (auto* v : {&dp, &dg, &dm, &dv, &de}) for (auto* b : *v) delete b;
+  // the streaming rate: one 64 Mi-element tensor, norm + fused pass = 44 bytes per element
+  const size_t n = (size_t)64 << 20;
+  DevBuf<float> big(5 * n);
+  HIPCHK(hipMemset(big.p, 0, 5 * n * sizeof(float)));
+  std::vector<KdMtTensor> one = {KdMtTensor{big.p, big.p + n, big.p + 2 * n, big.p + 3 * n, big.p + 4 * n, (long long)n, 0, 0}};
+  std::vector<int> bch;
+  for (size_t c = 0; c * KD_MT_CHUNK < n; ++c) { bch.push_back(0); bch.push_back((int)c); }
+  DevBuf<KdMtTensor> dbig(1);
+  dbig.up(one);
+  DevBuf<int> dbch(bch.size());
+  dbch.up(bch);
+  DevBuf<double> bws(bch.size() / 2);
+  const float us = time_us([&] {
+    kd_mt_sqnorm_f32(dbig.p, dbch.p, (int)bch.size() / 2, 1.0f, bws.p, pair.p, 0);
+    kd_mt_adamw_ema_f32(dbig.p, dbch.p, (int)bch.size() / 2, &grp, 1, pair.p, decay, 1, 1, 0);
+  }, 10);
+  printf("optim 64 Mi elements, norm + fused step: %8.1f us  %6.2f TB/s (44 B / element)\n", us, 44.0 * n / us * 1e-6);
+}
+
 int main(int argc, char** argv) {
   if (argc > 1) g_filter = argv[1];
   printf("libkdiff_hip version %d\n", kd_version());
@@ -739,6 +818,7 @@ int main(int argc, char** argv) {
   run_mx8_case("mx8 L1 ff", 32768, 256, 768, 1024);
   run_mx8_case("mx8 L2 ff", 8192, 512, 1536, 256);
   run_mx8_case("mx8 ragged ff", 1000, 256, 768, 50);
+  run_optim_case();
   if (want("astat")) {
     const GemmCase ca[] = {
         {"astat L1 qkv", 32768, 768, 256, KD_EPI_QKV, 1, 1024, 4},

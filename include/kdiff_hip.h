@@ -552,6 +552,60 @@ int kd_f32_to_f64(const float* a, double* out, long long n, void* stream);
 int kd_fid_finish_f32(const float* mean_x, const float* mean_y, const double* cov_x, const double* cov_y, const double* sq, int d, float* out,
                       void* stream);
 
+/* The training step behind the loss (train.py:444-473: accelerator.clip_grad_norm_(model.parameters(), 1.) :464, opt.step() :465 with
+ * optim.AdamW :156-160, opt.zero_grad() :467, K.utils.ema_update :472 = k_diffusion/utils.py:88-104) and the sigma draw in front of it
+ * (train.py:453-454 -> make_sample_density, k_diffusion/config.py:234-268 -> utils.py:267-276, :323-385); csrc/optim_f32.hip.
+ * Multi-tensor kernels: ONE launch covers every tensor of `table`.  The caller keeps two device arrays and refreshes them (an asynchronous
+ * copy on the launch's stream) only when a pointer changes:
+ *   table   one KdMtTensor per parameter: p, g (gradient), m (exp_avg), v (exp_avg_sq), ema (the averaged model's copy, or NULL), n elements,
+ *           group (index into the call's group array);
+ *   chunks  2 ints per workgroup-sized piece: {tensor index, chunk index}; the piece is elements [chunk * KD_MT_CHUNK, min(n, (chunk + 1) *
+ *           KD_MT_CHUNK)) of that tensor.  n_chunks pieces; the grid is capped and strides over the list.
+ * fp32, contiguous.  16-byte accesses where all of a tensor's pointers are 16-byte aligned, element-wise otherwise.  No atomics: fixed summation
+ * order, the same bits on every call.
+ *   kd_mt_sqnorm_f32    : the L2 norm of all gradients in the table: squares and sums in fp64 (a product of two fp32 values is exact), one
+ *                         partial per piece in ws [n_chunks doubles], then a one-workgroup launch that adds the partials in index order.
+ *                         out[0] = (float)sqrt(sum), out[1] = min(1, max_norm / (out[0] + 1e-6)) in fp32: torch.nn.utils.clip_grad_norm_'s
+ *                         coefficient (a NaN norm gives NaN, an infinite one 0, as there).
+ *   kd_mt_adamw_ema_f32 : per element, with group constants lr, wd, beta1, beta2, eps, bc1 = 1 - beta1^step, bc2 = 1 - beta2^step (computed by
+ *                         the host in fp64, rounded to fp32 where torch rounds them): g' = g * clip[1] (clip = the out pair above; NULL: 1);
+ *                         p *= 1 - lr wd;  m = lerp(m, g', 1 - beta1);  v = v beta2 + (1 - beta2) g' g';  p -= (lr / bc1) m / (sqrt(v) /
+ *                         sqrt(bc2) + eps): torch.optim.AdamW with amsgrad = False, maximize = False, rounded once per foreach operation as torch's device path
+ *                         rounds (the multiply-add inside lerp / addcmul / addcdiv fused).  With use_ema and
+ *                         a tensor's ema set: ema = lerp(ema, p_new, 1 - ema_decay) (torch.lerp's two-sided form).  zero_grad: g = 0 in place
+ *                         (otherwise g is left as it was, unclipped).  Tensors whose group lies outside [0, n_groups) are skipped; more than
+ *                         16 groups take one launch per 16.
+ *   kd_mt_lerp_f32      : ema = lerp(ema, p, weight) for every tensor with ema set: K.utils.ema_update's parameter loop in one launch.
+ *   kd_sigma_density_f32: out[e] = the density's transform of the uniform u[e] (KD_DENSITY_*; u and normal fp32, or fp64 with u_f64; out fp32, or
+ *                         fp64 with out_f64; evaluated in fp64).  groups > 0 folds the stratification in: u <- (group + (e % row_len) groups + u)
+ *                         / (row_len groups).  params (8 doubles on the HOST, read at the call):
+ *                           LOGNORMAL {loc, scale}: exp(loc + scale icdf(u (1 - 2e-7) + 1e-7));  LOGLOGISTIC {loc, scale, min_cdf, max_cdf};
+ *                           LOGUNIFORM {log min, log max};  V_DIFFUSION {sigma_data, min_cdf, max_cdf};  COSINE_INTERPOLATED {t_min, t_max,
+ *                           shift of the noise_d_low schedule, the same three of the noise_d_high one, sigma_data};  SPLIT_LOGNORMAL {loc,
+ *                           scale_1, scale_2, scale_1 / (scale_1 + scale_2)} with `normal` = standard normal draws. */
+#define KD_MT_CHUNK 8192
+typedef struct {
+  float* p;
+  float* g;
+  float* m;
+  float* v;
+  float* ema;
+  long long n;
+  int group;
+  int reserved;
+} KdMtTensor;
+typedef struct {
+  double lr, wd, beta1, beta2, eps, bc1, bc2;
+} KdAdamGroup;
+enum { KD_DENSITY_LOGNORMAL = 0, KD_DENSITY_LOGLOGISTIC = 1, KD_DENSITY_LOGUNIFORM = 2, KD_DENSITY_V_DIFFUSION = 3,
+       KD_DENSITY_COSINE_INTERPOLATED = 4, KD_DENSITY_SPLIT_LOGNORMAL = 5 };
+int kd_mt_sqnorm_f32(const KdMtTensor* table, const int* chunks, int n_chunks, float max_norm, double* ws, float* out, void* stream);
+int kd_mt_adamw_ema_f32(const KdMtTensor* table, const int* chunks, int n_chunks, const KdAdamGroup* groups, int n_groups, const float* clip,
+                        double ema_decay, int use_ema, int zero_grad, void* stream);
+int kd_mt_lerp_f32(const KdMtTensor* table, const int* chunks, int n_chunks, double weight, void* stream);
+int kd_sigma_density_f32(int kind, const void* u, int u_f64, const void* normal, void* out, int out_f64, long long n, int row_len, int group,
+                         int groups, const double* params, void* stream);
+
 /* Final image conversion (k_diffusion/utils.py:27-34 to_pil_image): u8 = trunc((clamp(x,-1,1)+1)/2*255)
  * (torchvision's to_pil_image does mul(255).byte(), i.e. truncation) */
 int kd_to_uint8(const float* x, unsigned char* y, long long n, void* stream);

@@ -82,6 +82,22 @@ class KdCall(C.Structure):
     _fields_ = [("op", C.c_int), ("f", C.c_float), ("p", C.c_void_p * 5), ("i", C.c_int * 8)]
 
 
+class KdMtTensor(C.Structure):
+    """include/kdiff_hip.h KdMtTensor: one parameter of a multi-tensor launch (csrc/optim_f32.hip)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("ema", C.c_void_p),
+                ("n", C.c_longlong), ("group", C.c_int), ("reserved", C.c_int)]
+
+
+class KdAdamGroup(C.Structure):
+    """include/kdiff_hip.h KdAdamGroup: the constants of one AdamW group for one step (fp64, computed by the host)."""
+    _fields_ = [("lr", C.c_double), ("wd", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("bc1", C.c_double), ("bc2", C.c_double)]
+
+
+MT_CHUNK = 8192                                      # KD_MT_CHUNK
+(DENSITY_LOGNORMAL, DENSITY_LOGLOGISTIC, DENSITY_LOGUNIFORM, DENSITY_V_DIFFUSION, DENSITY_COSINE_INTERPOLATED,
+ DENSITY_SPLIT_LOGNORMAL) = range(6)                 # KD_DENSITY_*
+
 _vp, _i, _f, _ll, _d = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_double
 _u, _ull = C.c_uint, C.c_ulonglong
 
@@ -179,6 +195,10 @@ SIGNATURES = {
     "kd_sqrtm_vjp_div_f64": [_vp, _vp, _i, _i, _vp, _vp],
     "kd_f32_to_f64": [_vp, _vp, _ll, _vp],
     "kd_fid_finish_f32": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
+    "kd_mt_sqnorm_f32": [_vp, _vp, _i, _f, _vp, _vp, _vp],
+    "kd_mt_adamw_ema_f32": [_vp, _vp, _i, _vp, _i, _vp, _d, _i, _i, _vp],
+    "kd_mt_lerp_f32": [_vp, _vp, _i, _d, _vp],
+    "kd_sigma_density_f32": [_i, _vp, _i, _vp, _vp, _i, _ll, _i, _i, _i, _vp, _vp],
     "kd_prof_enable": [_i],
     "kd_prof_count": [],
     "kd_prof_get": [_i, C.c_char_p, _i, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double)],

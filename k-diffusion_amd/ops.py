@@ -1219,3 +1219,22 @@ def fid_finish(mean_x, mean_y, cov_x, cov_y, sq):
                                           _p(_chk(cov_y, "cov_y", torch.float64)), _p(_chk(sq, "sq", torch.float64)), d, _p(out), _stream()),
               "kd_fid_finish_f32")
     return out
+
+
+def sigma_density(kind, u, params, normal=None, group=0, groups=0, dtype=None):
+    """sigmas from uniform draws ``u`` (fp32 or fp64, any shape) under density ``kind`` (nat.DENSITY_*) with up to 8 host constants
+    ``params`` (include/kdiff_hip.h: kd_sigma_density_f32); ``normal``: standard normal draws of u's shape and dtype for the split
+    log-normal.  ``groups > 0`` folds the stratification of utils.stratified_uniform over u's last dimension in.  Output fp32, or fp64
+    with ``dtype=torch.float64``."""
+    _chk(u, "u", u.dtype if isinstance(u, torch.Tensor) and u.dtype == torch.float64 else torch.float32)
+    if normal is not None:
+        _chk(normal, "normal", u.dtype)
+        if normal.shape != u.shape:
+            raise ValueError("sigma_density: normal and u differ in shape")
+    out = torch.empty(u.shape, device=u.device, dtype=torch.float64 if dtype == torch.float64 else torch.float32)
+    if u.numel():
+        prm = (C.c_double * 8)(*[float(v) for v in params], *([0.0] * (8 - len(params))))
+        nat.check(nat.lib().kd_sigma_density_f32(int(kind), _p(u), int(u.dtype == torch.float64), _p(normal), _p(out),
+                                                 int(out.dtype == torch.float64), u.numel(), u.shape[-1] if u.ndim else 1, int(group), int(groups),
+                                                 prm, _stream()), "kd_sigma_density_f32")
+    return out

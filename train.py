@@ -1,0 +1,318 @@
+#!/usr/bin/env python3
+
+"""Trains Karras et al. (2022) diffusion models: the single-GPU, single-process form of the reference's train.py.
+
+The loss, its backward, the optimizer step (gradient clipping + AdamW + EMA + gradient zeroing, K.optim.AdamW), the sigma draw and the demo
+sampler all run on this project's HIP kernels.  Differences from the reference, by design:
+  * one process, one GPU; dataset type ``imagefolder`` only (PIL, LANCZOS resize + centre crop); no augmentation (``augment_prob`` must be
+    0; ``aug_cond`` is zeros [B, 9], what the reference's disabled pipeline yields); optimizer ``adamw`` only; no --gns, wandb or evaluation;
+  * a checkpoint also holds the RNG states and the position in the epoch, and the data order is a function of (seed, epoch), so that
+    ``--resume`` continues the run it was saved from bit for bit (the reference restarts the epoch and its RNG streams).
+"""
+
+import argparse
+from copy import deepcopy
+import json
+import math
+import os
+from pathlib import Path
+import sys
+import time
+
+import torch
+from torch.utils import data
+
+import k_diffusion_amd as K
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split('\n')[0], formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument('--batch-size', type=int, default=64, help='the batch size')
+    p.add_argument('--config', type=str, required=True, help='the configuration file')
+    p.add_argument('--demo-every', type=int, default=500, help='save a demo grid every this many steps')
+    p.add_argument('--end-step', type=int, default=None, help='the step to end training at')
+    p.add_argument('--grad-accum-steps', type=int, default=1, help='the number of gradient accumulation steps')
+    p.add_argument('--lr', type=float, help='the learning rate')
+    p.add_argument('--name', type=str, default='model', help='the name of the run')
+    p.add_argument('--num-workers', type=int, default=8, help='the number of data loader workers')
+    p.add_argument('--reset-ema', action='store_true', help='reset the EMA')
+    p.add_argument('--resume', type=str, help='the checkpoint to resume from')
+    p.add_argument('--resume-inference', type=str, help='the inference checkpoint to resume from')
+    p.add_argument('--sample-n', type=int, default=64, help='the number of images to sample for demo grids')
+    p.add_argument('--save-every', type=int, default=10000, help='save every this many steps')
+    p.add_argument('--seed', type=int, help='the random seed')
+    # flags of the reference that this form does not implement: named, so that their use fails with a reason
+    p.add_argument('--gns', action='store_true', help=argparse.SUPPRESS)
+    p.add_argument('--wandb-project', type=str, help=argparse.SUPPRESS)
+    p.add_argument('--evaluate-only', action='store_true', help=argparse.SUPPRESS)
+    p.add_argument('--evaluate-every', type=int, default=0, help=argparse.SUPPRESS)
+    p.add_argument('--evaluate-n', type=int, default=0, help=argparse.SUPPRESS)
+    p.add_argument('--mixed-precision', type=str, help=argparse.SUPPRESS)
+    p.add_argument('--compile', action='store_true', help=argparse.SUPPRESS)
+    p.add_argument('--checkpointing', action='store_true', help=argparse.SUPPRESS)
+    args = p.parse_args(argv)
+    if args.gns:
+        p.error('--gns measures the gradient noise scale across DDP ranks; this is the single-GPU loop')
+    if args.wandb_project:
+        p.error('wandb logging is not implemented')
+    if args.evaluate_only or args.evaluate_every > 0 or args.evaluate_n > 0:
+        p.error('the evaluation flags are not implemented here: compute FID / KID with K.evaluation on samples of the checkpoint')
+    if args.mixed_precision or args.compile or args.checkpointing:
+        p.error('--mixed-precision / --compile / --checkpointing are not implemented (the loss runs on the fp32 HIP path)')
+    if args.grad_accum_steps < 1:
+        p.error('--grad-accum-steps must be at least 1')
+    return args
+
+
+def make_grid(x, nrow):
+    """[N, C, H, W] -> [C, rows * H, nrow * W], row-major, no padding (torchvision.utils.make_grid(x, nrow, padding=0))."""
+    n, c, h, w = x.shape
+    rows = math.ceil(n / nrow)
+    grid = x.new_zeros(rows * nrow, c, h, w)
+    grid[:n] = x
+    return grid.view(rows, nrow, c, h, w).permute(2, 0, 3, 1, 4).reshape(c, rows * h, nrow * w)
+
+
+def epoch_batches(n_items, batch_size, data_seed, epoch):
+    """The epoch's batches (shuffle=True, drop_last=True) as a function of (data_seed, epoch)."""
+    perm = torch.randperm(n_items, generator=torch.Generator().manual_seed(data_seed + epoch)).tolist()
+    return [perm[i:i + batch_size] for i in range(0, n_items - batch_size + 1, batch_size)]
+
+
+def main(argv=None):
+    args = parse_args(argv)
+
+    config = K.config.load_config(args.config)
+    model_config = config['model']
+    dataset_config = config['dataset']
+    opt_config = config['optimizer']
+    sched_config = config['lr_sched']
+    ema_sched_config = config['ema_sched']
+
+    assert len(model_config['input_size']) == 2 and model_config['input_size'][0] == model_config['input_size'][1]
+    size = model_config['input_size']
+    if model_config.get('augment_prob', 0) > 0:
+        raise NotImplementedError('augment_prob > 0: KarrasAugmentationPipeline (scikit-image warps) is not implemented; set augment_prob to 0')
+    if opt_config['type'] != 'adamw':
+        raise NotImplementedError(f'optimizer type {opt_config["type"]!r}: only adamw runs on the fused HIP step')
+    if dataset_config['type'] != 'imagefolder':
+        raise NotImplementedError(f'dataset type {dataset_config["type"]!r}: only imagefolder is implemented')
+    if not torch.cuda.is_available():
+        raise RuntimeError('train.py needs a ROCm device; there is no CPU fallback')
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise NotImplementedError('multi-GPU (DDP) training is not implemented: run one process on one device')
+    device = torch.device('cuda')
+    print(f'Using device: {device}', flush=True)
+    print(f'Batch size: {args.batch_size}', flush=True)
+
+    if args.seed is not None:
+        seeds = torch.randint(-2 ** 63, 2 ** 63 - 1, [1], generator=torch.Generator().manual_seed(args.seed))
+        torch.manual_seed(seeds[0])
+    demo_gen = torch.Generator().manual_seed(torch.randint(-2 ** 63, 2 ** 63 - 1, ()).item())
+    data_seed = torch.randint(0, 2 ** 62, ()).item()
+    elapsed = 0.0
+
+    inner_model = K.config.make_model(config)
+    inner_model_ema = deepcopy(inner_model)
+    print(f'Parameters: {K.utils.n_params(inner_model):,}')
+    inner_model, inner_model_ema = inner_model.to(device), inner_model_ema.to(device)
+    if any(rate > 0 for _, rate in inner_model._dropout_rates()):
+        inner_model.enable_dropout()
+
+    lr = opt_config['lr'] if args.lr is None else args.lr
+    opt = K.optim.AdamW(inner_model.param_groups(lr), lr=lr, betas=tuple(opt_config['betas']), eps=opt_config['eps'],
+                        weight_decay=opt_config['weight_decay'])
+    opt.attach_ema(inner_model, inner_model_ema)
+
+    if sched_config['type'] == 'inverse':
+        sched = K.utils.InverseLR(opt, inv_gamma=sched_config['inv_gamma'], power=sched_config['power'], warmup=sched_config['warmup'])
+    elif sched_config['type'] == 'exponential':
+        sched = K.utils.ExponentialLR(opt, num_steps=sched_config['num_steps'], decay=sched_config['decay'], warmup=sched_config['warmup'])
+    elif sched_config['type'] == 'constant':
+        sched = K.utils.ConstantLRWithWarmup(opt, warmup=sched_config['warmup'])
+    else:
+        raise ValueError('Invalid schedule type')
+
+    assert ema_sched_config['type'] == 'inverse'
+    ema_sched = K.utils.EMAWarmup(power=ema_sched_config['power'], max_value=ema_sched_config['max_value'])
+    ema_stats = {}
+
+    channels = model_config['input_channels']
+    if channels not in (1, 3):
+        raise NotImplementedError(f'imagefolder yields RGB or greyscale images; input_channels = {channels}')
+
+    def tf(image):
+        image = K.utils.resize_center_crop(image, size[0])
+        return K.utils.from_pil_image(image if channels == 3 else image.convert('L'))
+
+    train_set = K.utils.FolderOfImages(dataset_config['location'], transform=tf)
+    print(f'Number of items in dataset: {len(train_set):,}')
+    if len(train_set) < args.batch_size:
+        raise ValueError(f'the dataset has {len(train_set)} images, fewer than one batch of {args.batch_size}')
+
+    image_key = dataset_config.get('image_key', 0)
+    num_classes = dataset_config.get('num_classes', 0)
+    cond_dropout_rate = dataset_config.get('cond_dropout_rate', 0.1)
+    class_key = dataset_config.get('class_key', 1)
+    if num_classes:
+        raise NotImplementedError('dataset.num_classes > 0: an imagefolder dataset carries no class labels')
+
+    sigma_min = model_config['sigma_min']
+    sigma_max = model_config['sigma_max']
+    sample_density = K.training.make_sample_density(model_config)
+
+    model = K.config.make_denoiser_wrapper(config)(inner_model)
+    model_ema = K.config.make_denoiser_wrapper(config)(inner_model_ema)
+
+    state_path = Path(f'{args.name}_state.json')
+    accum = args.grad_accum_steps
+    epoch, step, batch_in_epoch = 0, 0, 0
+
+    if state_path.exists() or args.resume:
+        ckpt_path = args.resume if args.resume else json.load(open(state_path))['latest_checkpoint']
+        print(f'Resuming from {ckpt_path}...')
+        ckpt = torch.load(ckpt_path, map_location='cpu', weights_only=False)
+        inner_model.load_state_dict(ckpt['model'])
+        inner_model_ema.load_state_dict(ckpt['model_ema'])
+        opt.load_state_dict(ckpt['opt'])
+        sched.load_state_dict(ckpt['sched'])
+        ema_sched.load_state_dict(ckpt['ema_sched'])
+        ema_stats = ckpt.get('ema_stats', ema_stats)
+        epoch, step = ckpt['epoch'], ckpt['step']
+        if 'demo_gen' in ckpt:
+            demo_gen.set_state(ckpt['demo_gen'])
+        elapsed = ckpt.get('elapsed', 0.0)
+        if 'rng_state' in ckpt:                      # a checkpoint of this script: continue its streams and its epoch
+            torch.set_rng_state(ckpt['rng_state'])
+            torch.cuda.set_rng_state(ckpt['cuda_rng_state'], device)
+            data_seed, batch_in_epoch = ckpt['data_seed'], ckpt['batch_in_epoch']
+            params = dict(inner_model.named_parameters())
+            for n, g in ckpt.get('pending_grads', {}).items():
+                params[n].grad = g.to(device)
+        else:                                        # a reference checkpoint: it counts from the next epoch and step
+            epoch, step = epoch + 1, step + 1
+        del ckpt
+
+    if args.reset_ema:
+        inner_model.load_state_dict(inner_model_ema.state_dict())
+        ema_sched = K.utils.EMAWarmup(power=ema_sched_config['power'], max_value=ema_sched_config['max_value'])
+        ema_stats = {}
+
+    if args.resume_inference:
+        import safetensors.torch as safetorch
+        print(f'Loading {args.resume_inference}...')
+        ckpt = safetorch.load_file(args.resume_inference)
+        inner_model.load_state_dict(ckpt)
+        inner_model_ema.load_state_dict(ckpt)
+        del ckpt
+
+    @torch.no_grad()
+    def demo():
+        print('Sampling...', flush=True)
+        filename = f'{args.name}_demo_{step:08}.png'
+        with K.utils.eval_mode(model_ema):
+            x = torch.randn([args.sample_n, channels, size[0], size[1]], generator=demo_gen).to(device) * sigma_max
+            model_fn, extra_args = model_ema, {}
+            if num_classes:
+                extra_args['class_cond'] = torch.randint(0, num_classes, [args.sample_n], generator=demo_gen).to(device)
+                model_fn = K.sampling.make_cfg_model_fn(model_ema, 1., num_classes)
+            sigmas = K.sampling.get_sigmas_karras(50, sigma_min, sigma_max, rho=7., device=device)
+            x_0 = K.sampling.sample_dpmpp_2m_sde(model_fn, x, sigmas, extra_args=extra_args, eta=0.0, solver_type='heun', disable=True)
+        grid = make_grid(x_0, math.ceil(args.sample_n ** 0.5))
+        K.utils.to_pil_image(grid.contiguous()).save(filename)
+
+    def save():
+        filename = f'{args.name}_{step:08}.pth'
+        print(f'Saving to {filename}...', flush=True)
+        obj = {
+            'config': config,
+            'model': inner_model.state_dict(),
+            'model_ema': inner_model_ema.state_dict(),
+            'opt': opt.state_dict(),
+            'sched': sched.state_dict(),
+            'ema_sched': ema_sched.state_dict(),
+            'epoch': epoch,
+            'step': step,
+            'gns_stats': None,
+            'ema_stats': ema_stats,
+            'demo_gen': demo_gen.get_state(),
+            'elapsed': elapsed,
+            'rng_state': torch.get_rng_state(),
+            'cuda_rng_state': torch.cuda.get_rng_state(device),
+            'data_seed': data_seed,
+            'batch_in_epoch': batch_in_epoch,
+        }
+        if step % accum != 0:                        # saved inside an accumulation window: the gradients gathered so far go along
+            obj['pending_grads'] = {n: p.grad for n, p in inner_model.named_parameters() if p.grad is not None}
+        torch.save(obj, filename)
+        json.dump({'latest_checkpoint': filename}, open(state_path, 'w'))
+
+    log = K.utils.CSVLogger(f'{args.name}_log.csv', ['step', 'epoch', 'time', 'loss', 'avg_loss', 'lr', 'ema_decay', 'grad_norm'])
+    losses_since_last_print = []
+    grad_norm = None
+
+    try:
+        while True:
+            batches = epoch_batches(len(train_set), args.batch_size, data_seed, epoch)[batch_in_epoch:]
+            train_dl = data.DataLoader(train_set, batch_sampler=batches, num_workers=args.num_workers, pin_memory=True,
+                                       generator=torch.Generator().manual_seed(data_seed + epoch)) if batches else ()
+            for batch in train_dl:
+                torch.cuda.synchronize()
+                start_timer = time.time()
+
+                sync_gradients = (step + 1) % accum == 0
+                reals = batch[image_key].to(device, non_blocking=True)
+                aug_cond = reals.new_zeros([reals.shape[0], 9])
+                extra_args = {}
+                if num_classes:
+                    class_cond = batch[class_key].to(device)
+                    drop = torch.rand(class_cond.shape, device=class_cond.device)
+                    class_cond.masked_fill_(drop < cond_dropout_rate, num_classes)
+                    extra_args['class_cond'] = class_cond
+                noise = torch.randn_like(reals)
+                with K.utils.enable_stratified(step % accum, accum):
+                    sigma = sample_density([reals.shape[0]], device=device)
+                losses = model.loss(reals, noise, sigma, aug_cond=aug_cond, **extra_args)
+                loss = losses.mean().item()
+                losses_since_last_print.append(loss)
+                (losses.mean() / accum).backward()
+                ema_decay = ema_sched.get_value()
+                if sync_gradients:
+                    # clip at 1, AdamW, the EMA update and the gradient zeroing in one pass (train.py:463-467, :472)
+                    grad_norm = opt.step(clip_grad_norm=1., ema_decay=ema_decay, zero_grad=True)
+                sched.step()
+                K.utils.ema_update_dict(ema_stats, {'loss': loss}, ema_decay ** (1 / accum))
+                if sync_gradients:
+                    ema_sched.step()
+
+                torch.cuda.synchronize()
+                elapsed += time.time() - start_timer
+
+                log.write(step, epoch, elapsed, loss, ema_stats['loss'], sched.get_last_lr()[0], ema_decay,
+                          '' if grad_norm is None else grad_norm.item())
+                if step % 25 == 0:
+                    loss_disp = sum(losses_since_last_print) / len(losses_since_last_print)
+                    losses_since_last_print.clear()
+                    print(f'Epoch: {epoch}, step: {step}, loss: {loss_disp:g}, avg loss: {ema_stats["loss"]:g}', flush=True)
+
+                step += 1
+                batch_in_epoch += 1
+
+                if step % args.demo_every == 0:
+                    demo()
+
+                if step == args.end_step or (step > 0 and step % args.save_every == 0):
+                    save()
+
+                if step == args.end_step:
+                    print('Done!')
+                    return
+
+            epoch += 1
+            batch_in_epoch = 0
+    except KeyboardInterrupt:
+        pass
+
+
+if __name__ == '__main__':
+    sys.exit(main())
