@@ -13,8 +13,8 @@
 //     wait + barrier sits in the MIDDLE of a stage -- are issued before the 12 MFMAs of the current chunk, so no MFMA waits for an LDS
 //     round trip even with one wave per SIMD (K >= 256: the fragments of a row take 128 / 256 registers).  A stage is 16 ds_read_b128
 //     per 24 MFMAs: inside the 6-issue-slot shadow of an MFMA measured in r03_issue_model.md;
-//   * RoPE angles from the token's axial position and the head's frequencies (hardware sin / cos in revolutions) instead of cos / sin
-//     tables: no vector loads inside the ring loop (hipcc waits vmcnt(0) for an ordinary load issued beside LDS-DMA, draining the ring).
+//   * RoPE angles from the token's axial position and the head's frequencies instead of cos / sin tables (x3_common.h: qk_tab_fill).
+// The per-head qk table, the workgroup -> (panel, n-split) mapping and the host's n-split choice live in x3_common.h.
 #include "x3_common.h"
 
 namespace kd {
@@ -55,25 +55,9 @@ __global__ __launch_bounds__(256, NC <= 8 ? 2 : 1) void gemm_x3_astat_kernel(con
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform, and provably so: LDS-DMA bases (M0) and W addresses stay scalar
   const auto warm = code_warm_begin<(NC <= 8 ? 14 : 24) * 1024>((int)blockIdx.x < p.warm && tid < 64);
-  // workgroup -> (row panel, n-split): the splits of one panel get ids 8 apart, i.e. the same XCD (one L2 fetches the panel's rows once)
-  int panel, split;
-  const int n_splits = p.n_splits, n_panels = gridDim.x / n_splits;
-  if ((n_panels & 7) == 0) {
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    panel = (j / n_splits) * 8 + xcd;
-    split = j % n_splits;
-  } else {
-    panel = blockIdx.x % n_panels;
-    split = blockIdx.x / n_panels;
-  }
-  // (integer division by a run-time value goes through the vector unit: hand the uniform results back to scalar registers, or every
-  // address and per-head constant derived from them is vector arithmetic, and the s_load operands below become waterfall loops)
-  panel = __builtin_amdgcn_readfirstlane(panel);
-  split = __builtin_amdgcn_readfirstlane(split);
-  const int nt_begin = __builtin_amdgcn_readfirstlane((int)((long)p.n_tiles * split / n_splits));
-  const int nt_end = __builtin_amdgcn_readfirstlane((int)((long)p.n_tiles * (split + 1) / n_splits));
-  const int n_tiles = nt_end - nt_begin, total = n_tiles * NK;
-  const int m0 = panel * 128;
+  const PanelSplit ps = panel_split(p.n_splits, p.n_tiles);
+  const int nt_begin = ps.t_begin, n_tiles = ps.t_end - ps.t_begin, total = n_tiles * NK;
+  const int m0 = ps.panel * 128;
   const bool probe = p.clk && blockIdx.x == 0 && tid == 0;
   if (probe) { p.clk[0] = __builtin_amdgcn_s_memtime(); p.clk[1] = __builtin_amdgcn_s_memrealtime(); }
   const WgStamp wgs = wg_stamp_begin(p.clk);
@@ -190,14 +174,9 @@ __global__ __launch_bounds__(256, NC <= 8 ? 2 : 1) void gemm_x3_astat_kernel(con
   }
   float py = 0.f, px = 0.f;
   if (EPI == KD_EPI_QKV) {
-    float* qk_tab = reinterpret_cast<float*>(smem + NSTG * STG + 4 * SCL + 4 * 2048);
-    if (tid < p.n_heads * 8) qk_tab[tid] = p.freq[tid];
-    if (tid < p.n_heads) qk_tab[128 + tid] = sqrtf(p.qk_scale[tid]);
-    const int tok = rowc % p.rows_per_sample;
-    py = p.pos[2 * tok];
-    px = p.pos[2 * tok + 1];
-    asm volatile("" : "+v"(py), "+v"(px));            // consumed HERE as far as the compiler knows: its wait for the two loads lands before
-  }                                                   // the ring starts, not as a vmcnt(0) in the first epilogue
+    qk_tab_fill(reinterpret_cast<float*>(smem + NSTG * STG + 4 * SCL + 4 * 2048), tid, p);
+    token_pos(p.pos, rowc % p.rows_per_sample, py, px);
+  }
   code_warm_end(warm);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   KD_BARRIER();                                        // every wave has taken its rows out of the slots it borrowed
@@ -406,12 +385,7 @@ __global__ __launch_bounds__(256, NC <= 8 ? 2 : 1) void gemm_x3_astat_kernel(con
         f32x16& a0 = acc[2 * vv];
         f32x16& a1 = acc[2 * vv + 1];
         if (which < 2) {
-          // the head's RoPE frequencies (this lane's four: 4 lh ..) and sqrt(cosine-sim scale) from the table parked in LDS by the prologue:
-          // one ds_read_b128 + one ds_read_b32, no vector-memory load beside the LDS-DMA ring and no per-element selects
-          const f32x4 fv = *reinterpret_cast<const f32x4*>(qkc + (head * 8 + 4 * lh) * 4);
-          const float qsc = *reinterpret_cast<const float*>(qkc + 512 + head * 4);
-          const float fr[4] = {fv[0], fv[1], fv[2], fv[3]};
-          b16::qk_prep_blocks(a0, a1, rs, qsc, p.eps, py, px, fr);
+          qk_prep_head(qkc, head, lh, a0, a1, rs, p.eps, py, px);
         } else {
 #pragma unroll
           for (int r = 0; r < 16; ++r) { a0[r] *= rs; a1[r] *= rs; }
@@ -495,22 +469,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x3h_kernel(const XArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const auto warm = code_warm_begin<20 * 1024>((int)blockIdx.x < p.warm && tid < 64);
-  int panel, split;
-  const int n_splits = p.n_splits, n_panels = gridDim.x / n_splits;
-  if ((n_panels & 7) == 0) {
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    panel = (j / n_splits) * 8 + xcd;
-    split = j % n_splits;
-  } else {
-    panel = blockIdx.x % n_panels;
-    split = blockIdx.x / n_panels;
-  }
-  panel = __builtin_amdgcn_readfirstlane(panel);
-  split = __builtin_amdgcn_readfirstlane(split);
-  const int ht_begin = __builtin_amdgcn_readfirstlane((int)((long)p.n_tiles * split / n_splits));      // (n_tiles counts HALF tiles here)
-  const int ht_end = __builtin_amdgcn_readfirstlane((int)((long)p.n_tiles * (split + 1) / n_splits));
-  const int n_ht = ht_end - ht_begin, total = n_ht * UNIT;
-  const int m0 = panel * 128;
+  const PanelSplit ps = panel_split(p.n_splits, p.n_tiles);      // (n_tiles counts HALF tiles here)
+  const int ht_begin = ps.t_begin, n_ht = ps.t_end - ps.t_begin, total = n_ht * UNIT;
+  const int m0 = ps.panel * 128;
   const bool probe = p.clk && blockIdx.x == (gridDim.x * 5) / 8 && tid == 0;
   if (probe) { p.clk[0] = __builtin_amdgcn_s_memtime(); p.clk[1] = __builtin_amdgcn_s_memrealtime(); }
   const WgStamp wgs = wg_stamp_begin(p.clk);
@@ -590,13 +551,8 @@ __global__ __launch_bounds__(256, 2) void gemm_x3h_kernel(const XArgs p) {
   }
   float py = 0.f, px = 0.f;
   if (EPI == KD_EPI_QKV) {
-    float* qk_tab = reinterpret_cast<float*>(smem + NSTG * STG + 4 * SCL + 4 * 2048);
-    if (tid < p.n_heads * 8) qk_tab[tid] = p.freq[tid];
-    if (tid < p.n_heads) qk_tab[128 + tid] = sqrtf(p.qk_scale[tid]);
-    const int tok = rowc % p.rows_per_sample;
-    py = p.pos[2 * tok];
-    px = p.pos[2 * tok + 1];
-    asm volatile("" : "+v"(py), "+v"(px));
+    qk_tab_fill(reinterpret_cast<float*>(smem + NSTG * STG + 4 * SCL + 4 * 2048), tid, p);
+    token_pos(p.pos, rowc % p.rows_per_sample, py, px);
   }
   code_warm_end(warm);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -728,10 +684,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3h_kernel(const XArgs p) {
       const int vec = n0 >> 6;                              // (q | k | v, head) vector index of these 64 columns
       const int which = vec >= 2 * p.n_heads ? 2 : (vec >= p.n_heads ? 1 : 0), head = vec - which * p.n_heads;
       if (which < 2) {
-        const f32x4 fv = *reinterpret_cast<const f32x4*>(qkc + (head * 8 + 4 * lh) * 4);
-        const float qsc = *reinterpret_cast<const float*>(qkc + 512 + head * 4);
-        const float fr[4] = {fv[0], fv[1], fv[2], fv[3]};
-        b16::qk_prep_blocks(acc[0], acc[1], rs, qsc, p.eps, py, px, fr);
+        qk_prep_head(qkc, head, lh, acc[0], acc[1], rs, p.eps, py, px);
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc[0][r] *= rs; acc[1][r] *= rs; }
@@ -775,18 +728,7 @@ static int launch(const XArgs& a0, const char* nm, double flops, double bytes, h
   constexpr int LDS = NSTG * STG + 4 * (K * 4 < 1024 ? 1024 : K * 4) + 4 * 2048 + 1024;     // ring + scale vectors + store strips + per-head constants
   static LdsAttr attr_set;
   attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
-  // n-splits of a panel: every workgroup pays the row prologue (about one n-tile's K loop) and then its share of the n-tiles; the grid
-  // runs in ceil(workgroups / resident slots) rounds.  The divisor of n_tiles with the smallest rounds x (1 + tiles per split) wins
-  // (ties: fewer splits = fewer redundant prologues).
-  const int panels = (a0.M + 127) / 128, slots = (NC <= 8 ? 2 : 1) * cu_count();
-  int best = 1;
-  long best_cost = -1;
-  for (int sp = 1; sp <= a0.n_tiles; ++sp) {
-    if (a0.n_tiles % sp) continue;
-    const long rounds = ((long)panels * sp + slots - 1) / slots;
-    const long cost = rounds * (1 + a0.n_tiles / sp);
-    if (best_cost < 0 || cost < best_cost) { best = sp; best_cost = cost; }
-  }
+  const int panels = (a0.M + 127) / 128, best = best_n_splits(panels, a0.n_tiles, (NC <= 8 ? 2 : 1) * cu_count(), 1);
   const int forced = force_splits ? force_splits : option("x3_splits", 0);
   XArgs a = a0;
   a.n_splits = forced > 0 && forced <= a0.n_tiles ? forced : best;
@@ -802,15 +744,7 @@ static int launch_half(const XArgs& a0, const char* nm, double flops, double byt
   static LdsAttr attr_set;
   attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
   // the same cost model as launch() with two resident workgroups per CU; a prologue costs about two half tiles
-  const int panels = (a0.M + 127) / 128, slots = 2 * cu_count();
-  int best = 1;
-  long best_cost = -1;
-  for (int sp = 1; sp <= a0.n_tiles; ++sp) {
-    if (a0.n_tiles % sp) continue;
-    const long rounds = ((long)panels * sp + slots - 1) / slots;
-    const long cost = rounds * (2 + a0.n_tiles / sp);
-    if (best_cost < 0 || cost < best_cost) { best = sp; best_cost = cost; }
-  }
+  const int panels = (a0.M + 127) / 128, best = best_n_splits(panels, a0.n_tiles, 2 * cu_count(), 2);
   const int forced = option("x3_splits", 0);
   XArgs a = a0;
   a.n_splits = forced > 0 && forced <= a0.n_tiles && a0.n_tiles % forced == 0 ? forced : best;

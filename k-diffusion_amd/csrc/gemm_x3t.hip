@@ -15,7 +15,7 @@
 //             with stage kt - 1" and "everyone's pieces of stage kt + 1 are in" are the same rendezvous), two waves per SIMD
 //   epilogues in the lane that owns the row: store | + residual | qkv (cosine-sim scale + RoPE from positions, optional split-stored
 //             operands for the attention cores) | GEGLU, each to fp32 [M, N] or (c_split) to bf16 hi / lo planes for the next GEMM
-#include "bf16_common.h"
+#include "x3_common.h"
 
 namespace kd {
 namespace x3t {
@@ -24,11 +24,12 @@ using b16::bf16x8;
 using b16::u16;
 using b16::u32x4;
 using b16::pack_bf16;
+using x3::swz64;
+using x3::pack_split4;
+using x3::store_block_planes;
 
 constexpr int BMR = 256, AIMG = BMR * 64, WSTG = 16384, WIMG = 8192, STG = 2 * AIMG + WSTG, NSTG = 3;
 constexpr int LDS_BYTES = NSTG * STG + 1024;            // ring + per-head constants
-
-__device__ __forceinline__ int swz64(int row, int c) { return row * 64 + ((c ^ ((row >> 2) & 3)) << 4); }
 
 struct TArgs {
   const u16* Ah; const u16* Al; const char* Wp;
@@ -39,28 +40,6 @@ struct TArgs {
   float out_add, eps;
   int warm;
 };
-
-#define KD_BARRIER() asm volatile("s_barrier" ::: "memory")
-
-__device__ __forceinline__ f32x4 pack_split4(const f32x4 v) {
-  const unsigned h0 = pack_bf16(v[0], v[1]), h1 = pack_bf16(v[2], v[3]);
-  const unsigned l0 = pack_bf16(v[0] - b16::bf_lo(h0), v[1] - b16::bf_hi(h0)), l1 = pack_bf16(v[2] - b16::bf_lo(h1), v[3] - b16::bf_hi(h1));
-  return f32x4{__uint_as_float(h0), __uint_as_float(h1), __uint_as_float(l0), __uint_as_float(l1)};
-}
-// one 32-feature block of the lane's row (fp32, C-layout order) -> bf16 hi / lo planes
-__device__ __forceinline__ void store_block_planes(u16* hrow, u16* lrow, const float (&v)[16], int lh, bool ok) {
-  float hi[16], lo[16];
-#pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    const unsigned h = pack_bf16(v[r], v[r + 1]);
-    hi[r] = b16::bf_lo(h);
-    hi[r + 1] = b16::bf_hi(h);
-    lo[r] = v[r] - hi[r];
-    lo[r + 1] = v[r + 1] - hi[r + 1];
-  }
-  b16::store_block_bf16(hrow, hi, lh, ok);        // (exact: hi is a bf16 value)
-  b16::store_block_bf16(lrow, lo, lh, ok);
-}
 
 template <int EPI, bool CSPLIT>
 __global__ __launch_bounds__(512, 1) void gemm_x3_tiled_kernel(const TArgs p) {
@@ -110,16 +89,9 @@ __global__ __launch_bounds__(512, 1) void gemm_x3_tiled_kernel(const TArgs p) {
 
   float py[2] = {0.f, 0.f}, px[2] = {0.f, 0.f};
   if (EPI == KD_EPI_QKV) {
-    float* qk_tab = reinterpret_cast<float*>(smem + NSTG * STG);
-    if (tid < p.n_heads * 8) qk_tab[tid] = p.freq[tid];
-    if (tid < p.n_heads) qk_tab[128 + tid] = sqrtf(p.qk_scale[tid]);
+    x3::qk_tab_fill(reinterpret_cast<float*>(smem + NSTG * STG), tid, p);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int tok = min(m0 + wr * 64 + 32 * j + l31, p.M - 1) % p.rows_per_sample;
-      py[j] = p.pos[2 * tok];
-      px[j] = p.pos[2 * tok + 1];
-      asm volatile("" : "+v"(py[j]), "+v"(px[j]));            // consumed here as far as the compiler knows (its wait lands before the ring)
-    }
+    for (int j = 0; j < 2; ++j) x3::token_pos(p.pos, min(m0 + wr * 64 + 32 * j + l31, p.M - 1) % p.rows_per_sample, py[j], px[j]);
   }
   code_warm_end(warm);
   issue(0);
@@ -220,10 +192,7 @@ __global__ __launch_bounds__(512, 1) void gemm_x3_tiled_kernel(const TArgs p) {
       const int vec = (n0 >> 6) + wc;                        // (q | k | v, head) vector index of this wave's 64 columns
       const int which = vec >= 2 * p.n_heads ? 2 : (vec >= p.n_heads ? 1 : 0), head = vec - which * p.n_heads;
       if (which < 2) {
-        const f32x4 fv = *reinterpret_cast<const f32x4*>(qkc + (head * 8 + 4 * lh) * 4);
-        const float qsc = *reinterpret_cast<const float*>(qkc + 512 + head * 4);
-        const float fr[4] = {fv[0], fv[1], fv[2], fv[3]};
-        b16::qk_prep_blocks(acc[0][j], acc[1][j], 1.0f, qsc, p.eps, py[j], px[j], fr);
+        x3::qk_prep_head(qkc, head, lh, acc[0][j], acc[1][j], 1.0f, p.eps, py[j], px[j]);
       }
     }
 #pragma unroll

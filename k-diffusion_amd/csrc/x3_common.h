@@ -1,5 +1,7 @@
 // Shared pieces of the round-3 fp32-parity ("split3") kernels: gemm_x3.hip (norm -> projection), ffn_x3.hip (fused feed-forward block).
-// Packed weight stage, counted waits, hi / lo splitting, compile-time loops and the named-AccVGPR helpers.
+// Packed weight stage, counted waits, hi / lo splitting, compile-time loops and the named-AccVGPR helpers; at the end what the projection
+// kernels (gemm_x3.hip, gemm_x3t.hip) share outside their K loops: plane stores, the per-head qk table, the workgroup -> (panel, n-split)
+// mapping and the host's n-split choice.
 #pragma once
 #include "bf16_common.h"
 #include <utility>
@@ -125,6 +127,83 @@ __device__ __forceinline__ void mfma_ag0(f32x16& acc, const bf16x8 w) {
 template <int IDX>
 __device__ __forceinline__ void mfma_ag(f32x16& acc, const bf16x8 w) {
   asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, a[%c2:%c3], %0" : "+v"(acc) : "v"(w), "i"(IDX), "i"(IDX + 3));
+}
+
+// ==== what the split3 projection kernels (gemm_x3.hip, gemm_x3t.hip) share outside their K loops ==================================================
+// one 32-feature block of the lane's row (fp32, C-layout order) -> bf16 hi / lo planes
+__device__ __forceinline__ void store_block_planes(b16::u16* hrow, b16::u16* lrow, const float (&v)[16], int lh, bool ok) {
+  float hi[16], lo[16];
+#pragma unroll
+  for (int r = 0; r < 16; r += 2) {
+    const unsigned h = pack_bf16(v[r], v[r + 1]);
+    hi[r] = b16::bf_lo(h);
+    hi[r + 1] = b16::bf_hi(h);
+    lo[r] = v[r] - hi[r];
+    lo[r + 1] = v[r + 1] - hi[r + 1];
+  }
+  b16::store_block_bf16(hrow, hi, lh, ok);        // (exact: hi is a bf16 value)
+  b16::store_block_bf16(lrow, lo, lh, ok);
+}
+
+
+// ---- per-head qk constants: [n_heads <= 16][8] RoPE frequencies, then (at float 128) [16] sqrt(cosine-sim scale), parked in 1 KiB of LDS -----
+// RoPE angles come from the token's axial position and the head's frequencies (hardware sin / cos in revolutions) instead of cos / sin
+// tables, and the head's constants from this table: one ds_read_b128 + one ds_read_b32 per head vector, no vector-memory load beside the
+// LDS-DMA ring (hipcc waits vmcnt(0) for an ordinary load issued beside LDS-DMA, draining the ring) and no per-element selects.
+template <class P>
+__device__ __forceinline__ void qk_tab_fill(float* qk_tab, int tid, const P& p) {
+  if (tid < p.n_heads * 8) qk_tab[tid] = p.freq[tid];
+  if (tid < p.n_heads) qk_tab[128 + tid] = sqrtf(p.qk_scale[tid]);
+}
+// the axial position of token `tok`
+__device__ __forceinline__ void token_pos(const float* pos, int tok, float& py, float& px) {
+  py = pos[2 * tok];
+  px = pos[2 * tok + 1];
+  asm volatile("" : "+v"(py), "+v"(px));            // consumed HERE as far as the compiler knows: its wait for the two loads lands before
+}                                                   // the ring starts, not as a vmcnt(0) in the first epilogue
+// cosine-sim norm + RoPE of one q / k head vector (two 32-feature accumulator blocks of the lane's row)
+__device__ __forceinline__ void qk_prep_head(const char* qkc, int head, int lh, f32x16& a0, f32x16& a1, float rs, float eps, float py, float px) {
+  const f32x4 fv = *reinterpret_cast<const f32x4*>(qkc + (head * 8 + 4 * lh) * 4);       // this lane's four frequencies: 4 lh ..
+  const float qsc = *reinterpret_cast<const float*>(qkc + 512 + head * 4);
+  const float fr[4] = {fv[0], fv[1], fv[2], fv[3]};
+  b16::qk_prep_blocks(a0, a1, rs, qsc, eps, py, px, fr);
+}
+
+// ---- workgroup -> (row panel, its share [t_begin, t_end) of the n_tiles): the splits of one panel get ids 8 apart, i.e. the same XCD (one
+// L2 fetches the panel's rows once) ------------------------------------------------------------------------------------------------------------
+struct PanelSplit { int panel, t_begin, t_end; };
+__device__ __forceinline__ PanelSplit panel_split(int n_splits, int n_tiles) {
+  int panel, split;
+  const int n_panels = gridDim.x / n_splits;
+  if ((n_panels & 7) == 0) {
+    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+    panel = (j / n_splits) * 8 + xcd;
+    split = j % n_splits;
+  } else {
+    panel = blockIdx.x % n_panels;
+    split = blockIdx.x / n_panels;
+  }
+  // (integer division by a run-time value goes through the vector unit: hand the uniform results back to scalar registers, or every
+  // address and per-head constant derived from them is vector arithmetic, and the s_load operands of the users become waterfall loops)
+  panel = __builtin_amdgcn_readfirstlane(panel);
+  split = __builtin_amdgcn_readfirstlane(split);
+  return PanelSplit{panel, __builtin_amdgcn_readfirstlane((int)((long)n_tiles * split / n_splits)),
+                    __builtin_amdgcn_readfirstlane((int)((long)n_tiles * (split + 1) / n_splits))};
+}
+
+// n-splits of a panel (host): every workgroup pays the row prologue (about `prologue_weight` tiles' K loops) and then its share of the
+// n-tiles; the grid runs in ceil(workgroups / resident slots) rounds.  The divisor of n_tiles with the smallest rounds x (prologue_weight
+// + tiles per split) wins (ties: fewer splits = fewer redundant prologues).
+static inline int best_n_splits(int panels, int n_tiles, int slots, int prologue_weight) {
+  int best = 1;
+  long best_cost = -1;
+  for (int sp = 1; sp <= n_tiles; ++sp) {
+    if (n_tiles % sp) continue;
+    const long rounds = ((long)panels * sp + slots - 1) / slots;
+    const long cost = rounds * (prologue_weight + n_tiles / sp);
+    if (best_cost < 0 || cost < best_cost) { best = sp; best_cost = cost; }
+  }
+  return best;
 }
 
 }  // namespace x3
