@@ -143,5 +143,53 @@ __device__ __forceinline__ void qk_prep_blocks(f32x16& a0, f32x16& a1, float rs,
   for (int r = 0; r < 16; ++r) a1[r] *= g;
 }
 
+// ---- synchronisation ------------------------------------------------------------------------------------------------------
+#define KD_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+#define KD_BARRIER() asm volatile("s_barrier" ::: "memory")
+
+// s_waitcnt vmcnt(n) for a run-time n (the immediate has to be a constant: one case per value).  CAP = the largest count with a case of its
+// own -- the size of the kernel's jump table; anything above it waits for everything.
+template <int CAP>
+__device__ __forceinline__ void wait_vm_dyn(int n) {
+  static_assert(CAP <= 40, "add the cases");
+  switch (n) {
+#define KD_C(v) case v: if constexpr (v <= CAP) KD_WAIT_VM(v); else KD_WAIT_VM(0); break;
+    KD_C(0) KD_C(1) KD_C(2) KD_C(3) KD_C(4) KD_C(5) KD_C(6) KD_C(7) KD_C(8) KD_C(9) KD_C(10) KD_C(11) KD_C(12) KD_C(13) KD_C(14) KD_C(15)
+    KD_C(16) KD_C(17) KD_C(18) KD_C(19) KD_C(20) KD_C(21) KD_C(22) KD_C(23) KD_C(24) KD_C(25) KD_C(26) KD_C(27) KD_C(28) KD_C(29) KD_C(30) KD_C(31)
+    KD_C(32) KD_C(33) KD_C(34) KD_C(35) KD_C(36) KD_C(37) KD_C(38) KD_C(39) KD_C(40)
+#undef KD_C
+    default: KD_WAIT_VM(0); break;
+  }
+}
+
+// ---- epilogue pieces of the norm -> projection kernels, in the lane that owns the row -------------------------------------------------
+// KD_HEAD_CONSTS(freq, qk_scale, head, lh, fr, qsc): the head's 8 RoPE frequencies and its cosine-sim scale through the SCALAR cache (s_load,
+// lgkmcnt): fr[u] (float[4]) = this lane half's four frequencies, qsc (float) = qk_scale[head].  As ordinary loads (the compiler cannot prove
+// that the kernel's own stores leave them alone, so it will not use s_load by itself) they came back through vmcnt -- and the s_waitcnt
+// vmcnt(0) in front of their first use drained the whole weight ring in flight (and waited for the wave's earlier stores), once per 64 output
+// columns.  `freq + 8 head` has to be 32-byte aligned.
+// A MACRO, not a function: as a __forceinline__ function with the same body hipcc selects the frequencies another way (v_and + v_and_or instead
+// of v_cndmask + v_and_or) and the K = 256 / 512 qkv kernels move by a VGPR, four SGPRs and 4 bytes of scratch (profiles/b16_shared_refactor.md).
+#define KD_HEAD_CONSTS(freq, qk_scale, head, lh, fr, qsc) \
+  { \
+    typedef float f32x8s __attribute__((ext_vector_type(8))); \
+    f32x8s fq; \
+    asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" \
+                 : "=s"(fq), "=s"(qsc) : "s"((freq) + (head) * 8), "s"((qk_scale) + (head)) : "memory"); \
+_Pragma("unroll") \
+    for (int u = 0; u < 4; ++u) (fr)[u] = pick_half(fq[u], fq[4 + u], 0u - (unsigned)(lh)); \
+  }
+
+// GEGLU of one 32-feature block: value accumulators `av`, gate accumulators `ag` (raw: true value = acc * rs) -> v in C-layout order
+__device__ __forceinline__ void geglu_block(const f32x16& av, const f32x16& ag, float rs, float (&v)[16]) {
+  const float rsh = 0.5f * rs;
+#pragma unroll
+  for (int r = 0; r < 16; r += 2) {
+    const f32x2 o = geglu_pair(f32x2{av[r], av[r + 1]} * rsh, f32x2{ag[r], ag[r + 1]} * rs);
+    v[r] = o.x;
+    v[r + 1] = o.y;
+  }
+}
+
 }  // namespace b16
 }  // namespace kd

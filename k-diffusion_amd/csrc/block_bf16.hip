@@ -193,15 +193,9 @@ __global__ __launch_bounds__(512, 1) void attn_block_bf16_kernel(const BArgs p) 
   int off4[4];
 #pragma unroll
   for (int cc = 0; cc < 4; ++cc) off4[cc] = swz128(l31, 2 * cc + lh);
-  // the head's constants through the scalar cache (see gemm_astat_kernel)
-  typedef float f32x8s __attribute__((ext_vector_type(8)));
-  f32x8s fq;
-  float qsc;
-  asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-               : "=s"(fq), "=s"(qsc) : "s"(p.freq + head * 8), "s"(p.qk_scale + head) : "memory");
-  float fr[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) fr[u] = pick_half(fq[u], fq[4 + u], 0u - (unsigned)lh);
+  // the head's constants, once for the k and the q pass
+  float fr[4], qsc;
+  KD_HEAD_CONSTS(p.freq, p.qk_scale, head, lh, fr, qsc)
   const float sqs = sqrtf(qsc);
 
   bf16x8 qf[4];
@@ -414,26 +408,14 @@ __global__ __launch_bounds__(512, 1) void proj_block_bf16_kernel(const UArgs p) 
     if (kk == SPP - 1) {
       if (EPI == KD_EPI_GEGLU) {                        // value block acc[0], gate block acc[1] (gemm_astat_kernel's epilogue)
         float v[16];
-        const float rsh = 0.5f * rs;
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const f32x2 o = geglu_pair(f32x2{acc[0][r], acc[0][r + 1]} * rsh, f32x2{acc[1][r], acc[1][r + 1]} * rs);
-          v[r] = o.x;
-          v[r + 1] = o.y;
-        }
+        geglu_block(acc[0], acc[1], rs, v);
         store_block_bf16(crow + 32 * pass, v, lh, true);
       } else {                                          // one 64-column vector of q, k or v: dims 0..31 in acc[0], 32..63 in acc[1]
         const int vec = NPASS * slice + pass;
         const int which = vec / p.n_heads, head = vec - which * p.n_heads;
         if (which < 2) {
-          typedef float f32x8s __attribute__((ext_vector_type(8)));
-          f32x8s fq;
-          float qsc;
-          asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                       : "=s"(fq), "=s"(qsc) : "s"(p.freq + head * 8), "s"(p.qk_scale + head) : "memory");
-          float fr[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) fr[u] = pick_half(fq[u], fq[4 + u], 0u - (unsigned)lh);
+          float fr[4], qsc;
+          KD_HEAD_CONSTS(p.freq, p.qk_scale, head, lh, fr, qsc)
           qk_prep_blocks(acc[0], acc[1], rs, sqrtf(qsc), p.eps, py, px, fr);
         } else {
 #pragma unroll

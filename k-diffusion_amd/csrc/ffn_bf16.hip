@@ -30,9 +30,6 @@ struct FArgs {
   const u16* Att; const char* Wo;   // fused out projection in front of the block (round 3, width 128): X <- X + Att Wo^T first; NULL = none
 };
 
-#define KD_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define KD_BARRIER() asm volatile("s_barrier" ::: "memory")
-
 extern unsigned long long* g_clk;                     // gemm_bf16.hip (kd_prof_clock_buffer)
 __device__ __forceinline__ void wait_vm_count(int n) {      // s_waitcnt vmcnt(n) for the few run-time values the half-unit ring needs
   if (n >= 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");

@@ -176,13 +176,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_wstat_kernel(const GArgs p) {
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
           float v[16];
-          const float rsh = 0.5f * rs;
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) {
-            const f32x2 o = geglu_pair(f32x2{acc[2 * jj][r], acc[2 * jj][r + 1]} * rsh, f32x2{acc[2 * jj + 1][r], acc[2 * jj + 1][r + 1]} * rs);
-            v[r] = o.x;
-            v[r + 1] = o.y;
-          }
+          geglu_block(acc[2 * jj], acc[2 * jj + 1], rs, v);
           const int nb = n0 + 32 * jj;
           store_block_bf16(crow + min(nb, p.N - 32), v, lh, st_ok && nb < p.N);
         }
@@ -192,16 +186,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_wstat_kernel(const GArgs p) {
           const int vec = (n0 >> 6) + vv;                       // (q|k|v, head) vector index of these 64 columns
           const int which = vec / p.n_heads, head = vec - which * p.n_heads;
           if (which < 2) {
-            // per-head constants through the scalar cache (see the astat kernel: as vector loads they sit behind a vmcnt(0) that
-            // also waits for this wave's earlier stores)
-            typedef float f32x8s __attribute__((ext_vector_type(8)));
-            f32x8s fq;
-            float qsc;
-            asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                         : "=s"(fq), "=s"(qsc) : "s"(p.freq + head * 8), "s"(p.qk_scale + head) : "memory");
-            float fr[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) fr[u] = pick_half(fq[u], fq[4 + u], 0u - (unsigned)lh);
+            float fr[4], qsc;
+            KD_HEAD_CONSTS(p.freq, p.qk_scale, head, lh, fr, qsc)
             qk_prep_blocks(acc[2 * vv], acc[2 * vv + 1], rs, sqrtf(qsc), p.eps, py, px, fr);
           } else {
 #pragma unroll
@@ -384,21 +370,6 @@ struct TArgs {
   int warm;                 // code warm-up workgroups (kd_common.h)
 };
 
-#define KD_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define KD_BARRIER() asm volatile("s_barrier" ::: "memory")
-
-// s_waitcnt vmcnt(n) for a run-time n (the immediate has to be a constant: one case per value)
-__device__ __forceinline__ void wait_vm_dyn(int n) {
-  switch (n) {
-#define KD_C(v) case v: asm volatile("s_waitcnt vmcnt(" #v ")" ::: "memory"); break;
-    KD_C(0) KD_C(1) KD_C(2) KD_C(3) KD_C(4) KD_C(5) KD_C(6) KD_C(7) KD_C(8) KD_C(9) KD_C(10) KD_C(11) KD_C(12) KD_C(13) KD_C(14) KD_C(15)
-    KD_C(16) KD_C(17) KD_C(18) KD_C(19) KD_C(20) KD_C(21) KD_C(22) KD_C(23) KD_C(24) KD_C(25) KD_C(26) KD_C(27) KD_C(28) KD_C(29) KD_C(30) KD_C(31)
-    KD_C(32) KD_C(33) KD_C(34) KD_C(35) KD_C(36) KD_C(37) KD_C(38) KD_C(39) KD_C(40)
-#undef KD_C
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-
 // DEEP (BMT = 1 only): 4-slot ring, one workgroup per CU -- for grids of at most one tile per CU (the level-2 shapes: 8192 rows),
 // where the second workgroup of the 2-slot form does not exist and every K step would wait a full L2 round trip for its blocks.
 // LW (round 4; BMT = 1, DEEP ring, one workgroup per CU): LOADER WAVES as in csrc/gemm_x3r.hip.  The level-2 shapes (8192 rows: one tile per
@@ -507,10 +478,10 @@ __global__ __launch_bounds__(LW ? 512 : 256 * BMT, (BMT == 1 && (!DEEP || LW)) ?
 #pragma unroll
       for (int kt = 0; kt < NSTG - 1; ++kt)
         if (kt < nk) issue(kt);
-      wait_vm_dyn((4 + WPC) * min(NSTG - 2, nk - 1));            // step 0 in
+      wait_vm_dyn<40>((4 + WPC) * min(NSTG - 2, nk - 1));            // step 0 in
       KD_BARRIER();
       for (int kt = 0; kt < nk; ++kt) {
-        wait_vm_dyn(kt + 2 <= nk - 1 ? 4 + WPC : 0);              // step kt + 1 in; step kt + 2 may stay in flight
+        wait_vm_dyn<40>(kt + 2 <= nk - 1 ? 4 + WPC : 0);              // step kt + 1 in; step kt + 2 may stay in flight
         KD_BARRIER();                                            // mid step kt: the compute waves are done with step kt - 1, whose slot takes step kt + 3
         if (kt + NSTG - 1 < nk) issue(kt + NSTG - 1);
       }
@@ -562,7 +533,7 @@ __global__ __launch_bounds__(LW ? 512 : 256 * BMT, (BMT == 1 && (!DEEP || LW)) ?
       if (kt < nk) issue(kt);
   }
   for (int kt = 0; !LW && kt < nk; ++kt) {
-    wait_vm_dyn((4 + WPC) * min(NSTG - 2, nk - 1 - kt));      // the steps requested after kt may stay in flight
+    wait_vm_dyn<40>((4 + WPC) * min(NSTG - 2, nk - 1 - kt));      // the steps requested after kt may stay in flight
     KD_BARRIER();                 // every wave's pieces of step kt are in; everyone is done reading the slot refilled next
     if (kt + NSTG - 1 < nk) issue(kt + NSTG - 1);
     if (HAS_R && kt == max(nk - 2, 0)) {
@@ -876,7 +847,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_astat_kernel(
           if (nt > 0 && ks + 1 <= PDIST) allow += NST;
           if (nt > 1 && ks + 1 + NK <= PDIST) allow += NST;
         }
-        wait_vm_dyn(allow);
+        wait_vm_dyn<40>(allow);
       }
       KD_BARRIER();                      // every wave's share of block s is in; everyone is done reading slot (s-1) % NSTG
       if (s + PDIST < total) issue(s + PDIST);
@@ -906,13 +877,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_astat_kernel(
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
         float v[16];
-        const float rsh = 0.5f * rs;
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const f32x2 o = geglu_pair(f32x2{acc[2 * jj][r], acc[2 * jj][r + 1]} * rsh, f32x2{acc[2 * jj + 1][r], acc[2 * jj + 1][r + 1]} * rs);
-          v[r] = o.x;
-          v[r + 1] = o.y;
-        }
+        geglu_block(acc[2 * jj], acc[2 * jj + 1], rs, v);
         store_block_bf16(crow + n0 + 32 * jj, v, lh, ok);
       }
     } else if (EPI == KD_EPI_QKV) {
@@ -921,18 +886,8 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_astat_kernel(
         const int vec = (n0 >> 6) + vv;
         const int which = vec / p.n_heads, head = vec - which * p.n_heads;
         if (which < 2) {
-          // The head's 8 RoPE frequencies and its cosine-sim scale through the SCALAR cache (s_load, lgkmcnt).  As ordinary loads
-          // (the compiler cannot prove that the kernel's own stores leave them alone, so it will not use s_load by itself) they
-          // came back through vmcnt -- and the s_waitcnt vmcnt(0) in front of their first use drained the whole weight ring in
-          // flight, once per 64 output columns.
-          typedef float f32x8s __attribute__((ext_vector_type(8)));
-          f32x8s fq;
-          float qsc;
-          asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                       : "=s"(fq), "=s"(qsc) : "s"(p.freq + head * 8), "s"(p.qk_scale + head) : "memory");
-          float fr[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) fr[u] = pick_half(fq[u], fq[4 + u], 0u - (unsigned)lh);
+          float fr[4], qsc;
+          KD_HEAD_CONSTS(p.freq, p.qk_scale, head, lh, fr, qsc)
           qk_prep_blocks(acc[2 * vv], acc[2 * vv + 1], rs, sqrtf(qsc), p.eps, py, px, fr);
         } else {
 #pragma unroll
@@ -1348,15 +1303,24 @@ extern "C" int kd_prof_clock_buffer(void* dev_ptr) {
   return KD_OK;
 }
 
+// blocks of the packed image: n-tiles (GEGLU, bit 0 of `geglu`: 64 outputs a tile) x k-steps
+static void bf16_tiling(int N, int K, int geglu, int* n_tiles, int* nk) {
+  const int ncol = (geglu & 1) ? 64 : 128;
+  *n_tiles = (N + ncol - 1) / ncol;
+  *nk = (K + b16::WKS - 1) / b16::WKS;
+}
+
 extern "C" long long kd_packed_weight_bytes_bf16(int N, int K, int geglu) {
   if (N <= 0 || K <= 0) return 0;
-  const long n_tiles = (N + ((geglu & 1) ? 64 : 128) - 1) / ((geglu & 1) ? 64 : 128), nk = (K + b16::WKS - 1) / b16::WKS;
-  return n_tiles * nk * (long long)b16::WBLK;
+  int n_tiles, nk;
+  bf16_tiling(N, K, geglu, &n_tiles, &nk);
+  return (long long)n_tiles * nk * b16::WBLK;
 }
 
 extern "C" int kd_pack_weight_bf16(const float* W, void* out, int N, int K, int geglu, void* stream) {
   if (!W || !out || N <= 0 || K <= 0 || geglu < 0 || geglu > 3) return fail(KD_EINVAL, "kd_pack_weight_bf16: bad arguments");
-  const int n_tiles = (N + ((geglu & 1) ? 64 : 128) - 1) / ((geglu & 1) ? 64 : 128), nk = (K + b16::WKS - 1) / b16::WKS;
+  int n_tiles, nk;
+  bf16_tiling(N, K, geglu, &n_tiles, &nk);
   const long total = (long)n_tiles * nk * b16::WROWS * 8;
   hipLaunchKernelGGL(b16::pack_weight_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W,
                      reinterpret_cast<char*>(out), N, K, geglu, n_tiles, nk);

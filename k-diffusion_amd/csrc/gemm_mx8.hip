@@ -57,16 +57,6 @@ __device__ __forceinline__ void glds16(const void* src, void* dst) {
 
 __device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 
-__device__ __forceinline__ void wait_vm_dyn8(int n) {
-  switch (n) {
-#define KD_C(v) case v: asm volatile("s_waitcnt vmcnt(" #v ")" ::: "memory"); break;
-    KD_C(0) KD_C(1) KD_C(2) KD_C(3) KD_C(4) KD_C(5) KD_C(6) KD_C(7) KD_C(8) KD_C(9) KD_C(10) KD_C(11) KD_C(12) KD_C(13) KD_C(14) KD_C(15)
-    KD_C(16) KD_C(17) KD_C(18) KD_C(19) KD_C(20) KD_C(21) KD_C(22) KD_C(23) KD_C(24) KD_C(25) KD_C(26) KD_C(27) KD_C(28) KD_C(29) KD_C(30) KD_C(31)
-#undef KD_C
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-
 // NK64 = K / 64 (4 or 8).  128-row panels (4 waves), two workgroups per CU, n-splits of a panel on one XCD: gemm_astat_kernel's schedule.
 // C8OUT (EPI_GEGLU): the hidden activation leaves as the NEXT fp8 product's A operand -- e4m3 rows + one power-of-two scale per (row, 32
 // features), the same rule as the activations above -- instead of bf16: kd_gemm_mx8's tiled form (down projection) takes it by LDS-DMA.
@@ -217,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_astat_kernel(const MArgs p) {
   unsigned* wsl = reinterpret_cast<unsigned*>(smem + NSTG * WBLK + NWV * K * 4);
   for (int i = tid; i < n_tiles * 32; i += 256) wsl[i] = p.Ws[(size_t)nt_begin * 32 + i];
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  asm volatile("s_barrier" ::: "memory");              // every wave has taken its rows out of the slot it borrowed; the scale bytes are in
+  KD_BARRIER();                                        // every wave has taken its rows out of the slot it borrowed; the scale bytes are in
 #pragma unroll
   for (int s = 0; s < PDIST; ++s)
     if (s < total) issue(s);
@@ -247,9 +237,9 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_astat_kernel(const MArgs p) {
           if (nt > 0 && kb + 1 <= PDIST) allow += NST;
           if (nt > 1 && kb + 1 + NKB <= PDIST) allow += NST;
         }
-        wait_vm_dyn8(allow);
+        wait_vm_dyn<31>(allow);
       }
-      asm volatile("s_barrier" ::: "memory");
+      KD_BARRIER();
       if (s + PDIST < total) issue(s + PDIST);
       const char* st = smem + (s % NSTG) * WBLK + rd;
       i32x8 wf[2][4];
@@ -276,13 +266,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_astat_kernel(const MArgs p) {
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
         float v[16];
-        const float rsh = 0.5f * rs;
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const f32x2 o = geglu_pair(f32x2{acc[2 * jj][r], acc[2 * jj][r + 1]} * rsh, f32x2{acc[2 * jj + 1][r], acc[2 * jj + 1][r + 1]} * rs);
-          v[r] = o.x;
-          v[r + 1] = o.y;
-        }
+        geglu_block(acc[2 * jj], acc[2 * jj + 1], rs, v);
         if constexpr (C8OUT) {
           // v[4 g + e] = feature 8 g + 4 lh + e of the block: the block's maximum over both lanes of the row, then 16 e4m3 bytes per lane --
           // after the half-wave exchange lane half 0 holds features 0..15, lane half 1 features 16..31: one 16-byte store each
@@ -316,14 +300,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_astat_kernel(const MArgs p) {
         const int vec = (n0 >> 6) + vv;
         const int which = vec / p.n_heads, head = vec - which * p.n_heads;
         if (which < 2) {
-          typedef float f32x8s __attribute__((ext_vector_type(8)));
-          f32x8s fq;
-          float qsc;
-          asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                       : "=s"(fq), "=s"(qsc) : "s"(p.freq + head * 8), "s"(p.qk_scale + head) : "memory");
-          float fr[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) fr[u] = pick_half(fq[u], fq[4 + u], 0u - (unsigned)lh);
+          float fr[4], qsc;
+          KD_HEAD_CONSTS(p.freq, p.qk_scale, head, lh, fr, qsc)
           qk_prep_blocks(acc[2 * vv], acc[2 * vv + 1], rs, sqrtf(qsc), p.eps, py, px, fr);
         } else {
 #pragma unroll
@@ -437,7 +415,7 @@ __global__ __launch_bounds__(256, DEEP ? 1 : 2) void gemm_mx8_tiled_kernel(const
     if (NSTG == 2 || kt + 1 >= NKB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else if (kt + 2 >= NKB) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");
+    KD_BARRIER();
     if (kt + NSTG - 1 < NKB) issue(kt + NSTG - 1);
     if (HAS_R && kt == (NKB >= 2 ? NKB - 2 : 0)) {
 #pragma unroll
