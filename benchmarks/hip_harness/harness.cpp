@@ -788,6 +788,49 @@ static void run_optim_case() {
   printf("optim 64 Mi elements, norm + fused step: %8.1f us  %6.2f TB/s (44 B / element)\n", us, 44.0 * n / us * 1e-6);
 }
 
+// The weight gradient dW = G^T (A * row_scale) (csrc/wgrad_f32.hip) in its bf16 arithmetic (selector 2): both operands rounded to bf16 after
+// their prologue, fp32 accumulate, against the fp64 product of the operands rounded here, on a sample of output entries; then the three
+// arithmetics timed on the same shape.
+static void run_wgrad_case(const char* name, int M, int N, int K) {
+  if (!want(name)) return;
+  const auto G = randn((size_t)M * N), A = randn((size_t)M * K);
+  std::vector<float> rs(M);
+  for (int m = 0; m < M; ++m) rs[m] = 0.5f + (float)(m % 7) * 0.125f;
+  const int tiles = ((N + 127) / 128) * ((K + 127) / 128);
+  int nchunk = std::max(1, std::min(std::min((512 + tiles - 1) / tiles, (M + 127) / 128), 65535));
+  const int chunk = (((M + nchunk - 1) / nchunk + 31) / 32) * 32;
+  nchunk = (M + chunk - 1) / chunk;
+  DevBuf<float> dG(G.size()), dA(A.size()), drs(M), ws((size_t)nchunk * N * K), out((size_t)N * K);
+  dG.up(G); dA.up(A); drs.up(rs);
+  auto launch = [&](int arith) {
+    return kd_wgrad_f32(dG.p, KD_WG_PLAIN, dA.p, KD_WG_PLAIN, 0, M, N, K, 0, 0, 0, 0, 0, drs.p, nullptr, 0, 1, nullptr, 0, arith, chunk, nchunk, ws.p,
+                        out.p, 0);
+  };
+  if (launch(2) != 0) {
+    printf("%s: FAILED to launch: %s\n", name, kd_last_error());
+    ++g_fail;
+    return;
+  }
+  HIPCHK(hipDeviceSynchronize());
+  const std::vector<float> got = out.down();
+  double err = 0, ref_max = 0;
+  for (int s = 0; s < 64; ++s) {
+    const int n = (int)((size_t)s * 2654435761u % N), k = (int)((size_t)s * 40503u % K);
+    double acc = 0;
+    for (int m = 0; m < M; ++m) acc += (double)bf2f(f2bf(G[(size_t)m * N + n])) * (double)bf2f(f2bf(A[(size_t)m * K + k] * rs[m]));
+    err = std::max(err, fabs(got[(size_t)n * K + k] - acc));
+    ref_max = std::max(ref_max, fabs(acc));
+  }
+  const bool ok = err <= 2e-6 * ref_max * sqrt((double)M / 64 + 1);    // fp32 accumulation of exact products over M rows
+  printf("%s M=%d N=%d K=%d bf16 operands: max |err| %.2e of %.2e vs fp64 of the rounded operands: %s\n", name, M, N, K, err, ref_max,
+         ok ? "ok" : "FAILED");
+  if (!ok) ++g_fail;
+  for (int arith : {1, 2}) {
+    const float us = time_us([&] { launch(arith); }, 10);
+    printf("%s %s: %8.1f us  %7.2f TFLOP/s of products\n", name, arith == 1 ? "split3" : "bf16  ", us, 2.0 * M * N * K / us * 1e-6);
+  }
+}
+
 int main(int argc, char** argv) {
   if (argc > 1) g_filter = argv[1];
   printf("libkdiff_hip version %d\n", kd_version());
@@ -819,6 +862,9 @@ int main(int argc, char** argv) {
   run_mx8_case("mx8 L2 ff", 8192, 512, 1536, 256);
   run_mx8_case("mx8 ragged ff", 1000, 256, 768, 50);
   run_optim_case();
+  run_wgrad_case("wgrad L0 up", 131072, 768, 128);
+  run_wgrad_case("wgrad L2 down", 8192, 512, 1536);
+  run_wgrad_case("wgrad ragged", 4128 + 17, 200, 72);
   if (want("astat")) {
     const GemmCase ca[] = {
         {"astat L1 qkv", 32768, 768, 256, KD_EPI_QKV, 1, 1024, 4},

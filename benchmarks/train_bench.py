@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Cost of a training step's gradients (``Denoiser.loss`` + backward into every parameter, models/vjp.py) against one ``forward`` of the same
 denoiser, and the peak device memory of each.  Synthetic weights (synth.py), ``eval()``, fp32 split3 arithmetic by default; with
-``--dropout`` the training step runs in training mode with ``model.enable_dropout()`` at the config's rates (``--dropout-rate`` sets them).
+``--dropout`` the training step runs in training mode with ``model.enable_dropout()`` at the config's rates (``--dropout-rate`` sets them);
+``--wgrad bf16`` runs the weight-gradient GEMMs on bf16 operands (``model.set_wgrad_arithmetic``).
 
-    python benchmarks/train_bench.py [--config configs/config_oxford_flowers.json] [--batches 1 8 32] [--iters 3] [--dropout] [--dropout-rate 0 0 0.1]
+    python benchmarks/train_bench.py [--config configs/config_oxford_flowers.json] [--batches 1 8 32] [--iters 3] [--dropout] [--dropout-rate 0 0 0.1] [--wgrad bf16]
 
 Prints one JSON line per batch size ({"batch", "forward_ms", "train_ms", "ratio", "forward_peak_mib", "train_peak_mib"}).  Times are host
 clocks around work that ends in a device synchronise, after one warm-up call of every shape; the peaks are torch.cuda.max_memory_allocated
@@ -51,6 +52,8 @@ def main():
                                                              "(the forward still runs in eval())")
     ap.add_argument("--dropout-rate", type=float, nargs="+", default=None, help="per-level dropout rates (one value: every level) in place "
                                                                                  "of the config's")
+    ap.add_argument("--wgrad", choices=["bf16"], default=None, help="model.set_wgrad_arithmetic: bf16 weight-gradient GEMMs (default: the "
+                                                                    "backward pass's rule)")
     args = ap.parse_args()
     os.environ.setdefault("KDIFF_GEMM", "split3")
     raw = json.load(open(args.config))
@@ -63,6 +66,7 @@ def main():
     model = model.to("cuda")
     if args.dropout:
         model.enable_dropout()
+    model.set_wgrad_arithmetic(args.wgrad)
     den = K.Denoiser(model, mc["sigma_data"])
     nc = cfg.get("dataset", {}).get("num_classes", 0)
     shape = (mc["input_channels"], *mc["input_size"])
@@ -84,7 +88,7 @@ def main():
             den.loss(x, noise, sig, **kw).mean().backward()
         t_f, t_t = timed(fwd, args.iters), timed(train, args.iters)
         m_f, m_t = peak_mib(fwd), peak_mib(train)
-        print(json.dumps({"config": os.path.basename(args.config), "mode": os.environ["KDIFF_GEMM"], "batch": B,
+        print(json.dumps({"config": os.path.basename(args.config), "mode": os.environ["KDIFF_GEMM"], "batch": B, "wgrad": args.wgrad,
                           "dropout": mc["dropout_rate"] if args.dropout else None, "forward_ms": round(t_f, 3),
                           "train_ms": round(t_t, 3), "ratio": round(t_t / t_f, 2), "forward_peak_mib": round(m_f, 1),
                           "train_peak_mib": round(m_t, 1)}), flush=True)

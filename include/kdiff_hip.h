@@ -463,8 +463,11 @@ int kd_precond_vjp_f32(const float* g, int g_coef, const float* h, int h_coef, c
  *                        2gh x 2gw x chan, ph = pw = 2) or the NCHW patch gather (image chan x gh*ph x gw*pw); gathered columns are ordered
  *                        (py, px, channel).  A's prologue: a_geglu (A holds [value | gate] rows of 2K, the operand is value * gelu(gate)),
  *                        row_scale[m], col_scale[(m / rows_per_sample) * col_stride + k].  The rows are cut into nchunk chunks of chunk_rows
- *                        (chunk_rows * nchunk >= M); ws holds nchunk * N * K floats.  split3: bf16 hi / lo operands, 3 MFMAs per product, fp32
- *                        accumulate (the backward pass's rule under split3 / bf16 / fp8); 0: fp32 FMAs (exact).
+ *                        (chunk_rows * nchunk >= M); ws holds nchunk * N * K floats.  split3 selects the arithmetic.  1: bf16 hi / lo operands,
+ *                        3 MFMAs per product, fp32 accumulate (the backward pass's rule under split3 / bf16 / fp8); 0: fp32 FMAs (exact);
+ *                        2: bf16 operands, 1 MFMA per product, fp32 accumulate -- each operand element is rounded to bf16 (nearest even)
+ *                        after its whole prologue (gather, GEGLU, dropout mask, row_scale, col_scale), where a Linear backward under
+ *                        torch.autocast(bfloat16) rounds it; opt-in (ops.wgrad(bf16=True)), 128 x 128 output tiles.  Other values: KD_EINVAL.
  *   kd_row_rrms_f32    : rrms[r] = rsqrt(mean(x[r, :]^2) + eps).
  *   kd_colsum_f32      : out[s, j] (+)= sum over rows r of segment s (rows_per_seg rows each) of a[r, j] * (b[r, j] - b2[r, j]) * row_scale[r];
  *                        b, b2, row_scale may be NULL.  ws holds rows / 64 (rounded up per segment) * cols floats.

@@ -3,7 +3,9 @@
 //
 //   kd_wgrad_f32          dW[N, K] (+)= alpha * sum_m G[m, n] * A[m, k]: the weight gradient of a projection, both operands stored
 //                         M-major.  split3 (the backward pass's rule under split3 / bf16 / fp8): every operand split into bf16 hi + lo in
-//                         the staging pass, 3 bf16 MFMAs per product (hi hi, hi lo, lo hi), fp32 accumulate; exact: fp32 FMAs.  Either operand may be read through the 2x2 token-merge or the NCHW patch gather; A may be
+//                         the staging pass, 3 bf16 MFMAs per product (hi hi, hi lo, lo hi), fp32 accumulate; exact: fp32 FMAs; bf16 (opt-in,
+//                         the reference's --mixed-precision bf16 Linear backward): both operands rounded to bf16 after their whole
+//                         prologue, 1 bf16 MFMA per product, fp32 accumulate.  Either operand may be read through the 2x2 token-merge or the NCHW patch gather; A may be
 //                         scaled per row (RMSNorm rrms) and per (sample, column) (AdaRMSNorm scale) or be the GEGLU of [value | gate]
 //                         rows, so normalised rows are never written to memory just to be read back.
 //   kd_wgrad_drop_f32     the same with A's plain rows under a dropout mask (the FF hidden's dW_down = G^T (mask * geglu(U))): the
@@ -22,12 +24,14 @@
 #include "x3_common.h"
 
 #include <cmath>
+#include <cstdint>
 
 namespace kd {
 
 namespace {
 
 enum { WG_PLAIN = 0, WG_MERGE2x2 = 1, WG_PATCH_NCHW = 2 };
+enum { WG_EXACT = 0, WG_SPLIT3 = 1, WG_BF16 = 2 };      // the arithmetic selector (the C ABI's split3 argument)
 
 struct WgOperand {
   const float* p;
@@ -39,6 +43,7 @@ struct WgOperand {
   int col_stride;        // 0: one shared row of col_scale; else per sample (rows_per_sample rows each)
   const unsigned* bits;  // A only, DROP kernels: the dropout mask of the plain [M, cols] operand (dropout_f32.hip), kept elements times drop_scale
   float drop_scale;
+  int wide;              // bf16 kernel: plain rows, cols % 4 == 0 and 16-byte aligned pointers: 4 columns per load
 };
 
 struct WgGeom {
@@ -209,6 +214,151 @@ __global__ __launch_bounds__(256) void wgrad_x3_partial_kernel(WgOperand G, WgOp
   }
 }
 
+// ---- weight gradient, bf16 operands on the matrix cores: 128 (n) x 128 (k) output tile per workgroup of 4 waves (2 x 2 of 64 x 64, four
+// 32 x 32 accumulators each), 32 rows of m per LDS step, ONE MFMA per product.  Every operand element is rounded to bf16 (nearest even) after
+// its whole prologue (gather, GEGLU, dropout mask, row and column scale).  Staging of its own: waves 0, 1 stage the G panel and waves 2, 3
+// the A panel, a lane holding 4 adjacent columns x 8 consecutive rows -- one 16-byte load per row where the operand's rows are plain
+// (WgOperand::wide), element loads through wg_load otherwise -- and writing each column's 8 rows as ONE 16-byte store of an m-contiguous
+// image, so each MFMA fragment is one ds_read_b128.  Image: 4 columns x 32 m (64 bytes each) + 16 bytes of padding per column group
+// (272 bytes): the 8 lanes of a ds_write_b128 group (8 column groups, 272 bytes apart) and the 16 lanes of a ds_read_b128 group land on
+// distinct banks.  Two images per operand: the next panel is loaded before the current panel's MFMAs and staged after them into the other
+// buffer, one barrier per step.
+constexpr int BT = 128, BR = 32;                   // output tile edge; rows of m per step
+constexpr int BGRP = 136;                          // image stride of a 4-column group in bf16 (272 bytes)
+constexpr int BIMG = (BT / 4) * BGRP;              // one operand image in bf16
+
+__device__ __forceinline__ long wg_sample(long m, int rows_per_sample) {
+  return (m >> 31) ? m / rows_per_sample : (long)((unsigned)m / (unsigned)rows_per_sample);
+}
+
+// rows m0 .. m0 + 7 (the caller's panel row + 8 g) of columns col .. col + 3 (the tile's first column + 4 cq), zero outside the chunk and the matrix
+template <bool DROP>
+__device__ __forceinline__ void b16_load(const WgOperand& o, const WgGeom& q, long m0, long m_end, int col, int cols, float (&v)[8][4]) {
+  if (o.wide) {
+    const bool in_c = col < cols;                  // cols % 4 == 0: the 4 columns are inside together
+    f32x4 cs{1.f, 1.f, 1.f, 1.f};
+    long cs_sample = -1;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const long m = m0 + i;
+      f32x4 x{0.f, 0.f, 0.f, 0.f};
+      if (in_c && m < m_end) {
+        if (o.geglu) {
+          const float* r = o.p + m * 2 * (long)o.cols + col;
+          const f32x4 val = *reinterpret_cast<const f32x4*>(r), gate = *reinterpret_cast<const f32x4*>(r + o.cols);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) x[j] = val[j] * gelu_erf(gate[j]);
+        } else {
+          x = *reinterpret_cast<const f32x4*>(o.p + m * o.cols + col);
+        }
+        if (DROP) {
+          const long e = m * o.cols + col;          // e % 4 == 0: the 4 bits share a word
+          const unsigned nib = o.bits[e >> 5] >> (e & 31);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) x[j] *= ((nib >> j) & 1u) ? o.drop_scale : 0.0f;
+        }
+        if (o.row_scale) {
+          const float rs = o.row_scale[m];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) x[j] *= rs;
+        }
+        if (o.col_scale) {
+          const long sm = o.col_stride ? wg_sample(m, q.rows_per_sample) : 0;
+          if (sm != cs_sample) {
+            cs = *reinterpret_cast<const f32x4*>(o.col_scale + sm * o.col_stride + col);
+            cs_sample = sm;
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) x[j] *= cs[j];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[i][j] = x[j];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const long m = m0 + i;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[i][j] = (m < m_end && col + j < cols) ? wg_load<DROP>(o, q, m, col + j) : 0.f;
+    }
+  }
+}
+
+// column group cq, rows 8g .. 8g + 7 of one operand image: the transpose happens here
+__device__ __forceinline__ void b16_stage(const float (&v)[8][4], b16::u16* img, int cq, int g) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    *reinterpret_cast<b16::u32x4*>(img + cq * BGRP + j * BR + g * 8) =
+        b16::u32x4{b16::pack_bf16(v[0][j], v[1][j]), b16::pack_bf16(v[2][j], v[3][j]), b16::pack_bf16(v[4][j], v[5][j]), b16::pack_bf16(v[6][j], v[7][j])};
+}
+
+__device__ __forceinline__ b16::bf16x8 b16_frag(const b16::u16* img, int row, int k8) {
+  return __builtin_bit_cast(b16::bf16x8, *reinterpret_cast<const b16::u32x4*>(img + (row >> 2) * BGRP + (row & 3) * BR + k8));
+}
+
+template <bool DROP>
+__global__ __launch_bounds__(256) void wgrad_b16_partial_kernel(WgOperand G, WgOperand A, WgGeom q, long M, int N, int K, int chunk_rows,
+                                                                float* __restrict__ ws) {
+  __shared__ __attribute__((aligned(16))) b16::u16 img[2][2][BIMG];     // [buffer][G^T, A^T]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int wn = wave & 1, wk = wave >> 1;
+  const int n0 = blockIdx.x * BT, k0 = blockIdx.y * BT;
+  const long m_begin = (long)blockIdx.z * chunk_rows;
+  const long m_end = min(M, m_begin + chunk_rows);
+  const int side = wave >> 1;                      // waves 0, 1 stage G, waves 2, 3 stage A
+  const int cq = threadIdx.x & 31, g = (threadIdx.x >> 5) & 3;
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  float v[8][4];
+  auto load = [&](long m0) {
+    if (side) b16_load<DROP>(A, q, m0 + g * 8, m_end, k0 + 4 * cq, K, v);
+    else b16_load<false>(G, q, m0 + g * 8, m_end, n0 + 4 * cq, N, v);
+  };
+  load(m_begin);
+  b16_stage(v, img[0][side], cq, g);
+  __syncthreads();
+  int buf = 0;
+  for (long m0 = m_begin; m0 < m_end; m0 += BR, buf ^= 1) {
+    const bool more = m0 + BR < m_end;
+    if (more) load(m0 + BR);
+#pragma unroll
+    for (int ks = 0; ks < BR / 16; ++ks) {
+      const int k8 = ks * 16 + lh * 8;
+      b16::bf16x8 gf[2], af[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        gf[i] = b16_frag(img[buf][0], wn * 64 + i * 32 + l31, k8);
+        af[i] = b16_frag(img[buf][1], wk * 64 + i * 32 + l31, k8);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gf[i], af[j], acc[i][j], 0, 0, 0);
+    }
+    if (more) b16_stage(v, img[buf ^ 1][side], cq, g);
+    __syncthreads();
+  }
+  float* out = ws + (long)blockIdx.z * N * K;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int k = k0 + wk * 64 + j * 32 + l31;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int n = n0 + wn * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (n < N && k < K) out[(long)n * K + k] = acc[i][j][r];
+      }
+    }
+}
+
 // chunks added in ascending order; alpha (a device scalar or NULL) scales the sum; accumulate adds the result to dW
 __global__ __launch_bounds__(256) void chunk_reduce_kernel(const float* __restrict__ ws, int nchunk, long n, const float* alpha, int accumulate,
                                                            float* __restrict__ out) {
@@ -370,7 +520,8 @@ int launch_dropout_bits(unsigned* bits, long long n, const long long* key, unsig
 
 static int wgrad(const char* what, const float* G, int g_mode, const float* A, int a_mode, int a_geglu, long long M, int N, int K, int gh, int gw, int ph,
                  int pw, int chan, const float* row_scale, const float* col_scale, int col_stride, int rows_per_sample, const float* alpha,
-                 int accumulate, int split3, int chunk_rows, int nchunk, float* ws, float* dW, const unsigned* bits, float drop_scale, hipStream_t s) {
+                 int accumulate, int arith, int chunk_rows, int nchunk, float* ws, float* dW, const unsigned* bits, float drop_scale, hipStream_t s) {
+  if (arith < WG_EXACT || arith > WG_BF16) return fail(KD_EINVAL, "%s: arithmetic %d (0 exact, 1 split3, 2 bf16)", what, arith);
   if (!G || !A || !dW || !ws || M <= 0 || N <= 0 || K <= 0 || chunk_rows <= 0 || nchunk <= 0 || nchunk > 65535)
     return fail(KD_EINVAL, "%s: bad arguments", what);
   if ((long long)chunk_rows * nchunk < M) return fail(KD_EINVAL, "%s: %d chunks of %d rows do not cover %lld rows", what, nchunk, chunk_rows, M);
@@ -384,18 +535,24 @@ static int wgrad(const char* what, const float* G, int g_mode, const float* A, i
     if ((g_mode ? N : K) != ph * pw * chan) return fail(KD_EINVAL, "%s: gathered operand has %d columns, expected %d", what, g_mode ? N : K, ph * pw * chan);
   }
   if (col_scale && (rows_per_sample <= 0 || col_stride < 0)) return fail(KD_EINVAL, "%s: bad column scale layout", what);
-  WgOperand go{G, g_mode, N, 0, nullptr, nullptr, 0, nullptr, 0.f};
-  WgOperand ao{A, a_mode, K, a_geglu, row_scale, col_scale, col_stride, bits, drop_scale};
+  const auto aligned16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  const int g_wide = arith == WG_BF16 && g_mode == WG_PLAIN && N % 4 == 0 && aligned16(G);
+  const int a_wide = arith == WG_BF16 && a_mode == WG_PLAIN && K % 4 == 0 && aligned16(A) && (!col_scale || (aligned16(col_scale) && col_stride % 4 == 0));
+  WgOperand go{G, g_mode, N, 0, nullptr, nullptr, 0, nullptr, 0.f, g_wide};
+  WgOperand ao{A, a_mode, K, a_geglu, row_scale, col_scale, col_stride, bits, drop_scale, a_wide};
   WgGeom q{gh, gw, ph, pw, chan, rows_per_sample > 0 ? rows_per_sample : 1};
   {
-    LaunchScope prof(bits ? (split3 ? "wgrad_x3_drop_f32" : "wgrad_drop_f32") : (split3 ? "wgrad_x3_f32" : "wgrad_f32"), 2.0 * (double)M * N * K,
-                     4.0 * (double)M * (N + K), s);
-    const dim3 grid((unsigned)((N + WT - 1) / WT), (unsigned)((K + WT - 1) / WT), (unsigned)nchunk);
+    static const char* const names[3][2] = {{"wgrad_f32", "wgrad_drop_f32"}, {"wgrad_x3_f32", "wgrad_x3_drop_f32"}, {"wgrad_b16_f32", "wgrad_b16_drop_f32"}};
+    LaunchScope prof(names[arith][bits != nullptr], 2.0 * (double)M * N * K, 4.0 * (double)M * (N + K), s);
+    const int tile = arith == WG_BF16 ? BT : WT;
+    const dim3 grid((unsigned)((N + tile - 1) / tile), (unsigned)((K + tile - 1) / tile), (unsigned)nchunk);
     if (bits) {
-      if (split3) hipLaunchKernelGGL(wgrad_x3_partial_kernel<true>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
+      if (arith == WG_BF16) hipLaunchKernelGGL(wgrad_b16_partial_kernel<true>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
+      else if (arith == WG_SPLIT3) hipLaunchKernelGGL(wgrad_x3_partial_kernel<true>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
       else hipLaunchKernelGGL(wgrad_partial_kernel<true>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
     } else {
-      if (split3) hipLaunchKernelGGL(wgrad_x3_partial_kernel<false>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
+      if (arith == WG_BF16) hipLaunchKernelGGL(wgrad_b16_partial_kernel<false>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
+      else if (arith == WG_SPLIT3) hipLaunchKernelGGL(wgrad_x3_partial_kernel<false>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
       else hipLaunchKernelGGL(wgrad_partial_kernel<false>, grid, dim3(256), 0, s, go, ao, q, (long)M, N, K, chunk_rows, ws);
     }
   }

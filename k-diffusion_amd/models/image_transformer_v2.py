@@ -869,6 +869,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         self._fp_hooked = weakref.WeakSet()
         self._fp_sized, self._fp_sizes = (), ()
         self._dropout_on, self._dropout_gen = False, None
+        self.wgrad_arithmetic = None
 
     # ---- bookkeeping ---------------------------------------------------------------------------
     def _ada_norm_modules(self):
@@ -1029,6 +1030,18 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         if generator is not None and not isinstance(generator, torch.Generator):
             raise TypeError(f"enable_dropout: generator must be a torch.Generator or None (got {type(generator)})")
         self._dropout_on, self._dropout_gen = True, generator
+        return self
+
+    def set_wgrad_arithmetic(self, arithmetic=None):
+        """Opt in to bf16 weight gradients in the training loss.  ``None`` (the default): the backward pass's rule (split3, or exact fp32
+        under KDIFF_GEMM=exact).  ``"bf16"``: every weight-gradient GEMM dW = G^T X of ``loss_forward``'s backward rounds both operands to
+        bf16 after their prologue and accumulates in fp32, one MFMA per product (``ops.wgrad(bf16=True)``): a ``Linear`` backward of the
+        reference under ``--mixed-precision bf16``.  Only those GEMMs move: the primal (so the loss), the data-gradient GEMMs, the
+        attention rules, the column sums and the class embedding keep their fp32-grade arithmetic.  Honoured in every KDIFF_GEMM mode.
+        The setting is not part of the state_dict.  Returns the model."""
+        if arithmetic not in (None, "bf16"):
+            raise ValueError(f"ImageTransformerDenoiserModelV2.set_wgrad_arithmetic: {arithmetic!r} (None or 'bf16')")
+        self.wgrad_arithmetic = arithmetic
         return self
 
     def _dropout_applies(self):

@@ -27,7 +27,9 @@ Dropout (``dropout``: the training loss's key, ``enable_dropout``): the primal m
 on g W_out^T, the GEGLU VJP's g_h inside its kernel) and the weight gradient behind it (dW_out reads the masked o, dW_down masks its GEGLU
 prologue).  No mask is stored: every kernel regenerates the bits from (key, site, element).
 Arithmetic: fp32 in every KDIFF_GEMM mode, as the dual pass (split3 GEMMs under ``split3`` / ``bf16`` / ``fp8``, exact fp32 under
-``exact``).  No launch plan is built, read or evicted.
+``exact``).  ``model.set_wgrad_arithmetic("bf16")`` moves the weight-gradient GEMMs alone (every ``ops.wgrad`` of the sink) to bf16 operands
+with fp32 accumulation; the primal, the data-gradient GEMMs, the attention rules and the column sums stay as above, so the loss and the
+input gradient keep their bits.  No launch plan is built, read or evicted.
 """
 import torch
 
@@ -98,6 +100,11 @@ class _Sink:
         self.chain = self.wants(*behind)
         self.cond = cond
         self.dcond = None
+        self.bf16 = model.wgrad_arithmetic == "bf16"
+
+    def wgrad(self, G, A, **kw):
+        """``ops.wgrad`` in the model's weight-gradient arithmetic (``set_wgrad_arithmetic``)."""
+        return ops.wgrad(G, A, bf16=self.bf16, **kw)
 
     def wants(self, *ps):
         return any(id(p) in self.ids for p in ps)
@@ -112,7 +119,7 @@ class _Sink:
         if not (self.chain or self.wants(norm.linear.weight)):
             return
         ds = ops.colsum(gy, x, row_scale=rrms, rows_per_seg=rps)
-        self.put(norm.linear.weight, lambda: ops.wgrad(ds, self.cond))
+        self.put(norm.linear.weight, lambda: self.wgrad(ds, self.cond))
         if self.chain:
             self.dcond = ops.linear(ds, _wt(model, norm.linear.weight), residual=self.dcond)
 
@@ -135,9 +142,9 @@ def _layer_vjp(model, st, grids, x, g, cond, sink=None, drop=None):
     gu = ops.geglu_vjp(u, ops.linear(g, _wt(model, ff.down_proj.weight)), dropout=d_ff)      # g_h = mask (g W_down^T) into the GEGLU VJP
     gy = ops.linear(gu, _wt(model, ff.up_proj.weight))
     if sink is not None:
-        sink.put(ff.down_proj.weight, lambda: ops.wgrad(g, u, geglu=True, dropout=d_ff))      # g^T (mask geglu(u))
+        sink.put(ff.down_proj.weight, lambda: sink.wgrad(g, u, geglu=True, dropout=d_ff))      # g^T (mask geglu(u))
         r = ops.row_rrms(xf, itv2.EPS) if sink.wants(ff.up_proj.weight, ff.norm.linear.weight) or sink.chain else None
-        sink.put(ff.up_proj.weight, lambda: ops.wgrad(gu, xf, row_scale=r, col_scale=s_f, rows_per_sample=rps))
+        sink.put(ff.up_proj.weight, lambda: sink.wgrad(gu, xf, row_scale=r, col_scale=s_f, rows_per_sample=rps))
         sink.ada(model, ff.norm, gy, xf, r, rps)
     g = ops.rms_norm_vjp(xf, gy, s_f, rows_per_sample=rps, add=g)
     if not has_attn:
@@ -150,7 +157,7 @@ def _layer_vjp(model, st, grids, x, g, cond, sink=None, drop=None):
     if d_attn is not None:
         ops.dropout(go, *d_attn, out=go)
     if sink is not None:
-        sink.put(sa.out_proj.weight, lambda: ops.wgrad(g, o))                           # o: already masked by the recomputation
+        sink.put(sa.out_proj.weight, lambda: sink.wgrad(g, o))                           # o: already masked by the recomputation
     _, core, params = itv2.attn_geometry(spec, st.index)
     gq = getattr(ops, core + "_vjp")(prep, go, nh, *params)
     scale = sa.scale.detach().contiguous()
@@ -160,7 +167,7 @@ def _layer_vjp(model, st, grids, x, g, cond, sink=None, drop=None):
     gy = ops.linear(gq, _wt(model, sa.qkv_proj.weight))
     if sink is not None:
         r = ops.row_rrms(x, itv2.EPS) if sink.wants(sa.qkv_proj.weight, sa.norm.linear.weight) or sink.chain else None
-        sink.put(sa.qkv_proj.weight, lambda: ops.wgrad(gq, x, row_scale=r, col_scale=s_a, rows_per_sample=rps))
+        sink.put(sa.qkv_proj.weight, lambda: sink.wgrad(gq, x, row_scale=r, col_scale=s_a, rows_per_sample=rps))
         sink.ada(model, sa.norm, gy, x, r, rps)
     return ops.rms_norm_vjp(x, gy, s_a, rows_per_sample=rps, add=g)
 
@@ -183,17 +190,17 @@ def _mapping_vjp(m, keep, sink, drop=None):
         gu = ops.geglu_vjp(u, ops.linear(dc, _wt(m, blk.down_proj.weight)), dropout=dk)
         gy = ops.linear(gu, _wt(m, blk.up_proj.weight))
         r = ops.row_rrms(c, itv2.EPS)
-        sink.put(blk.down_proj.weight, lambda: ops.wgrad(dc, u, geglu=True, dropout=dk))
-        sink.put(blk.up_proj.weight, lambda: ops.wgrad(gu, c, row_scale=r, col_scale=nscale))
+        sink.put(blk.down_proj.weight, lambda: sink.wgrad(dc, u, geglu=True, dropout=dk))
+        sink.put(blk.up_proj.weight, lambda: sink.wgrad(gu, c, row_scale=r, col_scale=nscale))
         sink.put(blk.norm.scale, lambda: ops.colsum(gy, c, row_scale=r).reshape(-1))
         dc = ops.rms_norm_vjp(c, gy, nscale, add=dc)
     c0 = keep["c_sum"]
     sink.put(mp.in_norm.scale, lambda: ops.colsum(dc, c0, row_scale=ops.row_rrms(c0, itv2.EPS)).reshape(-1))
     dc = ops.rms_norm_vjp(c0, dc, mp.in_norm.scale.detach().contiguous())
-    sink.put(m.time_in_proj.weight, lambda: ops.wgrad(dc, keep["time_ff"]))
-    sink.put(m.aug_in_proj.weight, lambda: ops.wgrad(dc, keep["aug_ff"]))
+    sink.put(m.time_in_proj.weight, lambda: sink.wgrad(dc, keep["time_ff"]))
+    sink.put(m.aug_in_proj.weight, lambda: sink.wgrad(dc, keep["aug_ff"]))
     if m.mapping_cond_in_proj is not None:
-        sink.put(m.mapping_cond_in_proj.weight, lambda: ops.wgrad(dc, keep["mapping_rows"]))
+        sink.put(m.mapping_cond_in_proj.weight, lambda: sink.wgrad(dc, keep["mapping_rows"]))
     if m.class_emb is not None:
         sink.put(m.class_emb.weight, lambda: ops.class_emb_grad(dc, keep["ids"], m.class_emb.weight.shape[0]))
 
@@ -266,7 +273,7 @@ def backward(model, x, sigma, grad_out, aug_cond=None, class_cond=None, mapping_
         gh, gw = grids[0]
         ph, pw = m.patch_size
         r = ops.row_rrms(h, itv2.EPS)
-        sink.put(m.patch_out.proj.weight, lambda: ops.wgrad(g_img, h, gather=("g", ops.nat.WG_PATCH_NCHW), gather_geom=(gh, gw, ph, pw, m.out_channels),
+        sink.put(m.patch_out.proj.weight, lambda: sink.wgrad(g_img, h, gather=("g", ops.nat.WG_PATCH_NCHW), gather_geom=(gh, gw, ph, pw, m.out_channels),
                                                             row_scale=r, col_scale=out_scale))
         sink.put(m.out_norm.scale, lambda: ops.colsum(g, h, row_scale=r).reshape(-1))
     g = ops.rms_norm_vjp(h, g, out_scale)
@@ -282,7 +289,7 @@ def backward(model, x, sigma, grad_out, aug_cond=None, class_cond=None, mapping_
                 skip = merge_in[st.level]
                 _, _, one = _split_consts(m, sp, B, x.device)
                 gh, gw = xs.shape[1:3]
-                sink.put(sp.proj.weight, lambda: ops.wgrad(g, xs, gather=("g", ops.nat.WG_MERGE2x2), gather_geom=(gh, gw, 2, 2, skip.shape[-1]),
+                sink.put(sp.proj.weight, lambda: sink.wgrad(g, xs, gather=("g", ops.nat.WG_MERGE2x2), gather_geom=(gh, gw, 2, 2, skip.shape[-1]),
                                                            alpha=sp.fac.detach().contiguous()))
                 if sink.wants(sp.fac):                                                 # d fac = sum g (split(x) - skip)
                     y = ops.token_split_lerp(xs, sp.proj.weight, skip, one)
@@ -295,14 +302,14 @@ def backward(model, x, sigma, grad_out, aug_cond=None, class_cond=None, mapping_
             xm = merge_in.pop()
             if sink is not None:
                 gh, gw = g.shape[1:3]
-                sink.put(m.merges[st.level].proj.weight, lambda: ops.wgrad(g, xm, gather=("a", ops.nat.WG_MERGE2x2),
+                sink.put(m.merges[st.level].proj.weight, lambda: sink.wgrad(g, xm, gather=("a", ops.nat.WG_MERGE2x2),
                                                                           gather_geom=(gh, gw, 2, 2, xm.shape[-1])))
             g = ops.token_split_lerp(g, _wt(m, m.merges[st.level].proj.weight), gs, one)     # TokenMerge^T: depth-to-space (lerp weight 1)
             g = ops.rows_affine(gs, omf, g, ones)
     if sink is not None:
         gh, gw = grids[0]
         ph, pw = m.patch_size
-        sink.put(m.patch_in.proj.weight, lambda: ops.wgrad(g, x, gather=("a", ops.nat.WG_PATCH_NCHW), gather_geom=(gh, gw, ph, pw, m.in_channels)))
+        sink.put(m.patch_in.proj.weight, lambda: sink.wgrad(g, x, gather=("a", ops.nat.WG_PATCH_NCHW), gather_geom=(gh, gw, ph, pw, m.in_channels)))
         if sink.chain:
             _mapping_vjp(m, keep, sink, drop)
     g = ops.patch_out(g, None, _wt(m, m.patch_in.proj.weight), m.patch_size, m.in_channels)   # patch-in^T: the un-patch

@@ -778,6 +778,8 @@ def precond_vjp(g, g_coef, sigma, sigma_data, h=None, h_coef=nat.PC_ONE, out=Non
 # mode; every sum runs in a fixed order through a workspace (no atomics), so repeat calls give the same bits.
 
 WGRAD_BLOCKS = 1024          # workgroups a weight-gradient GEMM aims at (row chunks x output tiles); the chunking is a function of the shape
+WGRAD_BF16_BLOCKS = 512      # the same for the bf16 form's 128 x 128 tiles (two workgroups per CU)
+WGRAD_BF16 = 2               # kd_wgrad_f32's arithmetic selector: 0 exact, 1 split3, 2 bf16 operands
 
 
 DROPOUT_SITE = 1 << 62                # include/kdiff_hip.h: every dropout site id has this bit; the Brownian / randn counters never do
@@ -826,8 +828,17 @@ def wgrad_chunks(M, N, K):
     return chunk, -(-M // chunk)
 
 
+def wgrad_chunks_bf16(M, N, K):
+    """(chunk_rows, nchunk) of the bf16 form of ``kd_wgrad_f32`` (128 x 128 output tiles, steps of 32 rows): a function of the shape alone."""
+    tiles = -(-N // 128) * -(-K // 128)
+    nchunk = max(1, min(-(-WGRAD_BF16_BLOCKS // tiles), -(-M // 128), 65535))
+    chunk = -(-M // nchunk)
+    chunk = -(-chunk // 32) * 32
+    return chunk, -(-M // chunk)
+
+
 def wgrad(G, A, *, N=None, K=None, out=None, accumulate=False, gather=None, gather_geom=None, geglu=False, row_scale=None, col_scale=None,
-          rows_per_sample=None, alpha=None, precision=None, dropout=None):
+          rows_per_sample=None, alpha=None, precision=None, dropout=None, bf16=False):
     """Weight gradient of a projection: dW[N, K] (+)= alpha * sum_m G[m, n] * A[m, k] over the stored rows m of G and A.
 
     ``gather``: None, ("g" | "a", nat.WG_MERGE2x2 | nat.WG_PATCH_NCHW) -- that operand is read through the 2x2 token merge of a fine NHWC
@@ -836,7 +847,9 @@ def wgrad(G, A, *, N=None, K=None, out=None, accumulate=False, gather=None, gath
     ``rows_per_sample`` rows).  ``alpha``: a one-element device tensor multiplying the result.  Arithmetic: the backward pass's rule --
     split3 on the matrix cores under KDIFF_GEMM split3 / bf16 / fp8, fp32 FMAs under exact (``precision`` overrides).  ``dropout`` =
     (key, site, p): A's plain [M, K] operand (after the GEGLU prologue) is masked as ``dropout`` masks that site; p == 0 is the plain
-    call."""
+    call.  ``bf16`` (opt-in, whatever ``precision`` and KDIFF_GEMM say): both operands are rounded to bf16 (nearest even) after their whole
+    prologue -- gather, GEGLU, dropout mask, row and column scale -- and every product is one bf16 MFMA with fp32 accumulation, the
+    arithmetic of a ``Linear`` backward under the reference's ``--mixed-precision bf16``."""
     g_mode = a_mode = nat.WG_PLAIN
     gh = gw = ph = pw = chan = 0
     if gather is not None:
@@ -880,11 +893,15 @@ def wgrad(G, A, *, N=None, K=None, out=None, accumulate=False, gather=None, gath
         out = torch.empty(N, K, device=G.device, dtype=torch.float32)
     elif _chk(out, "out").shape != (N, K):
         raise ValueError(f"wgrad: out shape {tuple(out.shape)} != {(N, K)}")
-    split3 = (_prec_of(G) if precision is None else precision) != nat.PREC_EXACT
-    chunk, nchunk = wgrad_chunks(M, N, K)
+    if bf16:
+        arith = WGRAD_BF16
+        chunk, nchunk = wgrad_chunks_bf16(M, N, K)
+    else:
+        arith = int((_prec_of(G) if precision is None else precision) != nat.PREC_EXACT)
+        chunk, nchunk = wgrad_chunks(M, N, K)
     ws = torch.empty(nchunk * N * K, device=G.device, dtype=torch.float32)
     args = (_p(_chk(G, "G")), g_mode, _p(_chk(A, "A")), a_mode, int(bool(geglu)), M, N, K, gh, gw, ph, pw, chan, _p(row_scale), _p(col_scale),
-            col_stride, int(rows_per_sample or 1), _p(None if alpha is None else _chk(alpha, "alpha")), int(bool(accumulate)), int(split3), chunk,
+            col_stride, int(rows_per_sample or 1), _p(None if alpha is None else _chk(alpha, "alpha")), int(bool(accumulate)), arith, chunk,
             nchunk, _p(ws), _p(out))
     drop = _dropout_args(dropout)
     if drop is None:

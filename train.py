@@ -47,7 +47,7 @@ def parse_args(argv=None):
     p.add_argument('--evaluate-only', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--evaluate-every', type=int, default=0, help=argparse.SUPPRESS)
     p.add_argument('--evaluate-n', type=int, default=0, help=argparse.SUPPRESS)
-    p.add_argument('--mixed-precision', type=str, help=argparse.SUPPRESS)
+    p.add_argument('--mixed-precision', type=str, help="'bf16': the weight-gradient GEMMs run on bf16 operands with fp32 accumulation")
     p.add_argument('--compile', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--checkpointing', action='store_true', help=argparse.SUPPRESS)
     args = p.parse_args(argv)
@@ -57,6 +57,10 @@ def parse_args(argv=None):
         p.error('wandb logging is not implemented')
     if args.evaluate_only or args.evaluate_every > 0 or args.evaluate_n > 0:
         p.error('the evaluation flags are not implemented here: compute FID / KID with K.evaluation on samples of the checkpoint')
+    if args.mixed_precision == 'bf16':
+        args.mixed_precision, args.wgrad_bf16 = None, True
+    else:
+        args.wgrad_bf16 = False
     if args.mixed_precision or args.compile or args.checkpointing:
         p.error('--mixed-precision / --compile / --checkpointing are not implemented (the loss runs on the fp32 HIP path)')
     if args.grad_accum_steps < 1:
@@ -118,6 +122,10 @@ def main(argv=None):
     inner_model, inner_model_ema = inner_model.to(device), inner_model_ema.to(device)
     if any(rate > 0 for _, rate in inner_model._dropout_rates()):
         inner_model.enable_dropout()
+    if args.wgrad_bf16:                              # the trained model only: the EMA copy never takes gradients
+        inner_model.set_wgrad_arithmetic('bf16')
+        print('Mixed precision bf16: the weight-gradient GEMMs round their operands to bf16 (fp32 accumulation); the forward pass, the '
+              'loss, the data-gradient GEMMs, the attention rules, the optimizer and the EMA stay fp32', flush=True)
 
     lr = opt_config['lr'] if args.lr is None else args.lr
     opt = K.optim.AdamW(inner_model.param_groups(lr), lr=lr, betas=tuple(opt_config['betas']), eps=opt_config['eps'],
