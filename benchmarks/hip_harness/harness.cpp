@@ -831,6 +831,90 @@ static void run_wgrad_case(const char* name, int M, int N, int K) {
   }
 }
 
+// Karras augmentation (csrc/augment_f32.hip): kd_augment_draw_f32 at a_prob = 1 (every gate fires: checked), then kd_augment_warp_f32 on smooth
+// images against an fp64 restatement -- M^-1 as a chain of 3 x 3 double products of the inverse factors, Catmull-Rom taps gathered with the
+// reflect fold -- on every pixel; then draw + warp timed together.  Bound: the fp32 coordinate carries a few ulp of W (8 ulp allowed) times the
+// image's slope (below 1/4 per pixel here), plus the fp32 rounding of the interpolation itself (1e-6 on values of order 1).
+struct Mat3 { double m[3][3]; };
+static Mat3 mul3(const Mat3& a, const Mat3& b) {
+  Mat3 c{};
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) for (int k = 0; k < 3; ++k) c.m[i][j] += a.m[i][k] * b.m[k][j];
+  return c;
+}
+static Mat3 trans3(double x, double y) { return {{{1, 0, x}, {0, 1, y}, {0, 0, 1}}}; }
+static Mat3 scale3(double x, double y) { return {{{x, 0, 0}, {0, y, 0}, {0, 0, 1}}}; }
+static Mat3 rot3(double t) { return {{{cos(t), -sin(t), 0}, {sin(t), cos(t), 0}, {0, 0, 1}}}; }
+static int reflect_idx(long i, int n) {
+  const long period = 2L * (n - 1);
+  long j = i % period;
+  if (j < 0) j += period;
+  return (int)(j > n - 1 ? period - j : j);
+}
+static double cubic(double t, double p0, double p1, double p2, double p3) {
+  return p1 + 0.5 * t * (p2 - p0 + t * (2 * p0 - 5 * p1 + 4 * p2 - p3 + t * (3 * (p1 - p2) + p3 - p0)));
+}
+
+static void run_augment_case(const char* name, int B, int C, int H, int W) {
+  if (!want(name)) return;
+  const double s = pow(2.0, 0.2), n = pow(2.0, 0.2), t = 0.125;
+  const size_t hw = (size_t)H * W, total = (size_t)B * C * hw;
+  std::vector<float> x(total);
+  for (int b = 0; b < B; ++b)
+    for (int ch = 0; ch < C; ++ch)
+      for (int r = 0; r < H; ++r)
+        for (int c = 0; c < W; ++c) x[((size_t)(b * C + ch) * H + r) * W + c] = (float)sin(0.2 * c + 0.13 * r + ch + 0.37 * b);
+  const std::vector<long long> key = {0x1234567890abcdefLL};
+  DevBuf<long long> dkey(1);
+  DevBuf<float> dx(total), dy(total), draw((size_t)B * 8), dcond((size_t)B * 9), dmat((size_t)B * 6);
+  dkey.up(key); dx.up(x);
+  auto launch = [&] {
+    int rc = kd_augment_draw_f32(dkey.p, B, 1.0f, draw.p, 0);
+    return rc ? rc : kd_augment_warp_f32(dx.p, draw.p, (float)s, (float)n, (float)t, dy.p, dcond.p, dmat.p, B, C, H, W, 0);
+  };
+  if (launch() != 0) {
+    printf("%s: FAILED to launch: %s\n", name, kd_last_error());
+    ++g_fail;
+    return;
+  }
+  HIPCHK(hipDeviceSynchronize());
+  const std::vector<float> raw = draw.down(), y = dy.down(), cond = dcond.down(), mat = dmat.down();
+  double err = 0, err_cond = 0, err_mat = 0;
+  bool fired = true;
+  for (int b = 0; b < B; ++b) {
+    const float* a = &raw[(size_t)b * 8];
+    for (int k = 2; k < 8; ++k) fired = fired && a[k] != 0.0f;
+    const double cx = W / 2.0 - 0.5, cy = H / 2.0 - 0.5;
+    const Mat3 f[] = {trans3(cx, cy), trans3(-t * H * a[6], -t * W * a[7]), rot3(a[4]), scale3(pow(n, -a[5]), pow(n, a[5])), rot3(-a[4]), rot3(a[3]),
+                      scale3(pow(s, -a[2]), pow(s, -a[2])), scale3(1, 1 - 2 * a[1]), scale3(1 - 2 * a[0], 1), trans3(-cx, -cy)};
+    Mat3 inv = f[0];
+    for (int i = 1; i < 10; ++i) inv = mul3(inv, f[i]);
+    for (int i = 0; i < 6; ++i) err_mat = std::max(err_mat, fabs(mat[(size_t)b * 6 + i] - inv.m[i / 3][i % 3]));
+    const double want_cond[9] = {a[0], a[1], a[2], cos(a[3]) - 1, sin(a[3]), a[5] * cos(a[4]), a[5] * sin(a[4]), a[6], a[7]};
+    for (int i = 0; i < 9; ++i) err_cond = std::max(err_cond, fabs(cond[(size_t)b * 9 + i] - want_cond[i]));
+    for (int r = 0; r < H; ++r)
+      for (int c = 0; c < W; ++c) {
+        const double sx = inv.m[0][0] * c + inv.m[0][1] * r + inv.m[0][2], sy = inv.m[1][0] * c + inv.m[1][1] * r + inv.m[1][2];
+        const double fx = floor(sx), fy = floor(sy);
+        int xi[4], yi[4];
+        for (int k = 0; k < 4; ++k) { xi[k] = reflect_idx((long)fx - 1 + k, W); yi[k] = reflect_idx((long)fy - 1 + k, H); }
+        for (int ch = 0; ch < C; ++ch) {
+          const float* src = &x[(size_t)(b * C + ch) * hw];
+          double rows[4];
+          for (int k = 0; k < 4; ++k)
+            rows[k] = cubic(sx - fx, src[(size_t)yi[k] * W + xi[0]], src[(size_t)yi[k] * W + xi[1]], src[(size_t)yi[k] * W + xi[2]], src[(size_t)yi[k] * W + xi[3]]);
+          err = std::max(err, fabs(y[((size_t)(b * C + ch) * H + r) * W + c] - cubic(sy - fy, rows[0], rows[1], rows[2], rows[3])));
+        }
+      }
+  }
+  const double bound = 0.25 * 8 * W * ldexp(1.0, -23) + 1e-6;
+  const bool ok = fired && err <= bound && err_cond <= 2e-6 && err_mat <= 10 * std::max(H, W) * ldexp(1.0, -23);
+  printf("%s %dx%dx%dx%d: y max |err| %.2e (bound %.2e), cond %.2e, mat %.2e vs fp64, all gates fired %d: %s\n", name, B, C, H, W, err, bound, err_cond,
+         err_mat, (int)fired, ok ? "ok" : "FAILED");
+  if (!ok) ++g_fail;
+  const float us = time_us([&] { launch(); }, 50);
+  printf("%s draw + warp: %8.1f us  %7.1f GB/s of image bytes read + written\n", name, us, 2.0 * total * 4 / us * 1e-3);
+}
+
 int main(int argc, char** argv) {
   if (argc > 1) g_filter = argv[1];
   printf("libkdiff_hip version %d\n", kd_version());
@@ -865,6 +949,9 @@ int main(int argc, char** argv) {
   run_wgrad_case("wgrad L0 up", 131072, 768, 128);
   run_wgrad_case("wgrad L2 down", 8192, 512, 1536);
   run_wgrad_case("wgrad ragged", 4128 + 17, 200, 72);
+  run_augment_case("augment cifar batch", 64, 3, 32, 32);
+  run_augment_case("augment 256", 32, 3, 256, 256);
+  run_augment_case("augment ragged", 3, 2, 33, 45);
   if (want("astat")) {
     const GemmCase ca[] = {
         {"astat L1 qkv", 32768, 768, 256, KD_EPI_QKV, 1, 1024, 4},

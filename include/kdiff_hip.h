@@ -518,6 +518,38 @@ int kd_wgrad_drop_f32(const float* G, int g_mode, const float* A, int a_mode, in
                       int split3, int chunk_rows, int nchunk, float* ws, float* dW, const long long* key, unsigned long long site,
                       unsigned threshold, float scale, unsigned* bits, void* stream);
 
+/* Karras et al. augmentation of a training batch (the reference's KarrasAugmentationPipeline.__call__, k_diffusion/augmentation.py:40-89, run
+ * there per image on CPU data-loader workers with scikit-image; csrc/augment_f32.hip).  Neither entry point synchronises.
+ *   kd_augment_draw_f32 : raw[batch, 8] = (a0 .. a7) per sample, the reference's draws (:44-70) in its order: a0 in {0, 1} ungated;
+ *                         a1 in {0, 1} * do; a2 = N(0, 1) * do; a3 = U[-pi, pi) * do; a4 = U[-pi, pi) * do and a5 = N(0, 1) * do on ONE gate;
+ *                         a6 = N * do and a7 = N * do on ONE gate; every do ~ Bernoulli(a_prob), 0 <= a_prob <= 1.  The torch RNG stream of the
+ *                         reference is NOT reproduced.
+ * Counter contract (key: one int64 per call, read through a device pointer like the dropout key):
+ *   block j of sample b = philox4x32_10(key, counter (b, 2^63 | 2^62 | j)), j = 0 .. 3, words w0 .. w3 (csrc/philox.h; the dropout sites
+ *   leave bit 63 clear, kd_randn_f32 sets bit 62 only from draw 2^62 on, the Brownian tree's nodes stay below 2^62);
+ *     u(w) = (w >> 8) / 2^24 in [0, 1);  gate(w) = u(w) < a_prob (fp32);  bit(w) = w >> 31;
+ *     angle(w) = (u(w) - 1/2) * 6.28318501f (the fp32 below 2 pi: the result stays inside [-pi, pi));
+ *     normal(wr, wa) = sqrt(-2 ln(((wr >> 8) + 1) / 2^24)) * cos(2 pi u(wa)), kd_randn_f32's Box-Muller on the hardware log2 / sqrt / cos;
+ *   block 0: a0 = bit(w0);  a1 = gate(w1) ? bit(w2) : 0;  a2 = gate(w3) ? normal(block 1 w0, w1) : 0;
+ *   block 1: a3 = gate(w2) ? angle(w3) : 0;
+ *   block 2: g = gate(w0);  a4 = g ? angle(w1) : 0;  a5 = g ? normal(w2, w3) : 0;
+ *   block 3: g = gate(w0);  (a6, a7) = g ? the pair (r cos, r sin) of normal(w2, w3), sin as cos of a quarter turn less : (0, 0);  w1 unused.
+ *   kd_augment_warp_f32 : y[b] = x[b] [batch, chan, H, W] warped by raw[b], cond[batch, 9] = (a0, a1, a2, cos a3 - 1, sin a3, a5 cos a4,
+ *                         a5 sin a4, a6, a7) (:75), and with mat != NULL mat[batch, 6] = the top two rows of the inverse map that was used.
+ *                         The reference's matrix (:42-74; PIL's image.size is (W, H), so its `h` is W and its `w` is H), acting on
+ *                         (x = column, y = row, 1), with s = a_scale, n = a_aniso, t = a_trans, R(th) = [[cos th, -sin th], [sin th, cos th]]:
+ *                           M = T(W/2 - .5, H/2 - .5) S(1 - 2 a0, 1) S(1, 1 - 2 a1) S(s^a2, s^a2) R(-a3) R(a4) S(n^a5, n^-a5) R(-a4)
+ *                               T(t H a6, t W a7) T(-W/2 + .5, -H/2 + .5).
+ *                         Output pixel (c, r) samples x at M^-1 (c, r, 1); M^-1 is composed from the inverse factors in reverse order (libm
+ *                         sincosf / exp2f, no numeric inverse) and applied as L ((c, r) - centre) + (centre - translation).  Interpolation:
+ *                         scikit-image's order = 3: separable 4 x 4 Catmull-Rom p1 + 0.5 t (p2 - p0 + t (2 p0 - 5 p1 + 4 p2 - p3 + t (3 (p1 - p2)
+ *                         + p3 - p0))), along W first, taps at floor(coord) - 1 .. + 2, out-of-range tap indices folded by numpy-pad 'reflect'
+ *                         (d c b | a b c d | c b a, period 2 (N - 1), any distance; cval plays no part).  H, W >= 2 and H W < 2^31 - 256; a_scale,
+ *                         a_aniso > 0; y must not overlap x: KD_EINVAL otherwise.  A non-finite coordinate samples inside the image (no fault). */
+int kd_augment_draw_f32(const long long* key, int batch, float a_prob, float* raw, void* stream);
+int kd_augment_warp_f32(const float* x, const float* raw, float a_scale, float a_aniso, float a_trans, float* y, float* cond, float* mat,
+                        int batch, int chan, int H, int W, void* stream);
+
 /* Sample-quality metrics (k_diffusion/evaluation.py:93-161; csrc/metrics_f32.hip).  fp32-grade arithmetic: the Gram tiles follow the backward
  * pass's rule (split3 = 1: bf16 hi / lo operands, 3 MFMAs per product, fp32 accumulate; 0: fp32 FMAs).  Every sum has a fixed order (fp64
  * workspace, no atomics): repeat calls give the same bits.  Matrices are row-major fp32; batch items sx / sy elements apart.

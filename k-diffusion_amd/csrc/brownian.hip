@@ -21,13 +21,6 @@
 
 namespace kd {
 
-// Box-Muller on hardware transcendentals: radius from a word mapped to (0, 1], cosine of `rev` revolutions
-__device__ __forceinline__ float bm_radius(unsigned w) {
-  const float u = (float)((w >> 8) + 1u) * 5.9604644775390625e-08f;                  // (0, 1]
-  return __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u));   // sqrt(-2 ln u), v_log_f32 is log2
-}
-__device__ __forceinline__ float unit24(unsigned w) { return (float)(w >> 8) * 5.9604644775390625e-08f; }   // [0, 1)
-
 __device__ __forceinline__ float brownian_w(unsigned long long key, unsigned long long elem, double t, double T0, double T1, int depth) {
   double ta = T0, tb = T1;
   const float sd0 = __builtin_amdgcn_sqrtf((float)(T1 - T0));

@@ -4,8 +4,12 @@
 
 The loss, its backward, the optimizer step (gradient clipping + AdamW + EMA + gradient zeroing, K.optim.AdamW), the sigma draw and the demo
 sampler all run on this project's HIP kernels.  Differences from the reference, by design:
-  * one process, one GPU; dataset type ``imagefolder`` only (PIL, LANCZOS resize + centre crop); no augmentation (``augment_prob`` must be
-    0; ``aug_cond`` is zeros [B, 9], what the reference's disabled pipeline yields); optimizer ``adamw`` only; no --gns, wandb or evaluation;
+  * one process, one GPU; dataset type ``imagefolder`` only (PIL, LANCZOS resize + centre crop); optimizer ``adamw`` only; no --gns, wandb or
+    evaluation;
+  * augmentation (``augment_prob`` > 0) needs ``--device-augment``: the reference's KarrasAugmentationPipeline runs per image on the data-loader
+    workers with scikit-image; here K.augmentation warps the uploaded batch on the device, with parameters from this project's counter-based
+    generator (one key per step from the default device generator -- not the reference's torch draws).  Without the flag such a config is
+    refused; with ``augment_prob`` 0, ``aug_cond`` is zeros [B, 9], what the reference's disabled pipeline yields;
   * a checkpoint also holds the RNG states and the position in the epoch, and the data order is a function of (seed, epoch), so that
     ``--resume`` continues the run it was saved from bit for bit (the reference restarts the epoch and its RNG streams).
 """
@@ -29,6 +33,8 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0], formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('--batch-size', type=int, default=64, help='the batch size')
     p.add_argument('--config', type=str, required=True, help='the configuration file')
+    p.add_argument('--device-augment', action='store_true',
+                   help="run the config's Karras augmentation (augment_prob > 0) on the device, on this project's HIP warp kernel")
     p.add_argument('--demo-every', type=int, default=500, help='save a demo grid every this many steps')
     p.add_argument('--end-step', type=int, default=None, help='the step to end training at')
     p.add_argument('--grad-accum-steps', type=int, default=1, help='the number of gradient accumulation steps')
@@ -95,8 +101,10 @@ def main(argv=None):
 
     assert len(model_config['input_size']) == 2 and model_config['input_size'][0] == model_config['input_size'][1]
     size = model_config['input_size']
-    if model_config.get('augment_prob', 0) > 0:
-        raise NotImplementedError('augment_prob > 0: KarrasAugmentationPipeline (scikit-image warps) is not implemented; set augment_prob to 0')
+    augment_prob = model_config.get('augment_prob', 0)
+    if augment_prob > 0 and not args.device_augment:
+        raise NotImplementedError('augment_prob > 0: KarrasAugmentationPipeline (scikit-image warps) is not implemented; set augment_prob to 0, '
+                                  'or pass --device-augment to augment each batch on the device (K.augmentation)')
     if opt_config['type'] != 'adamw':
         raise NotImplementedError(f'optimizer type {opt_config["type"]!r}: only adamw runs on the fused HIP step')
     if dataset_config['type'] != 'imagefolder':
@@ -168,6 +176,10 @@ def main(argv=None):
     sigma_min = model_config['sigma_min']
     sigma_max = model_config['sigma_max']
     sample_density = K.training.make_sample_density(model_config)
+
+    aug = K.augmentation.KarrasAugmentationPipeline(augment_prob) if augment_prob > 0 else None
+    if aug is not None:
+        print(f'Device augmentation: a_prob {augment_prob:g}', flush=True)
 
     model = K.config.make_denoiser_wrapper(config)(inner_model)
     model_ema = K.config.make_denoiser_wrapper(config)(inner_model_ema)
@@ -270,7 +282,10 @@ def main(argv=None):
 
                 sync_gradients = (step + 1) % accum == 0
                 reals = batch[image_key].to(device, non_blocking=True)
-                aug_cond = reals.new_zeros([reals.shape[0], 9])
+                if aug is not None:                  # the key comes from the default device generator: its state is in the checkpoint
+                    reals, _, aug_cond = aug.batch(reals)
+                else:
+                    aug_cond = reals.new_zeros([reals.shape[0], 9])
                 extra_args = {}
                 if num_classes:
                     class_cond = batch[class_key].to(device)
