@@ -645,7 +645,9 @@ int kd_sigma_density_f32(int kind, const void* u, int u_f64, const void* normal,
  * (torchvision's to_pil_image does mul(255).byte(), i.e. truncation) */
 int kd_to_uint8(const float* x, unsigned char* y, long long n, void* stream);
 
-/* Per-launch timing hooks for bench.py (HIP events recorded on `stream` around each launch). */
+/* Per-launch timing hooks for bench.py (HIP events recorded on `stream` around each launch).  A record's name is the kernel (with its
+ * template switches), the shape, and -- where the launcher chooses between configurations (n-splits, tile form, wave count, slices) -- one
+ * field " cfg=..." stating what it launched, e.g. "gemm_x3_astat<e5> M=1000 N=384 K=128 cfg=splits3"; at most 95 characters. */
 int kd_prof_enable(int on);
 int kd_prof_count(void);
 int kd_prof_get(int i, char* name, int name_cap, float* ms, double* flops, double* bytes);

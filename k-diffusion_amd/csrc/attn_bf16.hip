@@ -513,7 +513,8 @@ static int launch_dense(const DArgs& a, long nproblems, const char* name, hipStr
   static LdsAttr set;
   set.ensure(reinterpret_cast<const void*>(k), LDS);
   const int n_slots = MODE == MODE_GLOBAL ? a.T : (1 << (2 * WinLog2<MODE>::v));
-  LaunchScope prof(name, 4.0 * (double)nproblems * n_slots * n_slots * DH, 2.0 * (double)a.batch * a.T * a.nh * DH * 4.0, s);
+  const CfgName cfg(name, "qw%d", QW);               // waves (32 query rows each) per workgroup
+  LaunchScope prof(cfg, 4.0 * (double)nproblems * n_slots * n_slots * DH, 2.0 * (double)a.batch * a.T * a.nh * DH * 4.0, s);
   hipLaunchKernelGGL(k, dim3((unsigned)(nproblems * NQB)), dim3(QW * 64), LDS, s, a);
   return check_launch(name);
 }

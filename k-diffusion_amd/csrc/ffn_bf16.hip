@@ -515,7 +515,8 @@ extern "C" int kd_ffn_bf16(const KdFfn* dp, void* stream) {
   if (prof_on()) snprintf(nm, sizeof(nm), "%s M=%d K=%d dff=%d", outp ? "ffn_bf16+out" : "ffn_bf16", d.M, d.K, d.d_ff);
   const double flops = 2.0 * d.M * (double)d.K * (3.0 * d.d_ff + (outp ? d.K : 0));
   const double bytes = (outp ? 6.0 : 4.0) * d.M * (double)d.K + 6.0 * d.d_ff * (double)d.K + (outp ? 2.0 * d.K * d.K : 0.0);
-  LaunchScope prof(nm, flops, bytes, s);
+  const CfgName cfg(nm, "variant%d", variant == 3 && !outp ? 3 : 1);
+  LaunchScope prof(cfg, flops, bytes, s);
   hipLaunchKernelGGL(kern, dim3((unsigned)((d.M + panel - 1) / panel)), dim3(threads), LDS, s, a);
   return check_launch("kd_ffn_bf16");
 }

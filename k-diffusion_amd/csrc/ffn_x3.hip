@@ -523,7 +523,8 @@ static int launch_ffn_half(const FArgs3& a, const char* nm, double flops, double
   auto kern = ffn_x3h_kernel<OUTP>;
   static LdsAttr attr_set;
   attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
-  LaunchScope prof(nm, flops, bytes, s);
+  const CfgName cfg(nm, "half1");
+  LaunchScope prof(cfg, flops, bytes, s);
   hipLaunchKernelGGL(kern, dim3((unsigned)((a.M + 127) / 128)), dim3(256), LDS, s, a);
   return check_launch("kd_ffn_f32");
 }
@@ -535,7 +536,8 @@ static int launch_ffn(const FArgs3& a, const char* nm, double flops, double byte
   constexpr int LDS = 8 * STG + 4 * (K * 4 < 1024 ? 1024 : K * 4) + 4 * 2048;
   static LdsAttr attr_set;
   attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
-  LaunchScope prof(nm, flops, bytes, s);
+  const CfgName cfg(nm, "half0");
+  LaunchScope prof(cfg, flops, bytes, s);
   hipLaunchKernelGGL(kern, dim3((unsigned)((a.M + 127) / 128)), dim3(256), LDS, s, a);
   return check_launch("kd_ffn_f32");
 }

@@ -277,11 +277,12 @@ static int launch(const GemmP& d, hipStream_t s) {
   const double n_eff = (EPI == KD_EPI_GEGLU) ? 2.0 * d.N : (double)d.N;
   char nm[96] = "gemm_astat";
   if (prof_on()) snprintf(nm, sizeof(nm), "gemm_astat<e%d> M=%d N=%d K=%d", EPI, d.M, d.N, d.K);
-  LaunchScope prof(nm, 2.0 * d.M * n_eff * d.K, 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N), s);
   // panels x n-splits: aim at >= 256 workgroups (one per CU) while every split keeps >= 2 n-tiles
   const int panels = (d.M + BMW - 1) / BMW, n_tiles = d.N / (EPI == KD_EPI_GEGLU ? 64 : 128);
   int splits = 1;
   while (panels * splits < 256 && n_tiles / (splits * 2) >= 2) splits *= 2;
+  const CfgName cfg(nm, "splits%d,waves%d", splits, NWV);
+  LaunchScope prof(cfg, 2.0 * d.M * n_eff * d.K, 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N), s);
   GemmP e = d;
   if (option("astat_storewait", 0)) e.debug |= 32;
   hipLaunchKernelGGL(kern, dim3((unsigned)panels, (unsigned)splits), dim3(64 * NWV), LDS_BYTES, s, e);

@@ -278,7 +278,8 @@ static int launch_wstat(const GArgs& a, int lds, const char* nm, double flops, d
   if (groups < 1) groups = 1;
   const int need = (chunks + NW - 1) / NW;
   if (groups > need) groups = need;
-  LaunchScope prof(nm, flops, bytes, s);
+  const CfgName cfg(nm, "waves%d,pf%d,slices%d", NW, PIPE ? 2 : (PF ? 1 : 0), a.n_slices);
+  LaunchScope prof(cfg, flops, bytes, s);
   hipLaunchKernelGGL(kern, dim3((unsigned)(groups * a.n_slices)), dim3(NW * 64), lds, s, a);
   return check_launch("kd_gemm_bf16(wstat)");
 }
@@ -621,7 +622,8 @@ static int launch_tiled(const TArgs& a, const char* nm, double flops, double byt
   static LdsAttr attr_set;
   attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
   const long tiles = (long)((a.M + 128 * BMT - 1) / (128 * BMT)) * a.n_tiles_n;
-  LaunchScope prof(nm, flops, bytes, s);
+  const CfgName cfg(nm, "bm%d,lw%d,deep%d", 128 * BMT, (int)LW, (int)DEEP);       // (the loader-wave form runs on the deep ring: lw1,deep1)
+  LaunchScope prof(cfg, flops, bytes, s);
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(LW ? 512 : 256 * BMT), LDS, s, a);
   return check_launch("kd_gemm_bf16(tiled)");
 }
@@ -928,7 +930,8 @@ static int launch_astat_w(const GArgs& a, int splits, const char* nm, double flo
   const int panels = (a.M + 32 * NWV - 1) / (32 * NWV);
   GArgs b = a;
   b.n_slices = splits;                                // (the astat kernel's use of this field: n-splits per panel)
-  LaunchScope prof(nm, flops, bytes, s);
+  const CfgName cfg(nm, "rows%d,splits%d", 32 * NWV, splits);
+  LaunchScope prof(cfg, flops, bytes, s);
   hipLaunchKernelGGL(kern, dim3((unsigned)(panels * splits)), dim3(NWV * 64), LDS, s, b);
   return check_launch("kd_gemm_bf16(astat)");
 }

@@ -611,7 +611,8 @@ extern "C" int kd_gemm_mx8(const KdGemm* dp, void* stream) {
   const double bytes = 2.0 * (double)d.M * d.K + (d.c_split ? (1.0 + 1.0 / 32) : 2.0) * (double)d.M * d.N + n_eff * d.K;
   char nm[96] = "gemm_mx8_astat";
   if (prof_on()) snprintf(nm, sizeof(nm), "gemm_mx8_astat<e%d%s> M=%d N=%d K=%d", d.epi, d.c_split ? ",c8" : "", d.M, d.N, d.K);
-  LaunchScope prof(nm, flops, bytes, s);
+  const CfgName cfg(nm, "splits%d", a.n_splits);
+  LaunchScope prof(cfg, flops, bytes, s);
   // ring + one scale vector (K floats) per wave + the channel-scale bytes of a split's n-tiles (<= 64 tiles)
 #define KD_MX(NKV, EP, C8) { constexpr int LDS = 4 * WBLK + 4 * NKV * 64 * 4 + 64 * 128; static LdsAttr set;           \
     set.ensure(reinterpret_cast<const void*>(gemm_mx8_astat_kernel<NKV, EP, C8>), LDS);                                  \

@@ -731,8 +731,9 @@ static int launch(const XArgs& a0, const char* nm, double flops, double bytes, h
   const int panels = (a0.M + 127) / 128, best = best_n_splits(panels, a0.n_tiles, (NC <= 8 ? 2 : 1) * cu_count(), 1);
   const int forced = force_splits ? force_splits : option("x3_splits", 0);
   XArgs a = a0;
-  a.n_splits = forced > 0 && forced <= a0.n_tiles ? forced : best;
-  LaunchScope prof(nm, flops, bytes, s);
+  a.n_splits = forced > 0 && forced <= a0.n_tiles ? forced : best;      // (any count up to n_tiles: panel_split hands out proportional, non-empty shares)
+  const CfgName cfg(nm, "splits%d", a.n_splits);
+  LaunchScope prof(cfg, flops, bytes, s);
   hipLaunchKernelGGL(kern, dim3((unsigned)(panels * a.n_splits)), dim3(256), LDS, s, a);
   return check_launch("kd_gemm_f32(x3 astat)");
 }
@@ -748,7 +749,8 @@ static int launch_half(const XArgs& a0, const char* nm, double flops, double byt
   const int forced = option("x3_splits", 0);
   XArgs a = a0;
   a.n_splits = forced > 0 && forced <= a0.n_tiles && a0.n_tiles % forced == 0 ? forced : best;
-  LaunchScope prof(nm, flops, bytes, s);
+  const CfgName cfg(nm, "splits%d", a.n_splits);
+  LaunchScope prof(cfg, flops, bytes, s);
   hipLaunchKernelGGL(kern, dim3((unsigned)(panels * a.n_splits)), dim3(256), LDS, s, a);
   return check_launch("kd_gemm_f32(x3 half tiles)");
 }

@@ -57,6 +57,25 @@ struct LaunchScope {
   ~LaunchScope() { if (t.idx >= 0) prof_end(t, s); }
 };
 
+// A launch-profile name with the configuration the launcher ACTUALLY chose appended as one field " cfg=..." (n-splits, tile form, wave
+// count, ...: tests/test_launch_config_gpu.py asserts it; bench.py groups by the text in front of the first space).  Only while profiling:
+// otherwise the name passes through untouched and nothing is formatted.  Stays within the 96 bytes of the launchers' name buffers.
+struct CfgName {
+  char buf[96];
+  const char* s;
+  __attribute__((format(printf, 3, 4))) CfgName(const char* nm, const char* fmt, ...) : s(nm) {
+    if (!prof_on()) return;
+    const int n = snprintf(buf, sizeof(buf), "%s cfg=", nm);
+    if (n < 0 || n >= (int)sizeof(buf)) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf + n, sizeof(buf) - n, fmt, ap);
+    va_end(ap);
+    s = buf;
+  }
+  operator const char*() const { return s; }
+};
+
 // hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, set ONCE PER KERNEL AND DEVICE from whichever host thread launches it first.
 // One function-local `static LdsAttr` per launch site (= per kernel instantiation): a bit per device ordinal.  hipFuncSetAttribute is
 // idempotent, so two threads racing on a kernel's first launch both set the same value before either publishes the device's bit; a thread

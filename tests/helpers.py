@@ -1,7 +1,20 @@
 """Test helpers shared by CPU and GPU tests."""
+import os
+import re
 import struct
 
 import torch
+
+
+def source_options():
+    """Every option name the library's dispatch code reads: ``option("name", default)`` in k-diffusion_amd/csrc."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "k-diffusion_amd", "csrc")
+    names = set()
+    for fn in os.listdir(csrc):
+        if fn.endswith((".hip", ".cpp", ".h")):
+            names |= set(re.findall(r'option\("([a-z0-9_]+)"', open(os.path.join(csrc, fn)).read()))
+    names.discard("name")                      # the usage example in kd_common.h
+    return names
 
 
 def state_dict_shapes(cfg):

@@ -6,6 +6,7 @@ plain fp64 reference (torch on the CPU, or the oracle's functions) at the tolera
 the same bits as the ordinary call, the same bits under both fills, guards and inputs untouched, nothing left unwritten.  Ops without an
 ``out=`` argument get guarded inputs only (the result checks still see a NaN the kernel left or let in).  Needs a real MI355X.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -96,6 +97,18 @@ def np_mask(key, site, p, n):
 
 
 CASES = []
+
+
+@contextlib.contextmanager
+def collect_into(table):
+    """Inside the block the builders below append their cases to ``table`` instead of this module's CASES (tests/test_launch_config_gpu.py
+    builds its rows with them); what this module collects and asserts does not change."""
+    global CASES
+    saved, CASES = CASES, table
+    try:
+        yield table
+    finally:
+        CASES = saved
 
 
 def case(name, op, src, mode=None, few_rows=False, kernel=None):

@@ -161,12 +161,8 @@ def test_every_option_name_used_in_the_sources_is_registered():
     """kd_set_option refuses unknown names; every name the kernels' dispatch code reads (option("name", default)) and every name
     the Python layer maps an environment variable to must therefore be in the library's table (checked in a child process: a set
     option overrides the call sites' defaults for the rest of the process)."""
-    csrc = os.path.join(REPO, "k-diffusion_amd", "csrc")
-    names = set()
-    for fn in os.listdir(csrc):
-        if fn.endswith((".hip", ".cpp", ".h")):
-            names |= set(re.findall(r'option\("([a-z0-9_]+)"', open(os.path.join(csrc, fn)).read()))
-    names.discard("name")                      # the usage example in kd_common.h
+    from tests.helpers import source_options
+    names = source_options()
     assert {"code_warm", "patch_fast", "ffn_fused", "wstat", "astat"} <= names
     code = (
         "import sys; sys.path.insert(0, %r)\n"
