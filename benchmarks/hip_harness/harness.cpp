@@ -340,8 +340,13 @@ static void run_mx8_case(const char* name, int M, int K, int dff, int rps) {
     }
   }
   const float us_up = time_us([&] { kd_gemm_mx8(&up, nullptr); }), us_dn = time_us([&] { kd_gemm_mx8(&dn, nullptr); });
-  printf("%-28s M=%6d K=%4d d_ff=%4d  hidden: max err / block max %.3g bad=%ld   down + skip: max|err|=%.4g bad=%ld   up %6.1f us (%6.1f TF/s)  down %6.1f us (%6.1f TF/s)  %s\n",
-         name, M, K, dff, max_eh, bad_h, max_eo, bad_o, us_up, 4.0 * M * (double)dff * K / us_up * 1e-6, us_dn, 2.0 * M * (double)dff * K / us_dn * 1e-6,
+  // the same up projection with a bf16 hidden (c_split = 0: its own kernel instantiation), timed only
+  DevBuf<uint16_t> dHb((size_t)M * dff);
+  KdGemm upb = up;
+  upb.c_split = 0; upb.C = reinterpret_cast<float*>(dHb.p); upb.C_lo = nullptr;
+  const float us_upb = kd_gemm_mx8(&upb, nullptr) ? -1.f : time_us([&] { kd_gemm_mx8(&upb, nullptr); });
+  printf("%-28s M=%6d K=%4d d_ff=%4d  hidden: max err / block max %.3g bad=%ld   down + skip: max|err|=%.4g bad=%ld   up %6.1f us (%6.1f TF/s)  up, bf16 out %6.1f us  down %6.1f us (%6.1f TF/s)  %s\n",
+         name, M, K, dff, max_eh, bad_h, max_eo, bad_o, us_up, 4.0 * M * (double)dff * K / us_up * 1e-6, us_upb, us_dn, 2.0 * M * (double)dff * K / us_dn * 1e-6,
          (bad_h || bad_o) ? "FAIL" : "ok");
   if (bad_h || bad_o) ++g_fail;
 }

@@ -250,12 +250,7 @@ __global__ __launch_bounds__(256, NaGeo<KS>::LDS <= 53 * 1024 ? 3 : 2) void attn
   const auto warm = code_warm_begin<7168>((int)blockIdx.x < a.warm && tid < 64);
   const int wy_ = wid >> 1, wx_ = wid & 1;
   const int tiles_x = (a.W + NA_TW - 1) / NA_TW, tiles_y = (a.H + NA_TH - 1) / NA_TH;
-  int r;
-  {   // XCD-aware tile order: neighbouring tiles (overlapping halos) run on ONE L2
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int q = nwg >> 3, rem = nwg & 7;
-    r = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + k;
-  }
+  int r = KD_XCD_CHUNK();      // XCD-aware order: neighbouring tiles (overlapping halos) run on ONE L2
   const int tx = r % tiles_x; r /= tiles_x;
   const int ty = r % tiles_y; r /= tiles_y;
   const int head = r % a.nh, b = r / a.nh;
@@ -495,41 +490,30 @@ __global__ __launch_bounds__(256, 1) void attn_na2d_wide_bf16_kernel(const NArgs
 
 template <int KS>
 static int launch_na_wide(const NArgs& a, hipStream_t s) {
-  auto k = attn_na2d_wide_bf16_kernel<KS>;
-  static LdsAttr set;
-  set.ensure(reinterpret_cast<const void*>(k), NaWide<KS>::LDS);
   const long nb = (long)a.batch * a.nh * ((a.H + NA_TH - 1) / NA_TH) * ((a.W + NA_TW - 1) / NA_TW);
-  char nm[64] = "attn_na2d_bf16";
-  if (prof_on()) snprintf(nm, sizeof(nm), "attn_na2d_bf16 k%d %dx%d nh=%d", KS, a.H, a.W, a.nh);
+  const ProfName nm("attn_na2d_bf16", "attn_na2d_bf16 k%d %dx%d nh=%d", KS, a.H, a.W, a.nh);
   LaunchScope prof(nm, 4.0 * a.batch * (double)a.H * a.W * a.nh * DH * KS * KS, 8.0 * a.batch * (double)a.H * a.W * a.nh * DH, s);
-  hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(256), NaWide<KS>::LDS, s, a);
+  launch<attn_na2d_wide_bf16_kernel<KS>>(dim3((unsigned)nb), dim3(256), NaWide<KS>::LDS, s, a);
   return check_launch("kd_attn_na2d_bf16");
 }
 
 template <int MODE, int NT, int QW>
 static int launch_dense(const DArgs& a, long nproblems, const char* name, hipStream_t s) {
   constexpr int LDS = NT * 32 * 256, NQB = (NT + QW - 1) / QW;
-  auto k = attn_dense_bf16_kernel<MODE, NT, QW>;
-  static LdsAttr set;
-  set.ensure(reinterpret_cast<const void*>(k), LDS);
   const int n_slots = MODE == MODE_GLOBAL ? a.T : (1 << (2 * WinLog2<MODE>::v));
   const CfgName cfg(name, "qw%d", QW);               // waves (32 query rows each) per workgroup
   LaunchScope prof(cfg, 4.0 * (double)nproblems * n_slots * n_slots * DH, 2.0 * (double)a.batch * a.T * a.nh * DH * 4.0, s);
-  hipLaunchKernelGGL(k, dim3((unsigned)(nproblems * NQB)), dim3(QW * 64), LDS, s, a);
+  launch<attn_dense_bf16_kernel<MODE, NT, QW>>(dim3((unsigned)(nproblems * NQB)), dim3(QW * 64), LDS, s, a);
   return check_launch(name);
 }
 
 template <int KS>
 static int launch_na(const NArgs& a, hipStream_t s) {
   const long nb = (long)a.batch * a.nh * ((a.H + NA_TH - 1) / NA_TH) * ((a.W + NA_TW - 1) / NA_TW);
-  auto k = attn_na2d_bf16_kernel<KS>;
-  static LdsAttr set;
   constexpr int LDS = NaGeo<KS>::LDS;
-  set.ensure(reinterpret_cast<const void*>(k), LDS);
-  char nm[64] = "attn_na2d_bf16";
-  if (prof_on()) snprintf(nm, sizeof(nm), "attn_na2d_bf16 k%d %dx%d nh=%d", KS, a.H, a.W, a.nh);
+  const ProfName nm("attn_na2d_bf16", "attn_na2d_bf16 k%d %dx%d nh=%d", KS, a.H, a.W, a.nh);
   LaunchScope prof(nm, 4.0 * a.batch * (double)a.H * a.W * a.nh * DH * KS * KS, 8.0 * a.batch * (double)a.H * a.W * a.nh * DH, s);
-  hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(256), LDS, s, a);
+  launch<attn_na2d_bf16_kernel<KS>>(dim3((unsigned)nb), dim3(256), LDS, s, a);
   return check_launch("kd_attn_na2d_bf16");
 }
 
@@ -545,11 +529,9 @@ extern "C" int kd_attn_global_bf16(const void* qkv, void* out, int batch, int T,
   hipStream_t s = (hipStream_t)stream;
   const long nb = (long)batch * nh;
   if (T > 256) {
-    static LdsAttr set;
-    set.ensure(reinterpret_cast<const void*>(attn_long_bf16_kernel), GL_LDS);
     const long nqb = (T + GL_QW * 32 - 1) / (GL_QW * 32);
     LaunchScope prof("attn_global_bf16", 4.0 * (double)nb * T * T * DH, 2.0 * (double)batch * T * nh * DH * 4.0, s);
-    hipLaunchKernelGGL(attn_long_bf16_kernel, dim3((unsigned)(nb * nqb)), dim3(GL_QW * 64), GL_LDS, s, a);
+    launch<attn_long_bf16_kernel>(dim3((unsigned)(nb * nqb)), dim3(GL_QW * 64), GL_LDS, s, a);
     return check_launch("kd_attn_global_bf16");
   }
   const int qw = option("attn_global_qw", 8);

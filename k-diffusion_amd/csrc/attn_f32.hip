@@ -332,15 +332,7 @@ __global__ __launch_bounds__(256, 2) void attn_na2d_kernel(const NaArgs a) {
   const int l31 = lane & 31, h2 = lane >> 5;
   const int wy_ = wid >> 1, wx_ = wid & 1;                            // this wave's 4x8 query block
   const int tiles_x = (a.W + NA_TW - 1) / NA_TW, tiles_y = (a.H + NA_TH - 1) / NA_TH;
-  // XCD-aware tile order: consecutive workgroups are dealt round-robin over the 8 XCDs (private L2s); give every XCD a
-  // CONTIGUOUS run of tiles so that the halos of neighbouring tiles (2.4x re-read of K and V) hit ONE L2 instead of
-  // being fetched from HBM by eight of them.  Bijective for any grid size; placement never affects correctness.
-  int r;
-  {
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int q = nwg >> 3, rem = nwg & 7;
-    r = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + k;
-  }
+  int r = KD_XCD_CHUNK();      // XCD-aware order: the halos of neighbouring tiles (2.4x re-read of K and V) hit ONE L2
   const int tx = r % tiles_x; r /= tiles_x;
   const int ty = r % tiles_y; r /= tiles_y;
   const int head = r % a.nh; const int b = r / a.nh;
@@ -1162,15 +1154,10 @@ static int launch_global_long(const DenseArgs& a, int prep, hipStream_t s) {
   const long nqb = (a.T + GL_QW * 32 - 1) / (GL_QW * 32);
   const long nblocks = (long)a.batch * a.nh * nqb;
   LaunchScope prof("attn_global_bf16x3", 4.0 * (double)a.batch * a.nh * a.T * a.T * DH, 4.0 * (double)a.batch * a.T * a.nh * DH * 4.0, s);
-#define KD_GL(PM)                                                                                                                                   \
-  {                                                                                                                                                \
-    auto k = attn_global_long_kernel<PM>;                                                                                                          \
-    static LdsAttr set;                                                                                                                       \
-    set.ensure(reinterpret_cast<const void*>(k), GL_LDS);   \
-    hipLaunchKernelGGL(k, dim3((unsigned)nblocks), dim3(GL_THR), GL_LDS, s, a);                                                                    \
-  }
-  if (prep == 1) KD_GL(1) else if (prep == 2) KD_GL(2) else KD_GL(0)
-#undef KD_GL
+  const dim3 grid((unsigned)nblocks), block(GL_THR);
+  if (prep == 1) launch<attn_global_long_kernel<1>>(grid, block, GL_LDS, s, a);
+  else if (prep == 2) launch<attn_global_long_kernel<2>>(grid, block, GL_LDS, s, a);
+  else launch<attn_global_long_kernel<0>>(grid, block, GL_LDS, s, a);
   return check_launch("kd_attn_global_f32");
 }
 
@@ -1181,36 +1168,22 @@ static int launch_global_split(const DenseArgs& a, int prep, long nblocks, hipSt
   const int n_slots = MODE == MODE_GLOBAL ? a.T : (1 << (2 * WinLog2<MODE>::v));
   LaunchScope prof(MODE == MODE_GLOBAL ? "attn_global_bf16x3" : "attn_window_bf16x3", 4.0 * (double)nblocks * n_slots * n_slots * DH,
                    4.0 * (double)a.batch * a.T * a.nh * DH * 4.0, s);
-#define KD_GS(PM)                                                                                                                                \
-  {                                                                                                                                             \
-    auto k = attn_global_split_kernel<MODE, NT, PM>;                                                                                            \
-    static LdsAttr set;                                                                                                                    \
-    set.ensure(reinterpret_cast<const void*>(k), lds);   \
-    hipLaunchKernelGGL(k, dim3((unsigned)nblocks), dim3(NT * 64), lds, s, a);                                                                   \
-  }
-  if (prep == 1) KD_GS(1) else if (prep == 2) KD_GS(2) else KD_GS(0)
-#undef KD_GS
+  const dim3 grid((unsigned)nblocks), block(NT * 64);
+  if (prep == 1) launch<attn_global_split_kernel<MODE, NT, 1>>(grid, block, lds, s, a);
+  else if (prep == 2) launch<attn_global_split_kernel<MODE, NT, 2>>(grid, block, lds, s, a);
+  else launch<attn_global_split_kernel<MODE, NT, 0>>(grid, block, lds, s, a);
   return check_launch("kd_attn_global_f32");
 }
 
 template <int MODE, int MAXT>
 static int launch_dense(const DenseArgs& a, int prep, long nblocks, const char* name, hipStream_t s) {
-  const size_t lds = (size_t)2 * MAXT * 32 * LDS_ROW * sizeof(float);
+  constexpr int lds = 2 * MAXT * 32 * LDS_ROW * sizeof(float);
   const int n_slots = MODE == MODE_GLOBAL ? a.T : (1 << (2 * WinLog2<MODE>::v));
   const double flops = 4.0 * (double)nblocks * n_slots * n_slots * DH;
   const double bytes = 4.0 * (double)a.batch * a.T * a.nh * DH * 4.0;
   LaunchScope prof(name, flops, bytes, s);
-  if (prep) {
-    auto k = attn_dense_kernel<MODE, MAXT, true>;
-    static LdsAttr set;
-    set.ensure(reinterpret_cast<const void*>(k), (int)lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)nblocks), dim3(MAXT * 64), lds, s, a);
-  } else {
-    auto k = attn_dense_kernel<MODE, MAXT, false>;
-    static LdsAttr set;
-    set.ensure(reinterpret_cast<const void*>(k), (int)lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)nblocks), dim3(MAXT * 64), lds, s, a);
-  }
+  if (prep) launch<attn_dense_kernel<MODE, MAXT, true>>(dim3((unsigned)nblocks), dim3(MAXT * 64), lds, s, a);
+  else launch<attn_dense_kernel<MODE, MAXT, false>>(dim3((unsigned)nblocks), dim3(MAXT * 64), lds, s, a);
   return check_launch(name);
 }
 
@@ -1308,18 +1281,13 @@ extern "C" int kd_attn_na2d_f32(const float* qkv, float* out, int batch, int H, 
                            "fp32 operands: kernel_size 7 only", ks);
   NaArgs a{qkv, out, scale_h, cos_t, sin_t, batch, H, W, nh, eps, option("code_warm", KD_CODE_WARM_DEFAULT)};
   const long nb = (long)batch * nh * ((H + NA_TH - 1) / NA_TH) * ((W + NA_TW - 1) / NA_TW);
-  char nm[64] = "attn_na2d";
-  if (prof_on()) snprintf(nm, sizeof(nm), "attn_na2d %dx%d nh=%d", H, W, nh);
+  const ProfName nm("attn_na2d", "attn_na2d %dx%d nh=%d", H, W, nh);
   LaunchScope prof(nm, 4.0 * batch * (double)H * W * nh * DH * ks * ks, 16.0 * batch * (double)H * W * nh * DH, s);
-  static LdsAttr attr_set[6];
-#define KD_NA_ATTR(I, PM, FU) attr_set[I].ensure(reinterpret_cast<const void*>(attn_na2d_kernel<PM, FU>), NA_LDS);
-  KD_NA_ATTR(0, 0, true) KD_NA_ATTR(1, 0, false) KD_NA_ATTR(2, 1, true) KD_NA_ATTR(3, 1, false) KD_NA_ATTR(4, 2, true) KD_NA_ATTR(5, 2, false)
-#undef KD_NA_ATTR
   const bool full = H >= NA_HR && W >= NA_HC;      // every halo key is inside the image
-#define KD_NA(PM)                                                                                              \
-  {                                                                                                           \
-    if (full) hipLaunchKernelGGL((attn_na2d_kernel<PM, true>), dim3((unsigned)nb), dim3(256), NA_LDS, s, a); \
-    else hipLaunchKernelGGL((attn_na2d_kernel<PM, false>), dim3((unsigned)nb), dim3(256), NA_LDS, s, a);      \
+#define KD_NA(PM)                                                                                   \
+  {                                                                                                \
+    if (full) launch<attn_na2d_kernel<PM, true>>(dim3((unsigned)nb), dim3(256), NA_LDS, s, a);    \
+    else launch<attn_na2d_kernel<PM, false>>(dim3((unsigned)nb), dim3(256), NA_LDS, s, a);        \
   }
   if (prep == 1) KD_NA(1) else if (prep == 2) KD_NA(2) else KD_NA(0)
 #undef KD_NA

@@ -43,12 +43,7 @@ __global__ __launch_bounds__(256, 2) void attn_ffn_x3h_kernel(const x3a::NArgs a
   const auto warm = code_warm_begin<28 * 1024>((int)blockIdx.x < a.warm && tid < 64);
   (void)wg_stamp_begin(a.clk);
   const int tiles_x = a.W / NA_TW, tiles_y = a.H / NA_TH;
-  int r;
-  {   // XCD-aware tile order: neighbouring tiles (overlapping halos) run on ONE L2
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int q = nwg >> 3, rem = nwg & 7;
-    r = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + k;
-  }
+  int r = KD_XCD_CHUNK();      // XCD-aware order: neighbouring tiles (overlapping halos) run on ONE L2
   const int tx = r % tiles_x; r /= tiles_x;
   const int ty = r % tiles_y, b = r / tiles_y;
   // Each stage (head 0, head 1, hand-over + phase B) derives its lane constants afresh from an opaque copy of the thread index: values the
@@ -125,12 +120,9 @@ extern "C" int kd_attn_ffn_f32(const float* qkv, const KdFfn* dp, int batch, int
   const double M = d.M, K = d.K;
   const double flops = 4.0 * M * nh * x3a::DH * ks * ks + 2.0 * M * 3.0 * d.d_ff * K + 2.0 * M * K * K;
   const double bytes = 16.0 * M * nh * x3a::DH + 4.0 * (3.0 * M * K + 3.0 * d.d_ff * K + K * K) - 8.0 * M * K;
-  char nm[96] = "attn_ffn_x3";
-  if (prof_on()) snprintf(nm, sizeof(nm), "attn_ffn_x3 %dx%d nh=%d K=%d d_ff=%d", H, W, nh, d.K, d.d_ff);
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(x3::attn_ffn_x3h_kernel), x3::AF_LDS);
+  const ProfName nm("attn_ffn_x3", "attn_ffn_x3 %dx%d nh=%d K=%d d_ff=%d", H, W, nh, d.K, d.d_ff);
   LaunchScope prof(nm, flops, bytes, (hipStream_t)stream);
-  hipLaunchKernelGGL(x3::attn_ffn_x3h_kernel, dim3((unsigned)(d.M / 128)), dim3(256), x3::AF_LDS, (hipStream_t)stream, a, f);
+  launch<x3::attn_ffn_x3h_kernel>(dim3((unsigned)(d.M / 128)), dim3(256), x3::AF_LDS, (hipStream_t)stream, a, f);
   return check_launch("kd_attn_ffn_f32");
 }
 

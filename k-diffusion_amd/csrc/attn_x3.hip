@@ -30,12 +30,7 @@ __global__ __launch_bounds__(256, NaGeo<KS>::LDS <= 80 * 1024 ? 2 : 1) void attn
   const auto warm = code_warm_begin<10240>((int)blockIdx.x < a.warm && tid < 64);
   const x3::WgStamp wgs = x3::wg_stamp_begin(a.clk);
   const int tiles_x = (a.W + NA_TW - 1) / NA_TW, tiles_y = (a.H + NA_TH - 1) / NA_TH;
-  int r;
-  {   // XCD-aware tile order: neighbouring tiles (overlapping halos) run on ONE L2
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int q = nwg >> 3, rem = nwg & 7;
-    r = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + k;
-  }
+  int r = KD_XCD_CHUNK();      // XCD-aware order: neighbouring tiles (overlapping halos) run on ONE L2
   const int tx = r % tiles_x; r /= tiles_x;
   const int ty = r % tiles_y; r /= tiles_y;
   const int head = r % a.nh, b = r / a.nh;
@@ -248,12 +243,7 @@ __global__ __launch_bounds__((NT < 4 ? NT : 4) * 64, 2) void attn_global_x3_kern
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, h2 = lane >> 5;
   const auto warm = code_warm_begin<10240>((int)blockIdx.x < a.warm && tid < 64);
   const x3::WgStamp wgs = x3::wg_stamp_begin(a.clk);
-  int r;
-  {   // XCD-aware order: the query blocks of one (sample, head) -- same K, V -- run on ONE L2
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int q = nwg >> 3, rem = nwg & 7;
-    r = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + k;
-  }
+  int r = KD_XCD_CHUNK();      // XCD-aware order: the query blocks of one (sample, head) -- same K, V -- run on ONE L2
   const int qb = r % QB; r /= QB;
   const int head = r % a.nh, b = r / a.nh;
   const size_t row_bytes = (size_t)3 * a.nh * DH * 4;
@@ -387,12 +377,9 @@ __global__ __launch_bounds__((NT < 4 ? NT : 4) * 64, 2) void attn_global_x3_kern
 template <int NT>
 static int launch_global(const GArgs& a, hipStream_t s) {
   constexpr int QW = NT < 4 ? NT : 4, T = 32 * NT, lds = T * ROWB;
-  auto kern = attn_global_x3_kernel<NT>;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), lds);
   const long nb = (long)a.batch * a.nh * (NT / QW);
   LaunchScope prof("attn_global_x3", 4.0 * (double)a.batch * a.nh * T * T * DH, 16.0 * (double)a.batch * T * a.nh * DH, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(QW * 64), lds, s, a);
+  launch<attn_global_x3_kernel<NT>>(dim3((unsigned)nb), dim3(QW * 64), lds, s, a);
   return check_launch("kd_attn_global_f32(x3)");
 }
 
@@ -411,20 +398,12 @@ template <int KS, bool WIDE>
 static int launch_na(const x3a::NArgs& a, hipStream_t s) {
   using namespace x3a;
   constexpr int lds = WIDE ? NaWide<(WIDE ? KS : 11)>::LDS : NaGeo<(WIDE ? 7 : KS)>::LDS;
-  const void* kern;
-  if constexpr (WIDE) kern = reinterpret_cast<const void*>(attn_na2d_x3_wide_kernel<KS>);
-  else kern = reinterpret_cast<const void*>(attn_na2d_x3_kernel<KS>);
-  static LdsAttr attr_set;
-  attr_set.ensure(kern, lds);
   const long nb = (long)a.batch * a.nh * ((a.H + NA_TH - 1) / NA_TH) * ((a.W + NA_TW - 1) / NA_TW);
-  char nm[64] = "attn_na2d_x3";
-  if (prof_on()) {
-    if (KS == 7) snprintf(nm, sizeof(nm), "attn_na2d_x3 %dx%d nh=%d", a.H, a.W, a.nh);
-    else snprintf(nm, sizeof(nm), "attn_na2d_x3 k%d %dx%d nh=%d", KS, a.H, a.W, a.nh);
-  }
+  const ProfName nm = KS == 7 ? ProfName("attn_na2d_x3", "attn_na2d_x3 %dx%d nh=%d", a.H, a.W, a.nh)
+                              : ProfName("attn_na2d_x3", "attn_na2d_x3 k%d %dx%d nh=%d", KS, a.H, a.W, a.nh);
   LaunchScope prof(nm, 4.0 * a.batch * (double)a.H * a.W * a.nh * DH * KS * KS, 16.0 * a.batch * (double)a.H * a.W * a.nh * DH, s);
-  if constexpr (WIDE) hipLaunchKernelGGL(attn_na2d_x3_wide_kernel<KS>, dim3((unsigned)nb), dim3(256), lds, s, a);
-  else hipLaunchKernelGGL(attn_na2d_x3_kernel<KS>, dim3((unsigned)nb), dim3(256), lds, s, a);
+  if constexpr (WIDE) launch<attn_na2d_x3_wide_kernel<KS>>(dim3((unsigned)nb), dim3(256), lds, s, a);
+  else launch<attn_na2d_x3_kernel<KS>>(dim3((unsigned)nb), dim3(256), lds, s, a);
   return check_launch("kd_attn_na2d_f32(x3)");
 }
 

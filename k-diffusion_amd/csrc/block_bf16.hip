@@ -462,11 +462,9 @@ extern "C" int kd_attn_block_bf16(const KdGemm* dp, void* stream) {
   constexpr int LDS = 8 * WBLK + 8 * 512 * 4;          // prologue: 8 wave-private staging slots + 8 scale vectors; later ring + K / V images
   const double flops = 2.0 * d.M * 3.0 * d.K * d.K + 4.0 * (double)a.batch * a.nh * 256.0 * 256.0 * DH;
   const double bytes = 2.0 * ((double)d.M * d.K * 2.0 + 3.0 * d.K * d.K);
-  char nm[96] = "attn_block_bf16";
-  if (prof_on()) snprintf(nm, sizeof(nm), "attn_block_bf16 M=%d K=%d nh=%d", d.M, d.K, d.n_heads);
+  const ProfName nm("attn_block_bf16", "attn_block_bf16 M=%d K=%d nh=%d", d.M, d.K, d.n_heads);
   LaunchScope prof(nm, flops, bytes, s);
-#define KD_BLK(NCV, TSV) { static LdsAttr set; set.ensure(reinterpret_cast<const void*>(attn_block_bf16_kernel<NCV, TSV>), LDS); \
-    hipLaunchKernelGGL((attn_block_bf16_kernel<NCV, TSV>), dim3((unsigned)(a.batch * a.nh)), dim3(512), LDS, s, a); }
+#define KD_BLK(NCV, TSV) launch<attn_block_bf16_kernel<NCV, TSV>>(dim3((unsigned)(a.batch * a.nh)), dim3(512), LDS, s, a);
 #define KD_BLK2(NCV) { if (a.clk) KD_BLK(NCV, true) else KD_BLK(NCV, false) }
   if (d.K == 512) KD_BLK2(32) else KD_BLK2(16)
 #undef KD_BLK2
@@ -503,11 +501,9 @@ extern "C" int kd_proj_block_bf16(const KdGemm* dp, void* stream) {
   constexpr int LDS = 8 * WBLK + 8 * 512 * 4;
   const double flops = 2.0 * d.M * (double)w_rows * d.K;
   const double bytes = 2.0 * ((double)d.M * d.K + (double)w_rows * d.K + (double)d.M * d.N);
-  char nm[96] = "proj_block_bf16";
-  if (prof_on()) snprintf(nm, sizeof(nm), "proj_block_bf16<e%d> M=%d N=%d K=%d", d.epi, d.M, d.N, d.K);
+  const ProfName nm("proj_block_bf16", "proj_block_bf16<e%d> M=%d N=%d K=%d", d.epi, d.M, d.N, d.K);
   LaunchScope prof(nm, flops, bytes, s);
-#define KD_PB(NCV, EP) { static LdsAttr set; set.ensure(reinterpret_cast<const void*>(proj_block_bf16_kernel<NCV, EP>), LDS); \
-    hipLaunchKernelGGL((proj_block_bf16_kernel<NCV, EP>), dim3((unsigned)(a.groups * a.slices)), dim3(512), LDS, s, a); }
+#define KD_PB(NCV, EP) launch<proj_block_bf16_kernel<NCV, EP>>(dim3((unsigned)(a.groups * a.slices)), dim3(512), LDS, s, a);
   if (d.K == 512) { if (d.epi == KD_EPI_GEGLU) KD_PB(32, KD_EPI_GEGLU) else KD_PB(32, KD_EPI_QKV) }
   else { if (d.epi == KD_EPI_GEGLU) KD_PB(16, KD_EPI_GEGLU) else KD_PB(16, KD_EPI_QKV) }
 #undef KD_PB

@@ -487,12 +487,9 @@ extern "C" int kd_ffn_bf16(const KdFfn* dp, void* stream) {
   if (d.attn && d.K != 128) return fail(KD_EINVAL, "kd_ffn_bf16: the fused out projection needs K == 128 (K=%d)", d.K);
   if (d.K == 256) {
     constexpr int LDS256 = 9 * WBLK;
-    static LdsAttr attr256;
-    attr256.ensure(reinterpret_cast<const void*>(ffn256_kernel), LDS256);
-    char nm2[96] = "ffn_bf16";
-    if (prof_on()) snprintf(nm2, sizeof(nm2), "ffn_bf16 M=%d K=%d dff=%d", d.M, d.K, d.d_ff);
+    const ProfName nm2("ffn_bf16", "ffn_bf16 M=%d K=%d dff=%d", d.M, d.K, d.d_ff);
     LaunchScope prof2(nm2, 2.0 * d.M * (double)d.K * (3.0 * d.d_ff), 4.0 * d.M * (double)d.K + 6.0 * d.d_ff * (double)d.K, s);
-    hipLaunchKernelGGL(ffn256_kernel, dim3((unsigned)((d.M + F2_NW * 32 - 1) / (F2_NW * 32))), dim3(F2_NW * 64), LDS256, s, a);
+    launch<ffn256_kernel>(dim3((unsigned)((d.M + F2_NW * 32 - 1) / (F2_NW * 32))), dim3(F2_NW * 64), LDS256, s, a);
     return check_launch("kd_ffn_bf16");
   }
   // 1 (default) plain, 3 skewed wave pairs.  Measured equal within noise (64.5 / 68.6 us at the level-0 shape; a third form with
@@ -504,20 +501,16 @@ extern "C" int kd_ffn_bf16(const KdFfn* dp, void* stream) {
     if (!d.Wp_out) return fail(KD_EINVAL, "kd_ffn_bf16: attn without Wp_out");
     a.Att = reinterpret_cast<const u16*>(d.attn); a.Wo = reinterpret_cast<const char*>(d.Wp_out);
   }
-  auto kern = outp ? ffn_kernel<8, false, true> : (variant == 3 ? ffn_kernel<8, true> : ffn_kernel<8, false>);
-  const int panel = FF_NW * 32, threads = FF_NW * 64;
-  const int LDS = (variant == 3 && !outp ? 10 : 9) * WBLK;
-  static LdsAttr attr_set[3];
-  attr_set[0].ensure(reinterpret_cast<const void*>(ffn_kernel<8, false>), 9 * WBLK);
-  attr_set[1].ensure(reinterpret_cast<const void*>(ffn_kernel<8, true>), 10 * WBLK);
-  attr_set[2].ensure(reinterpret_cast<const void*>(ffn_kernel<8, false, true>), 9 * WBLK);
-  char nm[96] = "ffn_bf16";
-  if (prof_on()) snprintf(nm, sizeof(nm), "%s M=%d K=%d dff=%d", outp ? "ffn_bf16+out" : "ffn_bf16", d.M, d.K, d.d_ff);
+  const int panel = FF_NW * 32;
+  const dim3 grid((unsigned)((d.M + panel - 1) / panel)), block(FF_NW * 64);
+  const ProfName nm("ffn_bf16", "%s M=%d K=%d dff=%d", outp ? "ffn_bf16+out" : "ffn_bf16", d.M, d.K, d.d_ff);
   const double flops = 2.0 * d.M * (double)d.K * (3.0 * d.d_ff + (outp ? d.K : 0));
   const double bytes = (outp ? 6.0 : 4.0) * d.M * (double)d.K + 6.0 * d.d_ff * (double)d.K + (outp ? 2.0 * d.K * d.K : 0.0);
   const CfgName cfg(nm, "variant%d", variant == 3 && !outp ? 3 : 1);
   LaunchScope prof(cfg, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)((d.M + panel - 1) / panel)), dim3(threads), LDS, s, a);
+  if (outp) launch<ffn_kernel<8, false, true>>(grid, block, 9 * WBLK, s, a);
+  else if (variant == 3) launch<ffn_kernel<8, true>>(grid, block, 10 * WBLK, s, a);
+  else launch<ffn_kernel<8, false>>(grid, block, 9 * WBLK, s, a);
   return check_launch("kd_ffn_bf16");
 }
 

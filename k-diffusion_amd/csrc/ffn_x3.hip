@@ -520,25 +520,19 @@ extern unsigned long long* g_clk;      // gemm_x3.hip (kd_prof_clock_buffer)
 template <bool OUTP>
 static int launch_ffn_half(const FArgs3& a, const char* nm, double flops, double bytes, hipStream_t s) {
   constexpr int LDS = 4 * STG + 4 * 1024 + 4 * 2048;
-  auto kern = ffn_x3h_kernel<OUTP>;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
   const CfgName cfg(nm, "half1");
   LaunchScope prof(cfg, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)((a.M + 127) / 128)), dim3(256), LDS, s, a);
+  launch<ffn_x3h_kernel<OUTP>>(dim3((unsigned)((a.M + 127) / 128)), dim3(256), LDS, s, a);
   return check_launch("kd_ffn_f32");
 }
 
 template <int NC, bool OUTP = false>
 static int launch_ffn(const FArgs3& a, const char* nm, double flops, double bytes, hipStream_t s) {
-  auto kern = ffn_x3_kernel<NC, OUTP>;
   constexpr int K = NC * 16;
   constexpr int LDS = 8 * STG + 4 * (K * 4 < 1024 ? 1024 : K * 4) + 4 * 2048;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
   const CfgName cfg(nm, "half0");
   LaunchScope prof(cfg, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)((a.M + 127) / 128)), dim3(256), LDS, s, a);
+  launch<ffn_x3_kernel<NC, OUTP>>(dim3((unsigned)((a.M + 127) / 128)), dim3(256), LDS, s, a);
   return check_launch("kd_ffn_f32");
 }
 
@@ -577,13 +571,11 @@ extern "C" int kd_ffn_f32(const KdFfn* dp, void* stream) {
   a.clk = x3::g_clk;
   const double flops = 2.0 * d.M * 3.0 * d.d_ff * d.K;
   const double bytes = 4.0 * (2.0 * d.M * d.K + 3.0 * d.d_ff * d.K);
-  char nm[96] = "ffn_x3";
-  if (prof_on()) snprintf(nm, sizeof(nm), "ffn_x3 M=%d K=%d d_ff=%d", d.M, d.K, d.d_ff);
+  const ProfName nm("ffn_x3", "%s M=%d K=%d d_ff=%d", d.attn ? "ffn_x3+out" : "ffn_x3", d.M, d.K, d.d_ff);
   if (d.attn) {
     if (!d.Wp_out) return fail(KD_EINVAL, "kd_ffn_f32: attn without Wp_out");
     a.Att = reinterpret_cast<const float*>(d.attn); a.Wo = reinterpret_cast<const char*>(d.Wp_out);
     const double fl2 = flops + 2.0 * d.M * d.K * d.K, by2 = 4.0 * (3.0 * d.M * d.K + 3.0 * d.d_ff * d.K + (double)d.K * d.K);
-    if (prof_on()) snprintf(nm, sizeof(nm), "ffn_x3+out M=%d K=%d d_ff=%d", d.M, d.K, d.d_ff);
     if (d.K == 128) return x3::launch_ffn_half<true>(a, nm, fl2, by2, (hipStream_t)stream);
     return x3::launch_ffn<16, true>(a, nm, fl2, by2, (hipStream_t)stream);
   }

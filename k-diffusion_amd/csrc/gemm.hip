@@ -108,16 +108,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void gemm_kernel(const G
   const int wr = wid >> 1, wc = wid & 1;
   constexpr int NCOL = (EPI == KD_EPI_GEGLU) ? 64 : BN;   // output columns covered per tile
   const int n_tiles = (p.N + NCOL - 1) / NCOL;
-  // XCD-aware tile order: the dispatcher deals consecutive workgroups round-robin over the 8 XCDs (private
-  // L2s), so give every XCD one CONTIGUOUS chunk of the (m-tile, n-tile) space with n fastest: the n-tiles
-  // that re-read one A row-panel then run back to back on ONE L2 instead of missing in 8 of them.  The remap
-  // is a bijection for any grid size (performance only -- correctness never depends on placement).
-  int tile;
-  {
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int tile = KD_XCD_CHUNK();      // XCD-aware order, n fastest: the n-tiles of one row panel run on ONE L2
   const int nt = tile % n_tiles, mt = tile / n_tiles;
   const int m0 = mt * BM, n0 = nt * NCOL;
   const int M = p.M, N = p.N, K = p.K;
@@ -576,16 +567,12 @@ static int launch(const GemmP& d, hipStream_t s) {
   constexpr size_t LDS_BYTES = LDS_BASE + (NORM ? SCALE_TAB_MAX_K * sizeof(float) : 0);
   constexpr int NCOL = (EPI == KD_EPI_GEGLU) ? 64 : BN;
   const long tiles = (long)((d.M + BM - 1) / BM) * ((d.N + NCOL - 1) / NCOL);
-  auto kern = gemm_kernel<AMODE, NORM, EPI, PREC, KS>;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), (int)LDS_BYTES);
   const double n_eff = (EPI == KD_EPI_GEGLU) ? 2.0 * d.N : (double)d.N;
-  char nm[96] = "gemm";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_%s<a%d,n%d,e%d%s> M=%d N=%d K=%d", PREC == KD_PREC_SPLIT3 ? "bf16x3" : "f32", AMODE, (int)NORM, EPI, KS == 2 ? ",ks2" : "", d.M, d.N, d.K);
+  const ProfName nm("gemm", "gemm_%s<a%d,n%d,e%d%s> M=%d N=%d K=%d", PREC == KD_PREC_SPLIT3 ? "bf16x3" : "f32", AMODE, (int)NORM, EPI, KS == 2 ? ",ks2" : "", d.M, d.N, d.K);
   // algorithmic bytes: A once, W once, C once (+ the residual / skip / x_in operand of the epilogues that read one)
   const double r_bytes = (EPI == KD_EPI_RESIDUAL || EPI == KD_EPI_SPLIT_LERP || (EPI == KD_EPI_UNPATCH_NCHW && d.sigma)) ? 4.0 * d.M * d.N : 0.0;
   LaunchScope prof(nm, 2.0 * d.M * n_eff * d.K, 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N) + r_bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256 * KS), LDS_BYTES, s, d);
+  kd::launch<gemm_kernel<AMODE, NORM, EPI, PREC, KS>>(dim3((unsigned)tiles), dim3(256 * KS), (int)LDS_BYTES, s, d);
   return check_launch("kd_gemm_f32");
 }
 

@@ -270,13 +270,9 @@ __global__ __launch_bounds__(64 * NWV, (NC <= 8 && NWV == 4) ? 2 : 1) void gemm_
 
 template <int NC, int EPI, int NWV>
 static int launch(const GemmP& d, hipStream_t s) {
-  auto kern = gemm_astat_kernel<NC, EPI, NWV>;
   constexpr int LDS_BYTES = lds_bytes(NWV), BMW = NWV * 32;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), LDS_BYTES);
   const double n_eff = (EPI == KD_EPI_GEGLU) ? 2.0 * d.N : (double)d.N;
-  char nm[96] = "gemm_astat";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_astat<e%d> M=%d N=%d K=%d", EPI, d.M, d.N, d.K);
+  const ProfName nm("gemm_astat", "gemm_astat<e%d> M=%d N=%d K=%d", EPI, d.M, d.N, d.K);
   // panels x n-splits: aim at >= 256 workgroups (one per CU) while every split keeps >= 2 n-tiles
   const int panels = (d.M + BMW - 1) / BMW, n_tiles = d.N / (EPI == KD_EPI_GEGLU ? 64 : 128);
   int splits = 1;
@@ -285,7 +281,7 @@ static int launch(const GemmP& d, hipStream_t s) {
   LaunchScope prof(cfg, 2.0 * d.M * n_eff * d.K, 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N), s);
   GemmP e = d;
   if (option("astat_storewait", 0)) e.debug |= 32;
-  hipLaunchKernelGGL(kern, dim3((unsigned)panels, (unsigned)splits), dim3(64 * NWV), LDS_BYTES, s, e);
+  kd::launch<gemm_astat_kernel<NC, EPI, NWV>>(dim3((unsigned)panels, (unsigned)splits), dim3(64 * NWV), LDS_BYTES, s, e);
   return check_launch("kd_gemm_f32(astat)");
 }
 

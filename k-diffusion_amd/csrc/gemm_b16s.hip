@@ -247,12 +247,9 @@ __global__ __launch_bounds__(512) void gemm_b16s_kernel(const SArgs p) {
 
 template <int EPI, bool NORM>
 static int launch(const SArgs& a, const char* nm, double flops, double bytes, hipStream_t s) {
-  auto kern = gemm_b16s_kernel<EPI, NORM>;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), LDS_BYTES);
   const int hcol = EPI == KD_EPI_GEGLU ? 32 : 64;
   LaunchScope prof(nm, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.N / hcol), (unsigned)((a.M + 31) / 32)), dim3(64 * NW), LDS_BYTES, s, a);
+  kd::launch<gemm_b16s_kernel<EPI, NORM>>(dim3((unsigned)(a.N / hcol), (unsigned)((a.M + 31) / 32)), dim3(64 * NW), LDS_BYTES, s, a);
   return check_launch("kd_gemm_bf16(b16s)");
 }
 
@@ -285,8 +282,7 @@ int gemm_b16s_try(const KdGemm& d, hipStream_t s, int* rc) {
   const double n_eff = geglu ? 2.0 * d.N : (double)d.N;
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 2.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N * (d.epi == KD_EPI_RESIDUAL ? 2 : 1));
-  char nm[96] = "gemm_bf16_few_rows";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_bf16_few_rows<n%d,e%d> M=%d N=%d K=%d", d.norm ? 1 : 0, d.epi, d.M, d.N, d.K);
+  const ProfName nm("gemm_bf16_few_rows", "gemm_bf16_few_rows<n%d,e%d> M=%d N=%d K=%d", d.norm ? 1 : 0, d.epi, d.M, d.N, d.K);
   if (d.epi == KD_EPI_STORE) *rc = d.norm ? launch<KD_EPI_STORE, true>(a, nm, flops, bytes, s) : launch<KD_EPI_STORE, false>(a, nm, flops, bytes, s);
   else if (d.epi == KD_EPI_RESIDUAL && !d.norm && d.R) *rc = launch<KD_EPI_RESIDUAL, false>(a, nm, flops, bytes, s);
   else if (d.epi == KD_EPI_QKV && d.norm && d.rope_pos && d.rope_freq) *rc = launch<KD_EPI_QKV, true>(a, nm, flops, bytes, s);

@@ -270,9 +270,6 @@ constexpr int WSTAT_LDS_MAX = 144 * 1024;
 
 template <int NC, int EPI, bool NORM, int NW, bool PF, bool PIPE>
 static int launch_wstat(const GArgs& a, int lds, const char* nm, double flops, double bytes, hipStream_t s) {
-  auto kern = gemm_wstat_kernel<NC, EPI, NORM, NW, PF, PIPE>;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), WSTAT_LDS_MAX);
   const int chunks = (a.M + 31) / 32;
   int groups = cu_count() / a.n_slices;
   if (groups < 1) groups = 1;
@@ -280,7 +277,7 @@ static int launch_wstat(const GArgs& a, int lds, const char* nm, double flops, d
   if (groups > need) groups = need;
   const CfgName cfg(nm, "waves%d,pf%d,slices%d", NW, PIPE ? 2 : (PF ? 1 : 0), a.n_slices);
   LaunchScope prof(cfg, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(groups * a.n_slices)), dim3(NW * 64), lds, s, a);
+  launch_max_lds<gemm_wstat_kernel<NC, EPI, NORM, NW, PF, PIPE>>(WSTAT_LDS_MAX, dim3((unsigned)(groups * a.n_slices)), dim3(NW * 64), lds, s, a);
   return check_launch("kd_gemm_bf16(wstat)");
 }
 
@@ -317,8 +314,7 @@ int gemm_wstat_try(const KdGemm& d, hipStream_t s, int* rc) {
   const double n_eff = geglu ? 2.0 * d.N : (double)d.N;
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 2.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N) + (d.epi == KD_EPI_RESIDUAL ? 2.0 * d.M * d.N : 0.0);
-  char nm[96] = "gemm_wstat";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_bf16_wstat<e%d,n%d> M=%d N=%d K=%d", d.epi, d.norm, d.M, d.N, d.K);
+  const ProfName nm("gemm_wstat", "gemm_bf16_wstat<e%d,n%d> M=%d N=%d K=%d", d.epi, d.norm, d.M, d.N, d.K);
   // 0 plain (default), 1 next-chunk prefetch, 2 software-pipelined tiles (qkv / GEGLU at K = 128).  All three measure the same
   // within noise (profiles/r02_wstat_ablation.md): under these kernels the chip runs at 1.6-2.2 GHz (s_memtime / s_memrealtime),
   // i.e. against its power limit, where re-arranging the same work buys nothing
@@ -390,12 +386,7 @@ __global__ __launch_bounds__(LW ? 512 : 256 * BMT, (BMT == 1 && (!DEEP || LW)) ?
   const int wid = LW ? (wid_all & (NWV - 1)) : wid_all;      // compute role: position in the tile; staging role: which pieces
   const auto warm = code_warm_begin<(EPI == KD_EPI_SPLIT_LERP ? 6 : 4) * 1024>((int)blockIdx.x < p.warm && tid < 64);
   const int wc = wid & 1, wr = wid >> 1;
-  int tile;
-  {   // XCD-aware order, n fastest: the n-tiles of one row panel run back to back on ONE L2 (bijective for any grid)
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int tile = KD_XCD_CHUNK();      // XCD-aware order, n fastest: the n-tiles of one row panel run on ONE L2
   const int nt = tile % p.n_tiles_n, mt = tile / p.n_tiles_n;
   const int m0 = mt * BMR, n0 = nt * 128;
   const int K = p.K, nk = p.nk;
@@ -617,14 +608,11 @@ __global__ __launch_bounds__(LW ? 512 : 256 * BMT, (BMT == 1 && (!DEEP || LW)) ?
 
 template <int AMODE, int EPI, int BMT, bool DEEP = false, bool LW = false>
 static int launch_tiled(const TArgs& a, const char* nm, double flops, double bytes, hipStream_t s) {
-  auto kern = gemm_tiled_kernel<AMODE, EPI, BMT, DEEP, LW>;
   constexpr int LDS = (BMT == 1 ? (DEEP ? 4 : 2) : 3) * (128 * BMT * 128 + WBLK);
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
   const long tiles = (long)((a.M + 128 * BMT - 1) / (128 * BMT)) * a.n_tiles_n;
   const CfgName cfg(nm, "bm%d,lw%d,deep%d", 128 * BMT, (int)LW, (int)DEEP);       // (the loader-wave form runs on the deep ring: lw1,deep1)
   LaunchScope prof(cfg, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(LW ? 512 : 256 * BMT), LDS, s, a);
+  launch<gemm_tiled_kernel<AMODE, EPI, BMT, DEEP, LW>>(dim3((unsigned)tiles), dim3(LW ? 512 : 256 * BMT), LDS, s, a);
   return check_launch("kd_gemm_bf16(tiled)");
 }
 
@@ -643,8 +631,7 @@ int gemm_tiled_try(const KdGemm& d, hipStream_t s, int* rc) {
   a.warm = option("code_warm", KD_CODE_WARM_DEFAULT);
   const double flops = 2.0 * d.M * (double)d.N * d.K;
   const double bytes = 2.0 * ((double)d.M * d.K + (double)d.N * d.K + (double)d.M * d.N) + (d.epi != KD_EPI_STORE ? 2.0 * d.M * d.N : 0.0);
-  char nm[96] = "gemm_tiled";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_bf16_tiled<a%d,e%d> M=%d N=%d K=%d", d.a_mode, d.epi, d.M, d.N, d.K);
+  const ProfName nm("gemm_tiled", "gemm_bf16_tiled<a%d,e%d> M=%d N=%d K=%d", d.a_mode, d.epi, d.M, d.N, d.K);
   // 256-row tiles halve the weight traffic per flop; worth it once they still give every CU a workgroup
   const long tiles256 = (long)((d.M + 255) / 256) * a.n_tiles_n, tiles128 = (long)((d.M + 127) / 128) * a.n_tiles_n;
   const int bmt = option("tiled_bm", 0);
@@ -693,22 +680,10 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_astat_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
   const auto warm = code_warm_begin<(NC == 32 ? 26 : 16) * 1024>((int)blockIdx.x < p.warm && tid < 64);   // kd_common.h: this kernel's code -> L2
-  // workgroup -> (row panel, n-split).  Workgroups go to the 8 XCDs round-robin by id: with the panel count a multiple of 8 the
-  // splits of ONE panel are given ids 8 apart, i.e. they run on one XCD at about the same time and its L2 fetches the panel's rows
-  // from HBM once instead of once per split (at level 2 the 8 splits otherwise read 67 MB for an 8 MB activation).
-  int panel, split;
-  const int n_splits = p.n_slices, n_panels = gridDim.x / n_splits;
-  if ((n_panels & 7) == 0) {
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    panel = (j / n_splits) * 8 + xcd;
-    split = j % n_splits;
-  } else {
-    panel = blockIdx.x % n_panels;
-    split = blockIdx.x / n_panels;
-  }
-  const int nt_begin = (int)((long)p.n_tiles * split / n_splits), nt_end = (int)((long)p.n_tiles * (split + 1) / n_splits);
+  const PanelSplit ps = panel_split(p.n_slices, p.n_tiles);      // (at level 2 the 8 splits otherwise read 67 MB for an 8 MB activation)
+  const int nt_begin = ps.t_begin, nt_end = ps.t_end;
   const int n_tiles = nt_end - nt_begin, total = n_tiles * NK;
-  const int m0 = panel * (32 * NWV);
+  const int m0 = ps.panel * (32 * NWV);
 
   const bool probe = p.clk && blockIdx.x == 0 && tid == 0;      // kd_prof_clock_buffer: workgroup 0's time line
   if (probe) { p.clk[0] = __builtin_amdgcn_s_memtime(); p.clk[1] = __builtin_amdgcn_s_memrealtime(); }
@@ -923,16 +898,13 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_astat_kernel(
 
 template <int NC, int EPI, int NWV>
 static int launch_astat_w(const GArgs& a, int splits, const char* nm, double flops, double bytes, hipStream_t s) {
-  auto kern = gemm_astat_kernel<NC, EPI, NWV>;
   constexpr int LDS = (NWV == 4 ? 4 : 8) * WBLK + NWV * NC * 64;      // ring + one scale vector (K floats) per wave
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
   const int panels = (a.M + 32 * NWV - 1) / (32 * NWV);
   GArgs b = a;
   b.n_slices = splits;                                // (the astat kernel's use of this field: n-splits per panel)
   const CfgName cfg(nm, "rows%d,splits%d", 32 * NWV, splits);
   LaunchScope prof(cfg, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(panels * splits)), dim3(NWV * 64), LDS, s, b);
+  launch<gemm_astat_kernel<NC, EPI, NWV>>(dim3((unsigned)(panels * splits)), dim3(NWV * 64), LDS, s, b);
   return check_launch("kd_gemm_bf16(astat)");
 }
 
@@ -940,27 +912,14 @@ template <int NC, int EPI>
 static int launch_astat(const GArgs& a, const char* nm, double flops, double bytes, hipStream_t s) {
   // panels x n-splits: 128-row panels, two workgroups per CU, n-tiles split until the grid fills them ("astat_rows" = 256: the
   // 256-row / one-workgroup-per-CU form).
-  // n-splits of a panel: every workgroup pays the row prologue (about one n-tile's worth of time, profiles/r02_astat_timeline.md)
-  // and then its share of the n-tiles; the grid runs in ceil(workgroups / resident slots) rounds.  Pick the divisor of n_tiles
-  // with the smallest estimated time  rounds x (1 + tiles per split)  (ties: fewer splits = fewer redundant prologues).
-  auto pick = [&](int panels, int slots) {
-    int best = 1;
-    long best_cost = -1;
-    for (int sp = 1; sp <= a.n_tiles; ++sp) {
-      if (a.n_tiles % sp) continue;
-      const long rounds = ((long)panels * sp + slots - 1) / slots;
-      const long cost = rounds * (1 + a.n_tiles / sp);
-      if (best_cost < 0 || cost < best_cost) { best = sp; best_cost = cost; }
-    }
-    return best;
-  };
+  // n-splits of a panel: best_n_splits with the row prologue at about one n-tile's worth of time (profiles/r02_astat_timeline.md)
   const int forced = option("astat_splits", 0), rows = option("astat_rows", 0);
-  const int p256 = (a.M + 255) / 256, s256 = pick(p256, cu_count());
+  const int p256 = (a.M + 255) / 256, s256 = best_n_splits(p256, a.n_tiles, cu_count(), 1);
   // measured (harness "astat", profiles/r02_harness_astat_rows.log): the 256-row form is never faster (L1 qkv 30.4 vs 28.2 us, L2 qkv
   // 47.0 vs 38.6, the GEGLU shapes equal) -- the L2 -> LDS stream it halves is not what limits these kernels -- so it runs on request only
   const bool wide = rows == 256;
   if (wide) return launch_astat_w<NC, EPI, 8>(a, forced > 0 && forced <= a.n_tiles ? forced : s256, nm, flops, bytes, s);
-  const int s128 = pick((a.M + 127) / 128, 2 * cu_count());
+  const int s128 = best_n_splits((a.M + 127) / 128, a.n_tiles, 2 * cu_count(), 1);
   return launch_astat_w<NC, EPI, 4>(a, forced > 0 && forced <= a.n_tiles ? forced : s128, nm, flops, bytes, s);
 }
 
@@ -983,8 +942,7 @@ int gemm_astat_try(const KdGemm& d, hipStream_t s, int* rc) {
   const double n_eff = geglu ? 2.0 * d.N : (double)d.N;
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 2.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N);
-  char nm[96] = "gemm_astat";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_bf16_astat<e%d> M=%d N=%d K=%d", d.epi, d.M, d.N, d.K);
+  const ProfName nm("gemm_astat", "gemm_bf16_astat<e%d> M=%d N=%d K=%d", d.epi, d.M, d.N, d.K);
 #define KD_AS(NCV, EP) if (d.K == NCV * 16 && d.epi == EP) { *rc = launch_astat<NCV, EP>(a, nm, flops, bytes, s); return 0; }
   KD_AS(16, KD_EPI_STORE) KD_AS(16, KD_EPI_QKV) KD_AS(16, KD_EPI_GEGLU)
   KD_AS(32, KD_EPI_STORE) KD_AS(32, KD_EPI_QKV) KD_AS(32, KD_EPI_GEGLU)
@@ -1237,21 +1195,17 @@ __global__ __launch_bounds__(256, 2) void gemm_generic_bf16_kernel(const KdGemm 
 
 template <int AMODE, int EPI>
 static int launch_generic(const KdGemm& d, hipStream_t s) {
-  auto kern = gemm_generic_bf16_kernel<AMODE, EPI>;
   constexpr int LDS = 2 * WBLK + 128 * 4;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
   constexpr int NCOL = EPI == KD_EPI_GEGLU ? 64 : 128;
   const long tiles = (long)((d.M + 127) / 128) * ((d.N + NCOL - 1) / NCOL);
   const double n_eff = EPI == KD_EPI_GEGLU ? 2.0 * d.N : (double)d.N;
-  char nm[96] = "gemm_generic";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_bf16_generic<a%d,e%d> M=%d N=%d K=%d", AMODE, EPI, d.M, d.N, d.K);
+  const ProfName nm("gemm_generic", "gemm_bf16_generic<a%d,e%d> M=%d N=%d K=%d", AMODE, EPI, d.M, d.N, d.K);
   const double a_bytes = (AMODE == KD_A_PATCH_NCHW ? 4.0 : 2.0) * d.M * d.K;
   const double c_bytes = (EPI == KD_EPI_UNPATCH_NCHW ? (d.sigma ? 8.0 : 4.0) : (EPI == KD_EPI_RESIDUAL || EPI == KD_EPI_SPLIT_LERP ? 4.0 : 2.0)) * d.M * d.N;
   LaunchScope prof(nm, 2.0 * d.M * n_eff * d.K, a_bytes + 2.0 * n_eff * d.K + c_bytes, s);
   KdGemm e = d;
   if (e.rows_per_sample <= 0) e.rows_per_sample = e.M;
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), LDS, s, e);
+  launch<gemm_generic_bf16_kernel<AMODE, EPI>>(dim3((unsigned)tiles), dim3(256), LDS, s, e);
   return check_launch("kd_gemm_bf16(generic)");
 }
 

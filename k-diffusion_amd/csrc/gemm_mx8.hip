@@ -70,19 +70,10 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_astat_kernel(const MArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
   const auto warm = code_warm_begin<16 * 1024>((int)blockIdx.x < p.warm && tid < 64);
-  int panel, split;
-  const int n_splits = p.n_splits, n_panels = gridDim.x / n_splits;
-  if ((n_panels & 7) == 0) {
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    panel = (j / n_splits) * 8 + xcd;
-    split = j % n_splits;
-  } else {
-    panel = blockIdx.x % n_panels;
-    split = blockIdx.x / n_panels;
-  }
-  const int nt_begin = (int)((long)p.n_tiles * split / n_splits), nt_end = (int)((long)p.n_tiles * (split + 1) / n_splits);
+  const PanelSplit ps = panel_split(p.n_splits, p.n_tiles);
+  const int nt_begin = ps.t_begin, nt_end = ps.t_end;
   const int n_tiles = nt_end - nt_begin, total = n_tiles * NKB;
-  const int m0 = panel * 128;
+  const int m0 = ps.panel * 128;
   const bool probe = p.clk && blockIdx.x == 0 && tid == 0;
   if (probe) { p.clk[0] = __builtin_amdgcn_s_memtime(); p.clk[1] = __builtin_amdgcn_s_memrealtime(); }
 
@@ -352,12 +343,7 @@ __global__ __launch_bounds__(256, DEEP ? 1 : 2) void gemm_mx8_tiled_kernel(const
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
   const auto warm = code_warm_begin<8192>((int)blockIdx.x < p.warm && tid < 64);
   const int wc = wid & 1, wr = wid >> 1;
-  int tile;
-  {   // XCD-aware order, n fastest: the n-tiles of one row panel run back to back on ONE L2
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int tile = KD_XCD_CHUNK();      // XCD-aware order, n fastest: the n-tiles of one row panel run on ONE L2
   const int nt = tile % p.n_tiles_n, mt = tile / p.n_tiles_n;
   const int m0 = mt * 128, n0 = nt * 128;
   const char* aptr[4];
@@ -554,12 +540,9 @@ static int mx8_tiled(const KdGemm& d, hipStream_t s) {
   const bool deep = tiles <= cu_count();              // at most one tile per CU: a 4-slot ring instead of two workgroups per CU
   const double flops = 2.0 * d.M * (double)d.N * d.K;
   const double bytes = (double)d.M * d.K * (1.0 + 1.0 / 32) + (double)d.N * d.K + 2.0 * d.M * d.N * (d.epi == KD_EPI_RESIDUAL ? 2.0 : 1.0);
-  char nm[96] = "gemm_mx8_tiled";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_mx8_tiled<e%d> M=%d N=%d K=%d", d.epi, d.M, d.N, d.K);
+  const ProfName nm("gemm_mx8_tiled", "gemm_mx8_tiled<e%d> M=%d N=%d K=%d", d.epi, d.M, d.N, d.K);
   LaunchScope prof(nm, flops, bytes, s);
-#define KD_MT(NKBV, EP, DP) { constexpr int LDS = (DP ? 4 : 2) * 2 * WBLK; static LdsAttr set;                                \
-    set.ensure(reinterpret_cast<const void*>(gemm_mx8_tiled_kernel<NKBV, EP, DP>), LDS);                                          \
-    hipLaunchKernelGGL((gemm_mx8_tiled_kernel<NKBV, EP, DP>), dim3((unsigned)tiles), dim3(256), LDS, s, a); }
+#define KD_MT(NKBV, EP, DP) launch<gemm_mx8_tiled_kernel<NKBV, EP, DP>>(dim3((unsigned)tiles), dim3(256), (DP ? 4 : 2) * 2 * WBLK, s, a);
 #define KD_MT2(NKBV) { if (d.epi == KD_EPI_RESIDUAL) { if (deep) KD_MT(NKBV, KD_EPI_RESIDUAL, true) else KD_MT(NKBV, KD_EPI_RESIDUAL, false) } \
                        else { if (deep) KD_MT(NKBV, KD_EPI_STORE, true) else KD_MT(NKBV, KD_EPI_STORE, false) } }
   if (nkb == 2) KD_MT2(2) else if (nkb == 4) KD_MT2(4) else if (nkb == 6) KD_MT2(6) else KD_MT2(12)
@@ -592,16 +575,8 @@ extern "C" int kd_gemm_mx8(const KdGemm* dp, void* stream) {
           reinterpret_cast<unsigned char*>(d.C), reinterpret_cast<unsigned char*>(d.C_lo),
           d.scale, d.scale_stride, d.rows_per_sample, d.eps, d.M, d.N, n_tiles, 1,
           d.n_heads, d.qk_scale, d.rope_pos, d.rope_freq, option("code_warm", KD_CODE_WARM_DEFAULT), g_clk};
-  // n-splits of a panel: gemm_astat's cost model (rounds x (row prologue + tiles per split)), two workgroups per CU
-  const int panels = (d.M + 127) / 128, slots = 2 * cu_count();
-  int best = 1;
-  long best_cost = -1;
-  for (int sp = 1; sp <= n_tiles; ++sp) {
-    if (n_tiles % sp) continue;
-    const long rounds = ((long)panels * sp + slots - 1) / slots;
-    const long cost = rounds * (2 + n_tiles / sp);
-    if (best_cost < 0 || cost < best_cost) { best = sp; best_cost = cost; }
-  }
+  // n-splits of a panel: two workgroups per CU, a row prologue costs about two n-tiles
+  const int panels = (d.M + 127) / 128, best = best_n_splits(panels, n_tiles, 2 * cu_count(), 2);
   const int forced = option("mx8_splits", 0);
   a.n_splits = forced > 0 && forced <= n_tiles ? forced : best;
   if ((n_tiles + a.n_splits - 1) / a.n_splits > 64) return fail(KD_EINVAL, "kd_gemm_mx8: more than 64 n-tiles per workgroup (N=%d)", d.N);
@@ -609,14 +584,12 @@ extern "C" int kd_gemm_mx8(const KdGemm* dp, void* stream) {
   const double n_eff = geglu ? 2.0 * d.N : (double)d.N;
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 2.0 * (double)d.M * d.K + (d.c_split ? (1.0 + 1.0 / 32) : 2.0) * (double)d.M * d.N + n_eff * d.K;
-  char nm[96] = "gemm_mx8_astat";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_mx8_astat<e%d%s> M=%d N=%d K=%d", d.epi, d.c_split ? ",c8" : "", d.M, d.N, d.K);
+  const ProfName nm("gemm_mx8_astat", "gemm_mx8_astat<e%d%s> M=%d N=%d K=%d", d.epi, d.c_split ? ",c8" : "", d.M, d.N, d.K);
   const CfgName cfg(nm, "splits%d", a.n_splits);
   LaunchScope prof(cfg, flops, bytes, s);
   // ring + one scale vector (K floats) per wave + the channel-scale bytes of a split's n-tiles (<= 64 tiles)
-#define KD_MX(NKV, EP, C8) { constexpr int LDS = 4 * WBLK + 4 * NKV * 64 * 4 + 64 * 128; static LdsAttr set;           \
-    set.ensure(reinterpret_cast<const void*>(gemm_mx8_astat_kernel<NKV, EP, C8>), LDS);                                  \
-    hipLaunchKernelGGL((gemm_mx8_astat_kernel<NKV, EP, C8>), dim3((unsigned)(panels * a.n_splits)), dim3(256), LDS, s, a); }
+#define KD_MX(NKV, EP, C8) \
+  launch<gemm_mx8_astat_kernel<NKV, EP, C8>>(dim3((unsigned)(panels * a.n_splits)), dim3(256), 4 * WBLK + 4 * NKV * 64 * 4 + 64 * 128, s, a);
   if (d.K == 512) {
     if (d.epi == KD_EPI_GEGLU) { if (d.c_split) KD_MX(8, KD_EPI_GEGLU, true) else KD_MX(8, KD_EPI_GEGLU, false) }
     else if (d.epi == KD_EPI_QKV) KD_MX(8, KD_EPI_QKV, false) else KD_MX(8, KD_EPI_STORE, false)

@@ -85,8 +85,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const KdGemm p) {
 template <bool NORM, int EPI>
 static int launch(const KdGemm& d, hipStream_t s) {
   const double n_eff = (EPI == KD_EPI_GEGLU) ? 2.0 * d.N : (double)d.N;
-  char nm[96] = "gemm_skinny";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_skinny<n%d,e%d> M=%d N=%d K=%d", (int)NORM, EPI, d.M, d.N, d.K);
+  const ProfName nm("gemm_skinny", "gemm_skinny<n%d,e%d> M=%d N=%d K=%d", (int)NORM, EPI, d.M, d.N, d.K);
   LaunchScope prof(nm, 2.0 * d.M * n_eff * d.K,
                    4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N * (EPI == KD_EPI_RESIDUAL ? 2.0 : 1.0)), s);
   const dim3 grid((unsigned)((d.N + CB - 1) / CB), (unsigned)((d.M + ROWS - 1) / ROWS));

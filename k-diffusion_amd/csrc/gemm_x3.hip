@@ -723,27 +723,21 @@ unsigned long long* g_clk = nullptr;
 
 template <int NC, int EPI>
 static int launch(const XArgs& a0, const char* nm, double flops, double bytes, hipStream_t s, int force_splits = 0) {
-  auto kern = gemm_x3_astat_kernel<NC, EPI>;
   constexpr int K = NC * 16, NSTG = NC <= 8 ? 4 : 8;
   constexpr int LDS = NSTG * STG + 4 * (K * 4 < 1024 ? 1024 : K * 4) + 4 * 2048 + 1024;     // ring + scale vectors + store strips + per-head constants
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
   const int panels = (a0.M + 127) / 128, best = best_n_splits(panels, a0.n_tiles, (NC <= 8 ? 2 : 1) * cu_count(), 1);
   const int forced = force_splits ? force_splits : option("x3_splits", 0);
   XArgs a = a0;
   a.n_splits = forced > 0 && forced <= a0.n_tiles ? forced : best;      // (any count up to n_tiles: panel_split hands out proportional, non-empty shares)
   const CfgName cfg(nm, "splits%d", a.n_splits);
   LaunchScope prof(cfg, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(panels * a.n_splits)), dim3(256), LDS, s, a);
+  kd::launch<gemm_x3_astat_kernel<NC, EPI>>(dim3((unsigned)(panels * a.n_splits)), dim3(256), LDS, s, a);
   return check_launch("kd_gemm_f32(x3 astat)");
 }
 
 template <int EPI>
 static int launch_half(const XArgs& a0, const char* nm, double flops, double bytes, hipStream_t s) {
-  auto kern = gemm_x3h_kernel<EPI>;
   constexpr int LDS = 4 * STG + 4 * 1024 + 4 * 2048 + 1024;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
   // the same cost model as launch() with two resident workgroups per CU; a prologue costs about two half tiles
   const int panels = (a0.M + 127) / 128, best = best_n_splits(panels, a0.n_tiles, 2 * cu_count(), 2);
   const int forced = option("x3_splits", 0);
@@ -751,7 +745,7 @@ static int launch_half(const XArgs& a0, const char* nm, double flops, double byt
   a.n_splits = forced > 0 && forced <= a0.n_tiles && a0.n_tiles % forced == 0 ? forced : best;
   const CfgName cfg(nm, "splits%d", a.n_splits);
   LaunchScope prof(cfg, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(panels * a.n_splits)), dim3(256), LDS, s, a);
+  kd::launch<gemm_x3h_kernel<EPI>>(dim3((unsigned)(panels * a.n_splits)), dim3(256), LDS, s, a);
   return check_launch("kd_gemm_f32(x3 half tiles)");
 }
 
@@ -787,11 +781,10 @@ int gemm_x3_try(const GemmP& d, hipStream_t s, int* rc) {
   const double n_eff = d.epi == KD_EPI_GEGLU ? 2.0 * d.N : (double)d.N;
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N * (d.epi == KD_EPI_RESIDUAL || (unpatch && d.sigma) ? 2 : 1));
-  char nm[96] = "gemm_x3_astat";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_x3_astat<e%d> M=%d N=%d K=%d", d.epi, d.M, d.N, d.K);
-  if (d.K == 256 && d.epi != KD_EPI_RESIDUAL && !d.c_split && option("x3_half", 1)) {      // two workgroups per CU, half tiles
+  const bool half = d.K == 256 && d.epi != KD_EPI_RESIDUAL && !d.c_split && option("x3_half", 1);      // two workgroups per CU, half tiles
+  const ProfName nm("gemm_x3_astat", half ? "gemm_x3_astat<e%d,h> M=%d N=%d K=%d" : "gemm_x3_astat<e%d> M=%d N=%d K=%d", d.epi, d.M, d.N, d.K);
+  if (half) {
     a.n_tiles = d.N / (d.epi == KD_EPI_GEGLU ? 32 : 64);
-    if (prof_on()) snprintf(nm, sizeof(nm), "gemm_x3_astat<e%d,h> M=%d N=%d K=%d", d.epi, d.M, d.N, d.K);
     if (d.epi == KD_EPI_QKV) *rc = launch_half<KD_EPI_QKV>(a, nm, flops, bytes, s);
     else if (d.epi == KD_EPI_GEGLU) *rc = launch_half<KD_EPI_GEGLU>(a, nm, flops, bytes, s);
     else *rc = launch_half<KD_EPI_STORE>(a, nm, flops, bytes, s);

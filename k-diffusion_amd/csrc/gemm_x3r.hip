@@ -51,13 +51,7 @@ __global__ __launch_bounds__(LW ? 512 : 256, LW ? 2 : 1) void gemm_x3r_kernel(co
   const int wid = LW ? (wid_all & 3) : wid_all;                    // row group: rows 32 wid .. + 31 of the tile (compute AND staging role)
   const auto warm = code_warm_begin<12 * 1024>((int)blockIdx.x < p.warm && tid < 64);
   const int n_tiles = p.N / 128;
-  int tile;
-  {   // XCD-aware order: the n-tiles that re-read one row panel run back to back on ONE L2
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
-  tile = __builtin_amdgcn_readfirstlane(tile);
+  const int tile = __builtin_amdgcn_readfirstlane(KD_XCD_CHUNK());      // XCD-aware order, n fastest: the n-tiles of one row panel run on ONE L2
   const int nt = tile % n_tiles, mt = tile / n_tiles;
   const int m0 = mt * 128, n0 = nt * 128;
   const int nk = p.nk;
@@ -314,13 +308,10 @@ __global__ __launch_bounds__(LW ? 512 : 256, LW ? 2 : 1) void gemm_x3r_kernel(co
 
 template <int AMODE, int EPI, bool LW, bool PROBE>
 static int launch_lw(const RArgs& a, const char* nm, double flops, double bytes, hipStream_t s) {
-  auto kern = gemm_x3r_kernel<AMODE, EPI, LW, PROBE>;
   constexpr int LDS = NSTG * STAGE + 4 * 2048;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), LDS);
   const long tiles = (long)((a.M + 127) / 128) * (a.N / 128);
   LaunchScope prof(nm, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(LW ? 512 : 256), LDS, s, a);
+  kd::launch<gemm_x3r_kernel<AMODE, EPI, LW, PROBE>>(dim3((unsigned)tiles), dim3(LW ? 512 : 256), LDS, s, a);
   return check_launch("kd_gemm_f32(x3 residual / merge)");
 }
 template <int AMODE, int EPI>
@@ -361,8 +352,7 @@ int gemm_x3r_try(const GemmP& d, hipStream_t s, int* rc) {
   a.clk = x3::g_clk;
   const double flops = 2.0 * d.M * (double)d.N * d.K;
   const double bytes = 4.0 * ((double)d.M * d.K + (double)d.N * d.K + (double)d.M * d.N * (d.epi == KD_EPI_STORE ? 1 : 2));
-  char nm[96] = "gemm_x3r";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_x3r<a%d,e%d> M=%d N=%d K=%d", d.a_mode, d.epi, d.M, d.N, d.K);
+  const ProfName nm("gemm_x3r", "gemm_x3r<a%d,e%d> M=%d N=%d K=%d", d.a_mode, d.epi, d.M, d.N, d.K);
   if (d.a_mode == KD_A_PLAIN && d.epi == KD_EPI_RESIDUAL) *rc = launch<KD_A_PLAIN, KD_EPI_RESIDUAL>(a, nm, flops, bytes, s);
   else if (d.epi == KD_EPI_SPLIT_LERP) *rc = launch<KD_A_PLAIN, KD_EPI_SPLIT_LERP>(a, nm, flops, bytes, s);
   else if (d.a_mode == KD_A_PLAIN) *rc = launch<KD_A_PLAIN, KD_EPI_STORE>(a, nm, flops, bytes, s);

@@ -372,12 +372,9 @@ __global__ __launch_bounds__(512) void gemm_x3s_kernel(const SArgs p) {
 
 template <int EPI, int SC, int RB>
 static int launch(const SArgs& a, const char* nm, double flops, double bytes, hipStream_t s) {
-  auto kern = gemm_x3s_kernel<EPI, SC, RB>;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), lds_bytes<RB>());
   const int hcol = EPI == KD_EPI_GEGLU ? 32 : 64;
   LaunchScope prof(nm, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.N / hcol), (unsigned)((a.M + 32 * RB - 1) / (32 * RB))), dim3(64 * NW), lds_bytes<RB>(), s, a);
+  kd::launch<gemm_x3s_kernel<EPI, SC, RB>>(dim3((unsigned)(a.N / hcol), (unsigned)((a.M + 32 * RB - 1) / (32 * RB))), dim3(64 * NW), lds_bytes<RB>(), s, a);
   return check_launch("kd_gemm_f32(x3s)");
 }
 // (RB = 2, 64 rows per workgroup with every W fragment feeding two row blocks -- a third less through the L1 per row, half the workgroups --
@@ -438,8 +435,7 @@ int gemm_x3s_try(const GemmP& d, hipStream_t s, int* rc) {
   const double n_eff = geglu ? 2.0 * d.N : (double)d.N;
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N * (d.epi == KD_EPI_RESIDUAL ? 2 : 1));
-  char nm[96] = "gemm_x3s";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_x3s<n%d,e%d> M=%d N=%d K=%d", sc, d.epi, d.M, d.N, d.K);
+  const ProfName nm("gemm_x3s", "gemm_x3s<n%d,e%d> M=%d N=%d K=%d", sc, d.epi, d.M, d.N, d.K);
   if (option("x3s_trace", 0)) {                 // debugging aid (kd_set_option): one line per launch on stderr, the stream drained in front of it
     fprintf(stderr, "x3s: epi=%d norm=%d M=%d N=%d K=%d rps=%d stride=%d heads=%d packed=%d c_split=%d A=%p Wp=%p C=%p R=%p scale=%p pos=%p freq=%p\n", d.epi, d.norm, d.M, d.N, d.K,
             a.rows_per_sample, a.scale_stride, a.n_heads, a.qkv_packed, a.c_split, (const void*)a.A, (const void*)a.Wp, (void*)a.C, (const void*)a.R, (const void*)a.scale, (const void*)a.pos, (const void*)a.freq);

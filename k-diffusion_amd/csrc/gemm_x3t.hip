@@ -50,12 +50,7 @@ __global__ __launch_bounds__(512, 1) void gemm_x3_tiled_kernel(const TArgs p) {
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const auto warm = code_warm_begin<12288>((int)blockIdx.x < p.warm && tid < 64);
   const int wc = wid & 1, wr = wid >> 1;
-  int tile;
-  {   // XCD-aware order, n fastest: the n-tiles of one row panel run back to back on ONE L2 (bijective for any grid)
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int tile = KD_XCD_CHUNK();      // XCD-aware order, n fastest: the n-tiles of one row panel run on ONE L2
   const int nt = __builtin_amdgcn_readfirstlane(tile % p.n_tiles_n), mt = __builtin_amdgcn_readfirstlane(tile / p.n_tiles_n);
   const int m0 = mt * BMR, n0 = nt * NCOL;
   const int K = p.K, nk = p.nk;
@@ -271,12 +266,9 @@ __global__ __launch_bounds__(256) void norm_split_kernel(const float* __restrict
 
 template <int EPI, bool CSPLIT>
 static int launch(const TArgs& a, const char* nm, double flops, double bytes, hipStream_t s) {
-  auto kern = gemm_x3_tiled_kernel<EPI, CSPLIT>;
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), LDS_BYTES);
   const long tiles = (long)((a.M + BMR - 1) / BMR) * a.n_tiles_n;
   LaunchScope prof(nm, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(512), LDS_BYTES, s, a);
+  kd::launch<gemm_x3_tiled_kernel<EPI, CSPLIT>>(dim3((unsigned)tiles), dim3(512), LDS_BYTES, s, a);
   return check_launch("kd_gemm_f32(x3 tiled)");
 }
 
@@ -302,8 +294,7 @@ int gemm_x3t_try(const GemmP& d, hipStream_t s, int* rc) {
   const double n_eff = d.epi == KD_EPI_GEGLU ? 2.0 * d.N : (double)d.N;
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N) + (d.epi == KD_EPI_RESIDUAL ? 4.0 * d.M * d.N : 0.0);
-  char nm[96] = "gemm_x3_tiled";
-  if (prof_on()) snprintf(nm, sizeof(nm), "gemm_x3_tiled<e%d%s> M=%d N=%d K=%d", d.epi, d.c_split ? ",planes" : "", d.M, d.N, d.K);
+  const ProfName nm("gemm_x3_tiled", "gemm_x3_tiled<e%d%s> M=%d N=%d K=%d", d.epi, d.c_split ? ",planes" : "", d.M, d.N, d.K);
 #define KD_T(EP, CS) if (d.epi == EP && (d.c_split != 0) == CS) { *rc = launch<EP, CS>(a, nm, flops, bytes, s); return 0; }
   KD_T(KD_EPI_STORE, false) KD_T(KD_EPI_STORE, true) KD_T(KD_EPI_RESIDUAL, false) KD_T(KD_EPI_QKV, false)
   KD_T(KD_EPI_GEGLU, false) KD_T(KD_EPI_GEGLU, true)

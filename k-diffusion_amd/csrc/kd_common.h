@@ -76,8 +76,25 @@ struct CfgName {
   operator const char*() const { return s; }
 };
 
+// A launch-profile name: the short literal while profiling is off (nothing is formatted), the formatted long form ("kernel<...> M=.. N=..")
+// while it is on.  CfgName appends its field to either.
+struct ProfName {
+  char buf[96];
+  const char* s;
+  __attribute__((format(printf, 3, 4))) ProfName(const char* short_nm, const char* fmt, ...) : s(short_nm) {
+    if (!prof_on()) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    s = buf;
+  }
+  ProfName(const ProfName&) = delete;                // (s points into buf)
+  operator const char*() const { return s; }
+};
+
 // hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, set ONCE PER KERNEL AND DEVICE from whichever host thread launches it first.
-// One function-local `static LdsAttr` per launch site (= per kernel instantiation): a bit per device ordinal.  hipFuncSetAttribute is
+// One function-local `static LdsAttr` per kernel instantiation (launch<> below owns it): a bit per device ordinal.  hipFuncSetAttribute is
 // idempotent, so two threads racing on a kernel's first launch both set the same value before either publishes the device's bit; a thread
 // that reads the bit (acquire) launches after the attribute call that published it (release).
 struct LdsAttr {
@@ -92,6 +109,20 @@ struct LdsAttr {
   }
 };
 
+// Launch KERN with `lds_bytes` of dynamic LDS.  The kernel is a template ARGUMENT, so the static below is one per kernel instantiation
+// (also where several kernels share one function type).  launch_max_lds: for a kernel whose launches differ in their LDS size; the
+// attribute is set once, to `max_lds_bytes`.
+template <auto KERN, class... A>
+void launch_max_lds(int max_lds_bytes, dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const A&... args) {
+  static LdsAttr attr_set;
+  if (max_lds_bytes > 0) attr_set.ensure(reinterpret_cast<const void*>(KERN), max_lds_bytes);
+  hipLaunchKernelGGL(KERN, grid, block, lds_bytes, s, args...);
+}
+template <auto KERN, class... A>
+void launch(dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const A&... args) {
+  launch_max_lds<KERN>(lds_bytes, grid, block, lds_bytes, s, args...);
+}
+
 // CUs of the CURRENT device (hipGetDevice), cached per device ordinal: the grid / split / kernel-selection rules of the launchers use it
 int cu_count();
 
@@ -99,6 +130,75 @@ inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(KD_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
   return KD_OK;
+}
+
+// ---- workgroup placement ----------------------------------------------------------------------------
+// XCD-aware order of a 1-D grid: the dispatcher deals consecutive workgroups round-robin over the 8 XCDs (private L2s), so give every
+// XCD one CONTIGUOUS chunk of the work items (for a GEMM the (m-tile, n-tile) space with n fastest: the n-tiles that re-read one A
+// row-panel then run back to back on ONE L2 instead of missing in 8 of them).  The remap is a bijection for any grid size (performance
+// only -- correctness never depends on placement).
+__host__ __device__ constexpr int xcd_chunk_item(int n_workgroups, int xcd, int k) {      // item of the k-th workgroup that XCD `xcd` receives
+  const int q = n_workgroups >> 3, r = n_workgroups & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+}
+__host__ __device__ constexpr int xcd_chunk(unsigned block, int n_workgroups) { return xcd_chunk_item(n_workgroups, block & 7, block >> 3); }
+// xcd_chunk(blockIdx.x, gridDim.x) in a kernel.  A macro, so that xcd and k are computed in the kernel's own text: behind a function the
+// compiler moves k's shift below the select and schedules the scalar prologue of 18 kernels in another order than with the expression
+// written out (profiles/launch_plumbing_refactor.md).
+#define KD_XCD_CHUNK() ::kd::xcd_chunk_item((int)gridDim.x, (int)(blockIdx.x & 7), (int)(blockIdx.x >> 3))
+
+constexpr bool xcd_chunk_permutes(int n) {       // every item of [0, n) exactly once
+  unsigned long long seen = 0;
+  for (int b = 0; b < n; ++b) {
+    const int t = xcd_chunk((unsigned)b, n);
+    if (t < 0 || t >= n || (seen >> t & 1)) return false;
+    seen |= 1ull << t;
+  }
+  return true;
+}
+constexpr bool xcd_chunk_permutes_up_to(int n_max) {
+  for (int n = 1; n <= n_max; ++n)
+    if (!xcd_chunk_permutes(n)) return false;
+  return true;
+}
+static_assert(xcd_chunk_permutes_up_to(64), "xcd_chunk: a permutation of [0, n) for every grid size (both branches, every remainder mod 8)");
+
+// workgroup -> (row panel, its share [t_begin, t_end) of the n_tiles).  Workgroups go to the 8 XCDs round-robin by id: with the panel
+// count a multiple of 8 the splits of ONE panel get ids 8 apart, i.e. they run on one XCD at about the same time and its L2 fetches the
+// panel's rows from HBM once instead of once per split.
+struct PanelSplit { int panel, t_begin, t_end; };
+__device__ __forceinline__ PanelSplit panel_split(int n_splits, int n_tiles) {
+  int panel, split;
+  const int n_panels = gridDim.x / n_splits;
+  if ((n_panels & 7) == 0) {
+    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+    panel = (j / n_splits) * 8 + xcd;
+    split = j % n_splits;
+  } else {
+    panel = blockIdx.x % n_panels;
+    split = blockIdx.x / n_panels;
+  }
+  // (integer division by a run-time value goes through the vector unit: hand the uniform results back to scalar registers, or every
+  // address and per-head constant derived from them is vector arithmetic, and the s_load operands of the users become waterfall loops)
+  panel = __builtin_amdgcn_readfirstlane(panel);
+  split = __builtin_amdgcn_readfirstlane(split);
+  return PanelSplit{panel, __builtin_amdgcn_readfirstlane((int)((long)n_tiles * split / n_splits)),
+                    __builtin_amdgcn_readfirstlane((int)((long)n_tiles * (split + 1) / n_splits))};
+}
+
+// n-splits of a panel (host): every workgroup pays the row prologue (about `prologue_weight` tiles' K loops) and then its share of the
+// n-tiles; the grid runs in ceil(workgroups / resident slots) rounds.  The divisor of n_tiles with the smallest rounds x (prologue_weight
+// + tiles per split) wins (ties: fewer splits = fewer redundant prologues).
+static inline int best_n_splits(int panels, int n_tiles, int slots, int prologue_weight) {
+  int best = 1;
+  long best_cost = -1;
+  for (int sp = 1; sp <= n_tiles; ++sp) {
+    if (n_tiles % sp) continue;
+    const long rounds = ((long)panels * sp + slots - 1) / slots;
+    const long cost = rounds * (prologue_weight + n_tiles / sp);
+    if (best_cost < 0 || cost < best_cost) { best = sp; best_cost = cost; }
+  }
+  return best;
 }
 
 // ---- device helpers ---------------------------------------------------------------------------------

@@ -230,16 +230,14 @@ __global__ __launch_bounds__(PNW * 64) void patchin4_kernel(const PArgs p) {
 }
 
 
-template <auto kern>                  // (the kernel is a template ARGUMENT: one LdsAttr per kernel, although all of them share one function type)
+template <auto kern>
 static int launch_patch(const PArgs& a, int lds, const char* nm, double flops, double bytes, hipStream_t s) {
-  static LdsAttr attr_set;
-  attr_set.ensure(reinterpret_cast<const void*>(kern), 64 * 1024);
   const int chunks = (a.M + 31) / 32;
   int groups = cu_count();
   const int need = (chunks + PNW - 1) / PNW;
   if (groups > need) groups = need;
   LaunchScope prof(nm, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(PNW * 64), lds, s, a);
+  launch_max_lds<kern>(64 * 1024, dim3((unsigned)groups), dim3(PNW * 64), lds, s, a);
   return check_launch(nm);
 }
 
@@ -253,11 +251,10 @@ int gemm_patch_try(const KdGemm& d, hipStream_t s, int* rc) {
   a.scale = d.scale; a.scale_stride = d.scale_stride; a.rows_per_sample = d.rows_per_sample > 0 ? d.rows_per_sample : d.M; a.eps = d.eps;
   a.M = d.M; a.N = d.N; a.K = d.K; a.gh = d.gh; a.gw = d.gw; a.ph = d.ph; a.chan = d.chan;
   a.sigma = d.sigma; a.sigma_data = d.sigma_data;
-  char nm[96];
   if (d.a_mode == KD_A_PLAIN && d.epi == KD_EPI_UNPATCH_NCHW) {
     if (d.N != feat || feat > 64 || (feat & 7) || (d.K != 128 && d.K != 256) || (d.sigma && !d.R)) return 1;
     a.A = reinterpret_cast<const u16*>(d.A); a.Cimg = d.C; a.R = d.R;
-    snprintf(nm, sizeof(nm), prof_on() ? "gemm_bf16_unpatch4 M=%d N=%d K=%d" : "gemm_unpatch4", d.M, d.N, d.K);
+    const ProfName nm("gemm_unpatch4", "gemm_bf16_unpatch4 M=%d N=%d K=%d", d.M, d.N, d.K);
     const double flops = 2.0 * d.M * d.N * (double)d.K, bytes = 2.0 * d.M * d.K + (d.sigma ? 8.0 : 4.0) * d.M * d.N + 2.0 * d.N * d.K;
     const int lds = (d.K / 64) * WBLK;
     if (d.K == 128) *rc = d.norm ? launch_patch<unpatch4_kernel<8, true>>(a, lds, nm, flops, bytes, s) : launch_patch<unpatch4_kernel<8, false>>(a, lds, nm, flops, bytes, s);
@@ -267,7 +264,7 @@ int gemm_patch_try(const KdGemm& d, hipStream_t s, int* rc) {
   if (d.a_mode == KD_A_PATCH_NCHW && d.epi == KD_EPI_STORE) {
     if (d.K != feat || feat > 64 || d.norm || (d.N & 127) || d.N > 512 || d.out_add != 0.f) return 1;
     a.img = d.A; a.Ct = reinterpret_cast<u16*>(d.C);
-    snprintf(nm, sizeof(nm), prof_on() ? "gemm_bf16_patchin4 M=%d N=%d K=%d" : "gemm_patchin4", d.M, d.N, d.K);
+    const ProfName nm("gemm_patchin4", "gemm_bf16_patchin4 M=%d N=%d K=%d", d.M, d.N, d.K);
     const double flops = 2.0 * d.M * d.N * (double)d.K, bytes = 4.0 * d.M * d.K + 2.0 * d.M * d.N + 2.0 * d.N * d.K;
     *rc = launch_patch<patchin4_kernel>(a, (d.N / 128) * WBLK, nm, flops, bytes, s);
     return 0;

@@ -169,42 +169,9 @@ __device__ __forceinline__ void qk_prep_head(const char* qkc, int head, int lh, 
   b16::qk_prep_blocks(a0, a1, rs, qsc, eps, py, px, fr);
 }
 
-// ---- workgroup -> (row panel, its share [t_begin, t_end) of the n_tiles): the splits of one panel get ids 8 apart, i.e. the same XCD (one
-// L2 fetches the panel's rows once) ------------------------------------------------------------------------------------------------------------
-struct PanelSplit { int panel, t_begin, t_end; };
-__device__ __forceinline__ PanelSplit panel_split(int n_splits, int n_tiles) {
-  int panel, split;
-  const int n_panels = gridDim.x / n_splits;
-  if ((n_panels & 7) == 0) {
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    panel = (j / n_splits) * 8 + xcd;
-    split = j % n_splits;
-  } else {
-    panel = blockIdx.x % n_panels;
-    split = blockIdx.x / n_panels;
-  }
-  // (integer division by a run-time value goes through the vector unit: hand the uniform results back to scalar registers, or every
-  // address and per-head constant derived from them is vector arithmetic, and the s_load operands of the users become waterfall loops)
-  panel = __builtin_amdgcn_readfirstlane(panel);
-  split = __builtin_amdgcn_readfirstlane(split);
-  return PanelSplit{panel, __builtin_amdgcn_readfirstlane((int)((long)n_tiles * split / n_splits)),
-                    __builtin_amdgcn_readfirstlane((int)((long)n_tiles * (split + 1) / n_splits))};
-}
-
-// n-splits of a panel (host): every workgroup pays the row prologue (about `prologue_weight` tiles' K loops) and then its share of the
-// n-tiles; the grid runs in ceil(workgroups / resident slots) rounds.  The divisor of n_tiles with the smallest rounds x (prologue_weight
-// + tiles per split) wins (ties: fewer splits = fewer redundant prologues).
-static inline int best_n_splits(int panels, int n_tiles, int slots, int prologue_weight) {
-  int best = 1;
-  long best_cost = -1;
-  for (int sp = 1; sp <= n_tiles; ++sp) {
-    if (n_tiles % sp) continue;
-    const long rounds = ((long)panels * sp + slots - 1) / slots;
-    const long cost = rounds * (prologue_weight + n_tiles / sp);
-    if (best_cost < 0 || cost < best_cost) { best = sp; best_cost = cost; }
-  }
-  return best;
-}
+using kd::PanelSplit;          // kd_common.h: workgroup placement, the n-split rule
+using kd::panel_split;
+using kd::best_n_splits;
 
 }  // namespace x3
 }  // namespace kd

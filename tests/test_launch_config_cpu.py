@@ -137,7 +137,7 @@ def test_cfg_matcher_refuses_the_right_kernel_under_another_configuration():
 
 
 def test_restated_split_rule():
-    # x3_common.h: best_n_splits -- ties go to fewer splits; one round of the chip is filled before tiles are shared out
+    # kd_common.h: best_n_splits -- ties go to fewer splits; one round of the chip is filled before tiles are shared out
     assert lc.best_n_splits(8, 12, 512, 2) == 12 and lc.best_n_splits(512, 12, 512, 2) == 1 and lc.best_n_splits(9, 6, 256, 1) == 6
     assert lc.best_n_splits(300, 4, 256, 1) == 2          # rounds x (1 + tiles): 2 x 5, 3 x 3, 5 x 2
     assert lc.tiled_cfg(300, 256, 1536, 128, 1)(256) == "bm128,lw1,deep1" and lc.tiled_cfg(300, 256, 1536, 256, 1)(256) == "bm256,lw0,deep0"

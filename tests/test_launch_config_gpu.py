@@ -55,7 +55,7 @@ def assert_served(what, names, kernel, cfg):
 # ---- host rules restated (the expected configuration where an option leaves part of the choice to the dispatch) ------------------------------------
 
 def best_n_splits(panels, n_tiles, slots, prologue_weight):
-    """x3_common.h: best_n_splits (gemm_bf16.hip's ``pick`` is the same rule with weight 1)"""
+    """kd_common.h: best_n_splits (the split3, bf16 and fp8 a-stationary launchers all call it; bf16 with weight 1)"""
     best, best_cost = 1, None
     for sp in range(1, n_tiles + 1):
         if n_tiles % sp:
@@ -124,8 +124,8 @@ def qkv(M, nh, K, mode, kernel, src, bf=False, packed=False):
 
 
 def splits_rows(table, c, option, kernel, n_tiles, splits, fmt="splits{}", extra=None):
-    """One row per forced split count.  Every count up to n_tiles is a supported configuration of the full-tile kernels: panel_split (and its copies
-    in gemm_bf16.hip / gemm_mx8.hip) hands split s the tiles [n_tiles s / S, n_tiles (s + 1) / S), which are disjoint, cover the range and are
+    """One row per forced split count.  Every count up to n_tiles is a supported configuration of the full-tile kernels: panel_split (kd_common.h; the
+    split3, bf16 and fp8 kernels share it) hands split s the tiles [n_tiles s / S, n_tiles (s + 1) / S), which are disjoint, cover the range and are
     non-empty for S <= n_tiles, and a workgroup's loop takes its tile count from that range alone -- so non-divisors are rows like any other."""
     for sp in splits:
         assert 1 <= sp <= n_tiles
