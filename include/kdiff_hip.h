@@ -550,6 +550,27 @@ int kd_augment_draw_f32(const long long* key, int batch, float a_prob, float* ra
 int kd_augment_warp_f32(const float* x, const float* raw, float a_scale, float a_aniso, float a_trans, float* y, float* cond, float* mat,
                         int batch, int chan, int H, int W, void* stream);
 
+/* Training batches from a dataset resident in device memory as uint8, and conditioning dropout of the class labels (the reference reaches
+ * CIFAR-10 / MNIST through torchvision datasets, PIL and data-loader workers, train.py:207-210, and drops labels with torch.rand, :449-450;
+ * csrc/data_u8.hip).  Neither entry point synchronises.
+ *   kd_batch_u8_f32      : out[b] = data[idx[b]] as fp32, b < batch: data [N, chan, H, W] uint8, planar (a CIFAR pickle row and an MNIST idx image
+ *                          both are), idx [batch] int64 with every entry in [0, N) -- the CALLER's check: N is not passed and nothing is
+ *                          clamped -- out [batch, chan, H, W].  Element values: (float)u / 255 * 2 - 1 with the bits of three IEEE fp32
+ *                          operations in that order (utils.from_pil_image; a 256-entry table evaluated at compile time, independent of the
+ *                          device's division flags).  chan H W < 2^31 - 256, any value (an image may start at any byte address: byte loads).
+ *                          labels [N] int64 and class_out [batch] int64 are both NULL (unlabelled data: key, drop_rate, num_classes unused)
+ *                          or both given: class_out[b] = labels[idx[b]] under the dropout rule.  out / class_out must not overlap the inputs.
+ *   kd_class_dropout_i64 : out[b] = labels[b] under the dropout rule, b < batch (labels that came through a DataLoader); out may be labels.
+ * Dropout rule (key: one int64 per call, read through a device pointer like the dropout and augmentation keys; may be NULL iff drop_rate is 0):
+ *   sample b is dropped iff u(w0) < drop_rate (fp32), u(w) = (w >> 8) / 2^24, w0 = word 0 of philox4x32_10(key, counter (b, 2^63 | 2^62 | 2^32))
+ *   (csrc/philox.h; the augmentation's blocks are 2^63 | 2^62 | j with j = 0 .. 3, the dropout sites leave bit 63 clear: no collision under
+ *   one key).  A dropped sample gets num_classes (the id of the model's extra embedding row), a kept one its label.  drop_rate 0 drops
+ *   nothing, 1 everything; 0 <= drop_rate <= 1 and num_classes > 0, KD_EINVAL otherwise.  The torch RNG stream of the reference is NOT
+ *   reproduced. */
+int kd_batch_u8_f32(const unsigned char* data, const long long* labels, const long long* idx, const long long* key, float drop_rate,
+                    int num_classes, float* out, long long* class_out, int batch, int chan, int H, int W, void* stream);
+int kd_class_dropout_i64(const long long* labels, const long long* key, float drop_rate, int num_classes, long long* out, int batch, void* stream);
+
 /* Sample-quality metrics (k_diffusion/evaluation.py:93-161; csrc/metrics_f32.hip).  fp32-grade arithmetic: the Gram tiles follow the backward
  * pass's rule (split3 = 1: bf16 hi / lo operands, 3 MFMAs per product, fp32 accumulate; 0: fp32 FMAs).  Every sum has a fixed order (fp64
  * workspace, no atomics): repeat calls give the same bits.  Matrices are row-major fp32; batch items sx / sy elements apart.

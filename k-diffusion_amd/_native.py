@@ -178,6 +178,8 @@ SIGNATURES = {
     "kd_dropout_f32": [_vp, _vp, _ll, _vp, _ull, _u, _f, _vp],
     "kd_augment_draw_f32": [_vp, _i, _f, _vp, _vp],
     "kd_augment_warp_f32": [_vp, _vp, _f, _f, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "kd_batch_u8_f32": [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _i, _i, _i, _i, _vp],
+    "kd_class_dropout_i64": [_vp, _vp, _f, _i, _vp, _i, _vp],
     "kd_row_rrms_f32": [_vp, _vp, _ll, _i, _f, _vp],
     "kd_colsum_f32": [_vp, _vp, _vp, _vp, _ll, _i, _ll, _i, _vp, _vp, _vp],
     "kd_attn_scale_grad_f32": [_vp, _vp, _i, _i, _vp, _vp],

@@ -4,8 +4,14 @@
 
 The loss, its backward, the optimizer step (gradient clipping + AdamW + EMA + gradient zeroing, K.optim.AdamW), the sigma draw and the demo
 sampler all run on this project's HIP kernels.  Differences from the reference, by design:
-  * one process, one GPU; dataset type ``imagefolder`` only (PIL, LANCZOS resize + centre crop); optimizer ``adamw`` only; no --gns, wandb or
-    evaluation;
+  * one process, one GPU; optimizer ``adamw`` only; no --gns, wandb or evaluation;
+  * dataset types ``imagefolder``, ``imagefolder-class`` and ``custom`` go through a DataLoader (PIL, LANCZOS resize + centre crop; the class
+    folders without torchvision: K.data.FolderOfImagesWithClasses); ``cifar10`` and ``mnist`` are read once from the files torchvision leaves on
+    disk -- nothing is downloaded -- and kept on the device as uint8 (K.data.DeviceImageDataset): one HIP launch assembles each step's batch,
+    there is no DataLoader, ``--num-workers`` is ignored and ``input_size`` must be the native 32 or 28; ``huggingface`` is refused;
+  * conditioning dropout (``dataset.num_classes`` > 0, ``cond_dropout_rate``) runs on the device from this project's counter-based generator
+    (K.data.class_dropout, or fused into the resident batch; one key per step from the default device generator -- not the reference's
+    torch.rand);
   * augmentation (``augment_prob`` > 0) needs ``--device-augment``: the reference's KarrasAugmentationPipeline runs per image on the data-loader
     workers with scikit-image; here K.augmentation warps the uploaded batch on the device, with parameters from this project's counter-based
     generator (one key per step from the default device generator -- not the reference's torch draws).  Without the flag such a config is
@@ -89,6 +95,36 @@ def epoch_batches(n_items, batch_size, data_seed, epoch):
     return [perm[i:i + batch_size] for i in range(0, n_items - batch_size + 1, batch_size)]
 
 
+DATASET_TYPES = ('imagefolder', 'imagefolder-class', 'cifar10', 'mnist', 'custom')
+RESIDENT_TYPES = {'cifar10': (3, 32), 'mnist': (1, 28)}        # type -> (channels, native size): kept on the device as uint8
+
+
+def check_dataset_config(config, class_emb_rows=None):
+    """Refuses, with a reason, what the data path cannot do.  ``class_emb_rows``: the rows of the built model's class-embedding table
+    (0 without one), checked against ``dataset.num_classes`` once the model exists."""
+    dataset_config, model_config = config['dataset'], config['model']
+    kind = dataset_config['type']
+    num_classes = dataset_config.get('num_classes', 0)
+    if kind == 'huggingface':
+        raise NotImplementedError("dataset type 'huggingface' is not implemented: the datasets library is not a dependency; export the images "
+                                  "to a folder (imagefolder / imagefolder-class) or wrap them in a custom dataset module")
+    if kind not in DATASET_TYPES:
+        raise ValueError(f'Invalid dataset type {kind!r}: one of {", ".join(DATASET_TYPES)}')
+    if kind == 'imagefolder' and num_classes:
+        raise NotImplementedError('dataset.num_classes > 0: an imagefolder dataset carries no class labels (use imagefolder-class)')
+    if kind in RESIDENT_TYPES:
+        channels, native = RESIDENT_TYPES[kind]
+        if list(model_config['input_size']) != [native, native]:
+            raise NotImplementedError(f'dataset type {kind!r} is kept on the device at its native {native} x {native}; input_size '
+                                      f'{list(model_config["input_size"])} would need a resize of the resident array, which is not implemented '
+                                      f'(export the images at that size to class folders and use imagefolder-class)')
+        if model_config['input_channels'] != channels:
+            raise ValueError(f'dataset type {kind!r} has {channels} channel(s); input_channels = {model_config["input_channels"]}')
+    if class_emb_rows is not None and class_emb_rows != (num_classes + 1 if num_classes else 0):
+        raise ValueError(f'dataset.num_classes = {num_classes} needs a class-embedding table of {num_classes + 1 if num_classes else 0} rows '
+                         f'(num_classes + 1: the last row is the dropped label); the model has {class_emb_rows}')
+
+
 def main(argv=None):
     args = parse_args(argv)
 
@@ -107,8 +143,7 @@ def main(argv=None):
                                   'or pass --device-augment to augment each batch on the device (K.augmentation)')
     if opt_config['type'] != 'adamw':
         raise NotImplementedError(f'optimizer type {opt_config["type"]!r}: only adamw runs on the fused HIP step')
-    if dataset_config['type'] != 'imagefolder':
-        raise NotImplementedError(f'dataset type {dataset_config["type"]!r}: only imagefolder is implemented')
+    check_dataset_config(config)
     if not torch.cuda.is_available():
         raise RuntimeError('train.py needs a ROCm device; there is no CPU fallback')
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
@@ -125,6 +160,7 @@ def main(argv=None):
     elapsed = 0.0
 
     inner_model = K.config.make_model(config)
+    check_dataset_config(config, inner_model.num_classes)
     inner_model_ema = deepcopy(inner_model)
     print(f'Parameters: {K.utils.n_params(inner_model):,}')
     inner_model, inner_model_ema = inner_model.to(device), inner_model_ema.to(device)
@@ -155,23 +191,32 @@ def main(argv=None):
 
     channels = model_config['input_channels']
     if channels not in (1, 3):
-        raise NotImplementedError(f'imagefolder yields RGB or greyscale images; input_channels = {channels}')
+        raise NotImplementedError(f'the image datasets yield RGB or greyscale images; input_channels = {channels}')
 
     def tf(image):
         image = K.utils.resize_center_crop(image, size[0])
         return K.utils.from_pil_image(image if channels == 3 else image.convert('L'))
 
-    train_set = K.utils.FolderOfImages(dataset_config['location'], transform=tf)
-    print(f'Number of items in dataset: {len(train_set):,}')
-    if len(train_set) < args.batch_size:
-        raise ValueError(f'the dataset has {len(train_set)} images, fewer than one batch of {args.batch_size}')
-
     image_key = dataset_config.get('image_key', 0)
     num_classes = dataset_config.get('num_classes', 0)
     cond_dropout_rate = dataset_config.get('cond_dropout_rate', 0.1)
     class_key = dataset_config.get('class_key', 1)
-    if num_classes:
-        raise NotImplementedError('dataset.num_classes > 0: an imagefolder dataset carries no class labels')
+
+    resident = dataset_config['type'] in RESIDENT_TYPES
+    if resident:                                     # the whole training set on the device as uint8; each step's batch is one launch
+        read = K.data.read_cifar10 if dataset_config['type'] == 'cifar10' else K.data.read_mnist
+        train_set = K.data.DeviceImageDataset(*read(dataset_config['location']), device=device, num_classes=num_classes or None)
+        print(f'Dataset resident on the device ({train_set.images.numel() / 2 ** 20:.1f} MiB of uint8): no data loader, --num-workers is '
+              f'ignored', flush=True)
+    elif dataset_config['type'] == 'imagefolder':
+        train_set = K.utils.FolderOfImages(dataset_config['location'], transform=tf)
+    elif dataset_config['type'] == 'imagefolder-class':
+        train_set = K.data.FolderOfImagesWithClasses(dataset_config['location'], transform=tf)
+    else:
+        train_set = K.data.load_custom(args.config, dataset_config, tf)
+    print(f'Number of items in dataset: {len(train_set):,}')
+    if len(train_set) < args.batch_size:
+        raise ValueError(f'the dataset has {len(train_set)} images, fewer than one batch of {args.batch_size}')
 
     sigma_min = model_config['sigma_min']
     sigma_max = model_config['sigma_max']
@@ -274,24 +319,30 @@ def main(argv=None):
     try:
         while True:
             batches = epoch_batches(len(train_set), args.batch_size, data_seed, epoch)[batch_in_epoch:]
-            train_dl = data.DataLoader(train_set, batch_sampler=batches, num_workers=args.num_workers, pin_memory=True,
-                                       generator=torch.Generator().manual_seed(data_seed + epoch)) if batches else ()
+            if resident:
+                train_dl = batches
+            else:
+                train_dl = data.DataLoader(train_set, batch_sampler=batches, num_workers=args.num_workers, pin_memory=True,
+                                           generator=torch.Generator().manual_seed(data_seed + epoch)) if batches else ()
             for batch in train_dl:
                 torch.cuda.synchronize()
                 start_timer = time.time()
 
                 sync_gradients = (step + 1) % accum == 0
-                reals = batch[image_key].to(device, non_blocking=True)
+                extra_args = {}
+                # conditioning dropout: the key comes from the default device generator, so its state is in the checkpoint
+                drop_key = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device=device) if num_classes else None
+                if resident:
+                    reals, class_cond = train_set.batch(batch, drop_key, cond_dropout_rate, num_classes)
+                else:
+                    reals = batch[image_key].to(device, non_blocking=True)
+                    class_cond = K.data.class_dropout(batch[class_key].to(device, torch.int64), drop_key, cond_dropout_rate, num_classes) if num_classes else None
+                if num_classes:
+                    extra_args['class_cond'] = class_cond
                 if aug is not None:                  # the key comes from the default device generator: its state is in the checkpoint
                     reals, _, aug_cond = aug.batch(reals)
                 else:
                     aug_cond = reals.new_zeros([reals.shape[0], 9])
-                extra_args = {}
-                if num_classes:
-                    class_cond = batch[class_key].to(device)
-                    drop = torch.rand(class_cond.shape, device=class_cond.device)
-                    class_cond.masked_fill_(drop < cond_dropout_rate, num_classes)
-                    extra_args['class_cond'] = class_cond
                 noise = torch.randn_like(reals)
                 with K.utils.enable_stratified(step % accum, accum):
                     sigma = sample_density([reals.shape[0]], device=device)
