@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Forward time of the image_v1 U-Net on the HIP kernels against the same architecture as plain torch in fp32 on the same GPU.
+
+Two models: the CIFAR-shaped one (depths [2, 4, 4], channels [128, 256, 512], 3 x 32 x 32, batch 64) and the MNIST-shaped one (channels
+[128, 128, 256], 1 x 28 x 28, batch 4), both with the augment wrapper and synthetic weights.  Per model: 10 warm-up forwards of each side, then 7
+samples of each, alternating, timed with HIP events; reported as median [min, max] in ms.  The torch side is tests/unet_ref.py's functional
+forward on the device (torch's conv / group-norm / SDPA kernels, depthwise resampling): the yardstick, not the code under test.
+
+``--profile`` instead runs 3 warm-up + 5 HIP forwards of ONE model and nothing else, for a kernel trace of its own:
+    rocprofv3 --kernel-trace --stats -d <dir> -- python benchmarks/unet_bench.py --profile cifar
+Prints one JSON line per model.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+MODELS = {
+    "cifar": ({"type": "image_v1", "input_channels": 3, "input_size": [32, 32], "mapping_out": 256, "depths": [2, 4, 4], "channels": [128, 256, 512],
+               "self_attn_depths": [False, True, True], "augment_wrapper": True, "sigma_data": 0.5, "sigma_min": 1e-2, "sigma_max": 80}, 64),
+    "mnist": ({"type": "image_v1", "input_channels": 1, "input_size": [28, 28], "mapping_out": 256, "depths": [2, 4, 4], "channels": [128, 128, 256],
+               "self_attn_depths": [False, False, True], "augment_wrapper": True, "sigma_data": 0.6162, "sigma_min": 1e-2, "sigma_max": 80}, 4),
+}
+
+
+def conv_flops(model, B, H, W):
+    """2 M N K of every convolution kd_conv2d_x3 serves in one forward (3 x 3, 1 x 1 skip / qkv / out projections)."""
+    import k_diffusion_amd as K
+    inner = model.inner_model
+    plan = inner._plan(B, H, W, torch.device("cuda", torch.cuda.current_device()))
+    total = 0.0
+    for call in plan.calls:
+        if call.func is K.unet_ops.conv2d:
+            x, w, b, h, ww = call.args[:5]
+            total += 2.0 * b * h * ww * w.shape[0] * w.shape[1] * w.shape[2] * w.shape[3]
+    return total
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--profile", choices=sorted(MODELS))
+    ap.add_argument("--models", nargs="*", default=["cifar", "mnist"])
+    ap.add_argument("--no-torch", action="store_true")
+    args = ap.parse_args()
+    import k_diffusion_amd as K
+    from tests import unet_ref as ur
+    ur.USE_SDPA = True
+    dev = torch.device("cuda")
+    for name in ([args.profile] if args.profile else args.models):
+        mc, B = MODELS[name]
+        cfg = K.config.load_config({"model": mc, "dataset": {"type": "imagefolder", "num_classes": 0}})
+        model = K.config.make_model(cfg).eval().requires_grad_(False)
+        sd = K.synth.synth_state_dict(model.state_dict(), seed=1)
+        model.load_state_dict(sd)
+        model = model.to(dev)
+        C, (H, W) = mc["input_channels"], mc["input_size"]
+        g = torch.Generator().manual_seed(3)
+        sigma = torch.exp(torch.randn(B, generator=g) * 1.2 - 1.2).to(dev)
+        x = (torch.randn(B, C, H, W, generator=g).to(dev) * (sigma ** 2 + 0.25).sqrt()[:, None, None, None]).contiguous()
+        aug = (0.5 * torch.randn(B, 9, generator=g)).to(dev)
+        hip = lambda: model(x, sigma, aug_cond=aug)
+        with torch.no_grad():
+            if args.profile:
+                for _ in range(8):
+                    hip()
+                torch.cuda.synchronize()
+                continue
+            sd_dev = ur.prepare(sd, torch.float32, dev)
+            ref = lambda: ur.forward(sd_dev, x, sigma, aug_cond=aug, dtype=torch.float32, device=dev, grouped_resample=True, prepared=True)
+            for _ in range(10):
+                hip()
+                if not args.no_torch:
+                    ref()
+            torch.cuda.synchronize()
+            t_hip, t_ref = [], []
+            for _ in range(7):
+                t_hip.append(timed(hip))
+                if not args.no_torch:
+                    t_ref.append(timed(ref))
+            err = None if args.no_torch else ((hip() - ref()).abs().max() / ref().abs().max()).item()
+        flops = conv_flops(model, B, H, W)
+        line = {"model": name, "batch": B, "hip_ms": [statistics.median(t_hip), min(t_hip), max(t_hip)],
+                "torch_fp32_ms": None if args.no_torch else [statistics.median(t_ref), min(t_ref), max(t_ref)],
+                "hip_vs_torch_rel_diff": err, "conv_gflop_per_forward": flops / 1e9, "launches_per_forward": len(model.inner_model._plan(B, H, W, x.device).calls) + 6}
+        print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -662,6 +662,43 @@ int kd_mt_lerp_f32(const KdMtTensor* table, const int* chunks, int n_chunks, dou
 int kd_sigma_density_f32(int kind, const void* u, int u_f64, const void* normal, void* out, int out_f64, long long n, int row_len, int group,
                          int groups, const double* params, void* stream);
 
+/* ---- image_v1 U-Net (k_diffusion/models/image_v1.py), forward only (csrc/conv_x3.hip, csrc/unet_f32.hip) ----
+ * Activations are fp32 NHWC, token-major [batch * H * W, C]; every `ld*` is a row stride in floats (>= the row's channels, a multiple of 4),
+ * so an operand may be one column range of a wider buffer (the halves of a skip concatenation).  Rows are 16-byte aligned.  The kernels read
+ * no library option, use no atomics, and give the same bits on every run.
+ *
+ * kd_pack_conv_x3     w [c_out, c_in, ks, ks] fp32 (nn.Conv2d's layout) -> `out`, 4 * ks * ks * c_out * c_in bytes: a hi image then a lo image,
+ *                     each [ks * ks taps][c_out][c_in] bf16 with hi = bf16(w), lo = bf16(w - hi).
+ * kd_conv2d_x3        y = conv2d(x, w, padding = ks / 2) + bias + res for ks = 1 or 3, stride 1, in the split-bf16x3 arithmetic (three bf16 MFMAs
+ *                     per product, fp32 accumulation).  c_in and c_out are multiples of 64.  bias [c_out] and res (row stride ldr) may be NULL.
+ *                     y must not overlap x (a workgroup reads the halo of pixels other workgroups write); y may be res.
+ * kd_groupnorm_stats_f32   stats [batch, groups, 4] = {mean_hi, mean_lo, rstd, 0} per (sample, group) over (chan / groups channels x hw pixels):
+ *                     mean_hi + mean_lo is the fp64 mean, rstd = 1 / sqrt(biased variance + eps) (F.group_norm), sums in fp64.
+ * kd_adagn_apply_f32  y = (x - mean) * rstd * (1 + w_b) + b_b with w_b = wb[b * wb_stride + c], b_b = wb[b * wb_stride + chan + c] (the two
+ *                     chunks of AdaGN's mapper output), then the exact (erf) GELU if `gelu`.  y may be x.
+ * kd_down2_f32 / kd_up2_f32   Downsample2d / Upsample2d with the 'linear' kernel and 'reflect' padding: [H, W] -> [H / 2, W / 2] (H, W even) and
+ *                     [H, W] -> [2 H, 2 W]; H, W >= 2.  y must not overlap x.
+ * kd_unet_in_f32      y[pixel][n] = bias[n] + sum_k w[n][k] * img[b][k][pixel] * c_in(b) for an NCHW image of c_img channels; c_in(b) =
+ *                     1 / sqrt(sigma_b^2 + sigma_data^2), or 1 when sigma is NULL.
+ * kd_unet_out_f32     F[b][o][pixel] = bias[o] + sum_n w[o][n] * x[pixel][n] for c_img <= 4 image channels, written NCHW; with sigma:
+ *                     out = F * c_out(b) + img * c_skip(b) (the Karras preconditioning, k_diffusion/layers.py:88-90).
+ * kd_cond_mlp_f32     y [rows, n_out] = act(x [rows, k_in] w[n_out, k_in]^T + bias + add) in fp32 FMAs, act = exact GELU if `gelu`; bias [n_out]
+ *                     and add [rows, n_out] may be NULL.  Meant for a few rows (the conditioning vectors of a batch). */
+int kd_pack_conv_x3(const float* w, void* out, int c_out, int c_in, int ks, void* stream);
+int kd_conv2d_x3(const float* x, int ldx, const void* wp, const float* bias, const float* res, int ldr, float* y, int ldy, int batch, int H, int W,
+                 int c_in, int c_out, int ks, void* stream);
+int kd_groupnorm_stats_f32(const float* x, int ldx, float* stats, int batch, int hw, int chan, int groups, float eps, void* stream);
+int kd_adagn_apply_f32(const float* x, int ldx, const float* stats, const float* wb, int wb_stride, float* y, int ldy, int batch, int hw, int chan,
+                       int groups, int gelu, void* stream);
+int kd_down2_f32(const float* x, int ldx, float* y, int ldy, int batch, int H, int W, int chan, void* stream);
+int kd_up2_f32(const float* x, int ldx, float* y, int ldy, int batch, int H, int W, int chan, void* stream);
+int kd_unet_in_f32(const float* img, const float* w, const float* bias, const float* sigma, float sigma_data, float* y, int ldy, int batch, int hw,
+                   int c_img, int chan, void* stream);
+int kd_unet_out_f32(const float* x, int ldx, const float* w, const float* bias, const float* img, const float* sigma, float sigma_data, float* out,
+                    int batch, int hw, int c_img, int chan, void* stream);
+int kd_cond_mlp_f32(const float* x, const float* w, const float* bias, const float* add, float* y, int rows, int n_out, int k_in, int gelu,
+                    void* stream);
+
 /* Final image conversion (k_diffusion/utils.py:27-34 to_pil_image): u8 = trunc((clamp(x,-1,1)+1)/2*255)
  * (torchvision's to_pil_image does mul(255).byte(), i.e. truncation) */
 int kd_to_uint8(const float* x, unsigned char* y, long long n, void* stream);

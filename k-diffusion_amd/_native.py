@@ -180,6 +180,15 @@ SIGNATURES = {
     "kd_augment_warp_f32": [_vp, _vp, _f, _f, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "kd_batch_u8_f32": [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _i, _i, _i, _i, _vp],
     "kd_class_dropout_i64": [_vp, _vp, _f, _i, _vp, _i, _vp],
+    "kd_pack_conv_x3": [_vp, _vp, _i, _i, _i, _vp],
+    "kd_conv2d_x3": [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "kd_groupnorm_stats_f32": [_vp, _i, _vp, _i, _i, _i, _i, _f, _vp],
+    "kd_adagn_apply_f32": [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "kd_down2_f32": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    "kd_up2_f32": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    "kd_unet_in_f32": [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _vp],
+    "kd_unet_out_f32": [_vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
+    "kd_cond_mlp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "kd_row_rrms_f32": [_vp, _vp, _ll, _i, _f, _vp],
     "kd_colsum_f32": [_vp, _vp, _vp, _vp, _ll, _i, _ll, _i, _vp, _vp, _vp],
     "kd_attn_scale_grad_f32": [_vp, _vp, _i, _i, _vp, _vp],

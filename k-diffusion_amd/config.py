@@ -2,9 +2,10 @@
 
 Mirrors the call surface of k_diffusion/config.py: ``load_config`` (:23-146, JSON file, dict, or the
 ``config`` entry of a safetensors checkpoint's metadata), ``make_model`` (:149-213, the
-image_transformer_v2 branch) and ``make_denoiser_wrapper`` (:216-231).  The merged dict has the
-same keys and defaults as the reference's, so configs and checkpoints are interchangeable.  The
-U-Net / transformer-v1 model families and ``make_sample_density`` (training) are out of scope.
+image_transformer_v2 branch and, for sampling, the image_v1 U-Net branch with its augment wrapper) and
+``make_denoiser_wrapper`` (:216-231).  The merged dict has the same keys and defaults as the
+reference's, so configs and checkpoints are interchangeable.  The transformer-v1 model family is out
+of scope; ``make_sample_density`` lives in ``training``.
 """
 import json
 from functools import partial
@@ -105,8 +106,16 @@ def _attention_spec(sa):
 def make_model(config):
     num_classes = config['dataset']['num_classes']
     m = config['model']
+    if m['type'] == 'image_v1':
+        # config.py:153-171: the U-Net, for sampling (models/image_v1.py states the supported subset and refuses the rest by field name)
+        model = models.ImageDenoiserModelV1(
+            m['input_channels'], m['mapping_out'], m['depths'], m['channels'], m['self_attn_depths'], m['cross_attn_depths'],
+            patch_size=m['patch_size'], dropout_rate=m['dropout_rate'],
+            mapping_cond_dim=m['mapping_cond_dim'] + (9 if m['augment_wrapper'] else 0), unet_cond_dim=m['unet_cond_dim'],
+            cross_cond_dim=m['cross_cond_dim'], skip_stages=m['skip_stages'], has_variance=m['has_variance'])
+        return models.image_v1.AugmentWrapperV1(model) if m['augment_wrapper'] else model
     if m['type'] != 'image_transformer_v2':
-        raise ValueError(f'unsupported model type {m["type"]}: only image_transformer_v2 is on the MI355X sampling hot path')
+        raise ValueError(f'unsupported model type {m["type"]}: image_transformer_v2 and image_v1 (sampling only) are on the MI355X hot path')
     v2 = models.image_transformer_v2
     per_level = (m['depths'], m['widths'], m['d_ffs'], m['self_attns'], m['dropout_rate'])
     assert all(len(p) == len(m['widths']) for p in per_level)

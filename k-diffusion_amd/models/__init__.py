@@ -1,4 +1,5 @@
-"""Denoiser networks.  Only the hourglass transformer (image_transformer_v2) is on the MI355X hot
-path; the reference's U-Net (image_v1) and transformer v1 families are out of scope."""
-from . import axial_rope, flops, image_transformer_v2  # noqa: F401
+"""Denoiser networks on the MI355X hot path: the hourglass transformer (image_transformer_v2; sampling, likelihood and training) and the
+reference's U-Net (image_v1; sampling only).  The transformer v1 family is out of scope."""
+from . import axial_rope, flops, image_transformer_v2, image_v1  # noqa: F401
 from .image_transformer_v2 import ImageTransformerDenoiserModelV2  # noqa: F401
+from .image_v1 import ImageDenoiserModelV1  # noqa: F401

@@ -1,0 +1,382 @@
+"""The reference's U-Net denoiser (k_diffusion/models/image_v1.py: ``ImageDenoiserModelV1``) for SAMPLING on the HIP kernels of
+csrc/conv_x3.hip and csrc/unet_f32.hip (wrappers: ``unet_ops``).
+
+The module tree below exists to carry the reference's parameters under the reference's names -- ``state_dict()`` has its keys and shapes,
+so a k-diffusion checkpoint loads as it is -- and no sub-module's ``forward`` is ever called.  The model's forward is a fixed list of
+kernel launches over fp32 NHWC token buffers ``[B H W, C]``, built once per (batch, height, width):
+
+* a 3 x 3 / 1 x 1 convolution is one ``kd_conv2d_x3`` launch (bias, residual and the output's row stride in its epilogue);
+* AdaGN (+ the GELU behind it) is a statistics pass and an apply pass; the (weight, bias) pairs of ALL AdaGN mappers come from one
+  ``kd_cond_mlp_f32`` launch over the mappers' concatenated weight;
+* ``torch.cat([x, skip], 1)`` is two column ranges of one buffer which their producers write through the row stride;
+* self-attention is ``ops.attn_global`` on the qkv convolution's output as it stands; SDPA's scale 1 / 8 (heads of 64) is folded into the q
+  rows of the packed qkv weight and bias, which is exact;
+* with ``forward_preconditioned`` the Karras scalings ride in ``proj_in`` / ``proj_out``.
+
+Scope: the forward pass in fp32-grade (split-bf16x3) arithmetic whatever ``KDIFF_GEMM`` says, ``patch_size == 1``, ``skip_stages == 0``, no
+variance output, no cross attention, no ``unet_cond``, channels that are multiples of 64, even H and W at every downsample.  Anything else is
+refused in the constructor; training (grad mode with something that requires grad) raises NotImplementedError.
+"""
+from functools import partial
+
+import torch
+from torch import nn
+
+from .. import ops
+from .. import unet_ops as uo
+from ..augmentation import KarrasAugmentWrapper
+
+_LINEAR = [1 / 8, 3 / 8, 3 / 8, 1 / 8]
+
+
+class _AdaGN(nn.Module):
+    """layers.py:162-175 (parameters only)."""
+
+    def __init__(self, feats_in, c_out, num_groups, eps=1e-5):
+        super().__init__()
+        self.num_groups, self.eps, self.c_out = num_groups, eps, c_out
+        self.mapper = nn.Linear(feats_in, c_out * 2)
+        nn.init.zeros_(self.mapper.weight)
+        nn.init.zeros_(self.mapper.bias)
+
+
+class _Resample(nn.Module):
+    """layers.py:251-280 (the 'linear' kernel buffer only; the kernels carry its values)."""
+
+    def __init__(self, up):
+        super().__init__()
+        k = torch.tensor([_LINEAR]) * (2 if up else 1)
+        self.up = up
+        self.register_buffer('kernel', k.T @ k)
+
+
+class _ResConvBlock(nn.Module):
+    """image_v1.py:15-29."""
+
+    def __init__(self, feats_in, c_in, c_mid, c_out, group_size=32, dropout_rate=0.):
+        super().__init__()
+        self.c_in, self.c_mid, self.c_out = c_in, c_mid, c_out
+        self.main = nn.Sequential(
+            _AdaGN(feats_in, c_in, max(1, c_in // group_size)), nn.GELU(), nn.Conv2d(c_in, c_mid, 3, padding=1),
+            nn.Dropout2d(dropout_rate, inplace=True),
+            _AdaGN(feats_in, c_mid, max(1, c_mid // group_size)), nn.GELU(), nn.Conv2d(c_mid, c_out, 3, padding=1),
+            nn.Dropout2d(dropout_rate, inplace=True))
+        if c_in == c_out:
+            self.skip = nn.Identity()
+        else:
+            self.skip = nn.Conv2d(c_in, c_out, 1, bias=False)
+            nn.init.orthogonal_(self.skip.weight)
+        nn.init.zeros_(self.main[-2].weight)
+        nn.init.zeros_(self.main[-2].bias)
+
+
+class _SelfAttention2d(nn.Module):
+    """layers.py:181-200."""
+
+    def __init__(self, feats_in, c_in, n_head, num_groups, dropout_rate=0.):
+        super().__init__()
+        self.c_in = self.c_out = c_in
+        self.n_head = n_head
+        self.norm_in = _AdaGN(feats_in, c_in, num_groups)
+        self.qkv_proj = nn.Conv2d(c_in, c_in * 3, 1)
+        self.out_proj = nn.Conv2d(c_in, c_in, 1)
+        self.dropout = nn.Dropout(dropout_rate)
+        nn.init.zeros_(self.out_proj.weight)
+        nn.init.zeros_(self.out_proj.bias)
+
+
+def _block_layers(n_layers, feats_in, c_in, c_mid, c_out, self_attn, dropout_rate, group_size=32, head_size=64):
+    mods = []
+    for i in range(n_layers):
+        my_c_in = c_in if i == 0 else c_mid
+        my_c_out = c_mid if i < n_layers - 1 else c_out
+        mods.append(_ResConvBlock(feats_in, my_c_in, c_mid, my_c_out, group_size, dropout_rate))
+        if self_attn:
+            mods.append(_SelfAttention2d(feats_in, my_c_out, max(1, my_c_out // head_size), max(1, my_c_out // group_size), dropout_rate))
+    return mods
+
+
+class _UNet(nn.Module):
+    def __init__(self, d_blocks, u_blocks):
+        super().__init__()
+        self.d_blocks = nn.ModuleList(d_blocks)
+        self.u_blocks = nn.ModuleList(u_blocks)
+        self.skip_stages = 0
+
+
+class _MappingNet(nn.Sequential):
+    """image_v1.py:80-86."""
+
+    def __init__(self, feats_in, feats_out, n_layers=2):
+        mods = []
+        for i in range(n_layers):
+            lin = nn.Linear(feats_in if i == 0 else feats_out, feats_out)
+            nn.init.orthogonal_(lin.weight)
+            mods += [lin, nn.GELU()]
+        super().__init__(*mods)
+
+
+class _Plan:
+    """Buffers and the fixed launch list of one (batch, H, W): ``head`` / ``tail`` take the call's own tensors, ``calls`` is everything between."""
+
+    def __init__(self, model, B, H, W, device):
+        n, ch = len(model.depths), model.channels
+        sizes = [(H >> i, W >> i) for i in range(n)]
+        for i in range(n - 1):
+            if sizes[i][0] % 2 or sizes[i][1] % 2 or min(sizes[i]) < 2:
+                raise ValueError(f"image_v1: input size {H}x{W}: level {i} is {sizes[i][0]}x{sizes[i][1]}, which the downsample cannot halve")
+        f32 = dict(device=device, dtype=torch.float32)
+        feats = model.feats_in
+        self.B, self.calls, pool = B, [], {}
+        self.ff, self.e, self.h1, self.h2 = (torch.empty(B, feats, **f32) for _ in range(4))
+
+        def alloc(rows, cols):
+            free_list = pool.get((rows, cols))
+            return free_list.pop() if free_list else torch.empty(rows, cols, **f32)
+
+        def free(t):
+            if t.is_contiguous() and t.storage_offset() == 0:          # (a column range of a concat buffer is not the pool's)
+                pool.setdefault(tuple(t.shape), []).append(t)
+
+        # every AdaGN mapper in one weight: its (weight, bias) pair is a column range of the table
+        norms = [m for m in model.u_net.modules() if isinstance(m, _AdaGN)]
+        self.map_w = torch.cat([m.mapper.weight.detach() for m in norms]).contiguous()
+        self.map_b = torch.cat([m.mapper.bias.detach() for m in norms]).contiguous()
+        self.table = torch.empty(B, self.map_w.shape[0], **f32)
+        offsets, off = {}, 0
+        for m in norms:
+            offsets[m] = off
+            off += 2 * m.c_out
+        emit = self.calls.append
+
+        def adagn(norm, x, out, gelu):
+            stats = torch.empty(B, norm.num_groups, 4, **f32)
+            wb = self.table[:, offsets[norm]:offsets[norm] + 2 * norm.c_out]
+            emit(partial(uo.groupnorm_stats, x, B, norm.num_groups, norm.eps, out=stats))
+            emit(partial(uo.adagn_apply, x, stats, wb, gelu=gelu, out=out))
+
+        def conv(x, weight, hw, bias=None, residual=None, out=None):
+            emit(partial(uo.conv2d, x, weight, B, hw[0], hw[1], bias=bias, residual=residual, out=out, packed=uo.pack_conv(weight)))
+
+        def res_block(layer, x, y, hw):
+            rows = x.shape[0]
+            t1 = alloc(rows, layer.c_in)
+            adagn(layer.main[0], x, t1, True)
+            t2 = alloc(rows, layer.c_mid)
+            conv(t1, layer.main[2].weight, hw, bias=layer.main[2].bias, out=t2)
+            free(t1)
+            adagn(layer.main[4], t2, t2, True)
+            res = x
+            if isinstance(layer.skip, nn.Conv2d):
+                res = alloc(rows, layer.c_out)
+                conv(x, layer.skip.weight, hw, out=res)
+            conv(t2, layer.main[6].weight, hw, bias=layer.main[6].bias, residual=res, out=y)
+            free(t2)
+            if res is not x:
+                free(res)
+
+        def attention(layer, x, y, hw):
+            rows, C = x.shape[0], layer.c_in
+            t1 = alloc(rows, C)
+            adagn(layer.norm_in, x, t1, False)
+            # SDPA scales q k^T by 1 / sqrt(64): a power of two, folded into the q rows (the first C output channels) exactly
+            wq, bq = layer.qkv_proj.weight.detach().clone(), layer.qkv_proj.bias.detach().clone()
+            wq[:C] *= 0.125
+            bq[:C] *= 0.125
+            qkv = alloc(rows, 3 * C)
+            emit(partial(uo.conv2d, t1, wq, B, hw[0], hw[1], bias=bq, out=qkv, packed=uo.pack_conv(wq, cache=False)))
+            free(t1)
+            a = alloc(rows, C)
+            emit(partial(ops.attn_global, qkv.view(B, hw[0] * hw[1], 3 * C), layer.n_head, out=a.view(B, hw[0] * hw[1], C)))
+            free(qkv)
+            conv(a, layer.out_proj.weight, hw, bias=layer.out_proj.bias, residual=x, out=y)
+            free(a)
+
+        def run_layer(layer, x, y, hw):
+            (res_block if isinstance(layer, _ResConvBlock) else attention)(layer, x, y, hw)
+
+        self.t0 = cur = alloc(B * H * W, ch[0])
+        cats = [None] * n
+        for i, block in enumerate(model.u_net.d_blocks):
+            hw = sizes[i]
+            rows = B * hw[0] * hw[1]
+            if i > 0:
+                nxt = alloc(rows, ch[i - 1])
+                emit(partial(uo.down2, cur, B, sizes[i - 1][0], sizes[i - 1][1], out=nxt))
+                cur = nxt
+            layers = list(block)[1:]
+            for j, layer in enumerate(layers):
+                if j == len(layers) - 1 and i < n - 1:                  # the level's skip: the right half of the up path's concat buffer
+                    cats[i] = alloc(rows, 2 * ch[i])
+                    dst = cats[i][:, ch[i]:]
+                else:
+                    dst = alloc(rows, layer.c_out)
+                run_layer(layer, cur, dst, hw)
+                free(cur)
+                cur = dst
+        for k, block in enumerate(model.u_net.u_blocks):
+            i = n - 1 - k
+            hw = sizes[i]
+            rows = B * hw[0] * hw[1]
+            if i < n - 1:
+                cur = cats[i]                                           # [upsampled | skip], both halves written by now
+            for layer in list(block)[:-1]:
+                dst = alloc(rows, layer.c_out)
+                run_layer(layer, cur, dst, hw)
+                free(cur)
+                cur = dst
+            if i > 0:
+                emit(partial(uo.up2, cur, B, hw[0], hw[1], out=cats[i - 1][:, :ch[i - 1]]))
+                free(cur)
+        self.last = cur
+
+
+class AugmentWrapperV1(KarrasAugmentWrapper):
+    """``KarrasAugmentWrapper`` around the U-Net (config.py:169-170) that also hands ``Denoiser.forward`` the inner model's fused
+    ``forward_preconditioned``, with the same conditioning rule: ``aug_cond`` (zeros [B, 9] when none is given) in front of ``mapping_cond``."""
+
+    def forward_preconditioned(self, input, sigma, sigma_data, aug_cond=None, mapping_cond=None, **kwargs):
+        cond = input.new_zeros([input.shape[0], 9]) if aug_cond is None else aug_cond
+        if mapping_cond is not None:
+            cond = torch.cat([cond, mapping_cond], dim=1)
+        return self.inner_model.forward_preconditioned(input, sigma, sigma_data, mapping_cond=cond, **kwargs)
+
+
+class ImageDenoiserModelV1(nn.Module):
+    """image_v1.py:89-176 with the reference's constructor signature, attributes, state_dict and ``param_groups``; forward only (see the
+    module docstring for the scope)."""
+
+    def __init__(self, c_in, feats_in, depths, channels, self_attn_depths, cross_attn_depths=None, mapping_cond_dim=0, unet_cond_dim=0,
+                 cross_cond_dim=0, dropout_rate=0., patch_size=1, skip_stages=0, has_variance=False):
+        super().__init__()
+        for field, value, want in (("patch_size", patch_size, 1), ("skip_stages", skip_stages, 0), ("has_variance", bool(has_variance), False),
+                                   ("cross_cond_dim", cross_cond_dim, 0), ("unet_cond_dim", unet_cond_dim, 0)):
+            if value != want:
+                raise ValueError(f"image_v1: {field}={value!r} is not supported on the HIP path (only {field}={want!r})")
+        if mapping_cond_dim < 0:
+            raise ValueError(f"image_v1: mapping_cond_dim={mapping_cond_dim} must be >= 0")
+        depths, channels, self_attn_depths = list(depths), list(channels), list(self_attn_depths)
+        if not depths or not (len(depths) == len(channels) == len(self_attn_depths)):
+            raise ValueError(f"image_v1: depths, channels and self_attn_depths must have one entry per level (got {len(depths)}, {len(channels)}, "
+                             f"{len(self_attn_depths)})")
+        if any(c <= 0 or c % 64 for c in channels):
+            raise ValueError(f"image_v1: channels={channels}: every channel count must be a multiple of 64 (heads of 64, groups of 32)")
+        if any(d < 1 for d in depths):
+            raise ValueError(f"image_v1: depths={depths}: every level needs at least one block")
+        if not 1 <= c_in <= 4:
+            raise ValueError(f"image_v1: c_in={c_in}: 1 to 4 image channels")
+        if feats_in <= 0 or feats_in % 2:
+            raise ValueError(f"image_v1: feats_in={feats_in} must be even and positive")
+        self.c_in, self.feats_in, self.depths, self.channels = c_in, feats_in, depths, channels
+        self.unet_cond_dim, self.patch_size, self.has_variance, self.dropout_rate = unet_cond_dim, patch_size, has_variance, dropout_rate
+        from ..layers import FourierFeatures
+        self.timestep_embed = FourierFeatures(1, feats_in)
+        if mapping_cond_dim > 0:
+            self.mapping_cond = nn.Linear(mapping_cond_dim, feats_in, bias=False)
+        self.mapping = _MappingNet(feats_in, feats_in)
+        self.proj_in = nn.Conv2d(c_in, channels[0], 1)
+        self.proj_out = nn.Conv2d(channels[0], c_in, 1)
+        nn.init.zeros_(self.proj_out.weight)
+        nn.init.zeros_(self.proj_out.bias)
+        n = len(depths)
+        d_blocks, u_blocks = [], []
+        for i in range(n):
+            mods = _block_layers(depths[i], feats_in, channels[max(0, i - 1)], channels[i], channels[i], self_attn_depths[i], dropout_rate)
+            d_blocks.append(nn.Sequential(_Resample(False) if i > 0 else nn.Identity(), *mods))
+        for i in range(n):
+            my_c_in = channels[i] * 2 if i < n - 1 else channels[i]
+            mods = _block_layers(depths[i], feats_in, my_c_in, channels[i], channels[max(0, i - 1)], self_attn_depths[i], dropout_rate)
+            u_blocks.append(nn.Sequential(*mods, _Resample(True) if i > 0 else nn.Identity()))
+        self.u_net = _UNet(d_blocks, reversed(u_blocks))
+        self._plans, self._plans_fp = {}, None
+
+    def param_groups(self, base_lr=2e-4):
+        """image_v1.py:117-133: the weights of ``mapping`` and ``u_net`` decay, everything else does not."""
+        wd, no_wd = [], []
+        for name, param in self.named_parameters():
+            (wd if (name.startswith("mapping") or name.startswith("u_net")) and name.endswith(".weight") else no_wd).append(param)
+        return [{"params": wd, "lr": base_lr}, {"params": no_wd, "lr": base_lr, "weight_decay": 0.0}]
+
+    def set_skip_stages(self, skip_stages):
+        if skip_stages != 0:
+            raise ValueError(f"image_v1: skip_stages={skip_stages!r} is not supported on the HIP path (only skip_stages=0)")
+        return self
+
+    def set_patch_size(self, patch_size):
+        if patch_size != 1:
+            raise ValueError(f"image_v1: patch_size={patch_size!r} is not supported on the HIP path (only patch_size=1)")
+
+    # ---- launch plans ---------------------------------------------------------------------------------------------------------------------
+    def _weights_fingerprint(self):
+        return tuple((id(t), t.data_ptr(), 0 if t.is_inference() else t._version) for t in list(self.parameters()) + list(self.buffers()))
+
+    def invalidate(self):
+        """Drop the launch plans (needed only after an in-place edit of weights created under torch.inference_mode())."""
+        self._plans, self._plans_fp = {}, None
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._plans, self._plans_fp = {}, None
+        return out
+
+    def _plan(self, B, H, W, device):
+        fp = self._weights_fingerprint()
+        if fp != self._plans_fp:
+            self._plans, self._plans_fp = {}, fp
+        key = (B, H, W, str(device))
+        plan = self._plans.get(key)
+        if plan is None:
+            if len(self._plans) >= 8:
+                self._plans.clear()
+            plan = self._plans[key] = _Plan(self, B, H, W, device)
+        return plan
+
+    def _run(self, input, sigma, mapping_cond, sigma_data, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False):
+        if unet_cond is not None or cross_cond is not None or cross_cond_padding is not None or return_variance:
+            raise ValueError("image_v1: unet_cond, cross_cond and return_variance are not supported on the HIP path")
+        tensors = [t for t in (input, sigma, mapping_cond) if isinstance(t, torch.Tensor)]
+        if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("image_v1: sampling only -- the U-Net has no backward pass on the HIP path; call it under torch.no_grad() "
+                                      "(and model.requires_grad_(False))")
+        if self.training and self.dropout_rate:
+            raise NotImplementedError("image_v1: sampling only -- dropout is a training quantity; call model.eval()")
+        if not isinstance(input, torch.Tensor) or input.dim() != 4 or input.shape[1] != self.c_in:
+            raise ValueError(f"image_v1: input is [B, {self.c_in}, H, W] (got {tuple(getattr(input, 'shape', ()))})")
+        if not input.is_cuda:
+            raise RuntimeError(f"image_v1 runs on the HIP path only: move the model and inputs to a ROCm device (got {input.device}); there is no "
+                               f"CPU fallback")
+        if self.proj_in.weight.device != input.device:
+            raise RuntimeError(f"model weights are on {self.proj_in.weight.device}, input on {input.device}")
+        if input.dtype != torch.float32 or self.proj_in.weight.dtype != torch.float32:
+            raise TypeError(f"image_v1: fp32 inputs and weights only (got {input.dtype}, {self.proj_in.weight.dtype})")
+        has_cond = hasattr(self, "mapping_cond")
+        if mapping_cond is not None and not has_cond:
+            raise ValueError("image_v1: mapping_cond given, but the model was built with mapping_cond_dim=0")
+        x = input.contiguous()
+        B, _, H, W = x.shape
+        sigma = sigma.to(device=x.device, dtype=torch.float32).reshape(-1).expand(B).contiguous()
+        plan = self._plan(B, H, W, x.device)
+        e = ops.fourier_sigma(sigma, self.timestep_embed.weight, out=plan.ff)
+        if mapping_cond is not None:
+            mc = mapping_cond.to(device=x.device, dtype=torch.float32).contiguous()
+            if tuple(mc.shape) != (B, self.mapping_cond.weight.shape[1]):
+                raise ValueError(f"image_v1: mapping_cond is [{B}, {self.mapping_cond.weight.shape[1]}] (got {tuple(mc.shape)})")
+            e = uo.cond_mlp(mc, self.mapping_cond.weight, add=plan.ff, out=plan.e)
+        h = uo.cond_mlp(e, self.mapping[0].weight, self.mapping[0].bias, gelu=True, out=plan.h1)
+        h = uo.cond_mlp(h, self.mapping[2].weight, self.mapping[2].bias, gelu=True, out=plan.h2)
+        uo.cond_mlp(h, plan.map_w, plan.map_b, out=plan.table)
+        pre = sigma_data is not None
+        uo.unet_in(x, self.proj_in.weight, self.proj_in.bias, sigma if pre else None, sigma_data if pre else 1.0, out=plan.t0)
+        for call in plan.calls:
+            call()
+        return uo.unet_out(plan.last, self.proj_out.weight, self.proj_out.bias, tuple(x.shape), image=x if pre else None,
+                           sigma=sigma if pre else None, sigma_data=sigma_data if pre else 1.0)
+
+    def forward(self, input, sigma, mapping_cond=None, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False):
+        """F(input, sigma): [B, C, H, W] fp32 on a ROCm device -> [B, C, H, W] (image_v1.py:135-157)."""
+        return self._run(input, sigma, mapping_cond, None, unet_cond, cross_cond, cross_cond_padding, return_variance)
+
+    def forward_preconditioned(self, input, sigma, sigma_data, mapping_cond=None, **kwargs):
+        """D(x, sigma) = F(x c_in, sigma) c_out + x c_skip (k_diffusion/layers.py:88-90) with c_in folded into ``proj_in`` and c_out / c_skip
+        into ``proj_out``: what ``Denoiser.forward`` calls."""
+        return self._run(input, sigma, mapping_cond, float(sigma_data), **kwargs)

@@ -1,4 +1,4 @@
-"""Deterministic synthetic ("random-init") weights for ImageTransformerDenoiserModelV2.
+"""Deterministic synthetic ("random-init") weights for ImageTransformerDenoiserModelV2 and ImageDenoiserModelV1.
 
 The reference zero-initialises every residual-branch output projection, every AdaRMSNorm
 projection and the final un-patch projection (image_transformer_v2.py:159, 365, 410, 458, 485,
@@ -46,6 +46,21 @@ def synth_tensor(name, shape, seed=0, template=None):
         return 0.5 + 0.1 * rn()
     if name.endswith("norm.linear.weight"):                  # AdaRMSNorm cond projection (zero-init in ref)
         return 0.03 * rn()
+    # ---- the image_v1 U-Net (models/image_v1.py; names may carry the augment wrapper's "inner_model." prefix).  The reference zero-initialises
+    # the AdaGN mappers, each block's second conv, out_proj and proj_out (image_v1.py:28-29,103-104; layers.py:169-170,190-191): all non-zero here
+    if name.endswith("timestep_embed.weight"):               # FourierFeatures buffer, std 1
+        return rn()
+    if name.endswith(".kernel"):                             # Downsample2d / Upsample2d: the model's own deterministic buffer
+        if template is None:
+            raise ValueError(f"{name} needs the constructed buffer as template")
+        return template.detach().to(torch.float32).clone()
+    if name.endswith("mapper.weight"):                       # AdaGN: (1 + w, b) stay a modulation, not the signal
+        return rn() * (0.3 / math.sqrt(shape[1]))
+    if len(shape) == 4:                                      # conv weights [C_out, C_in, k, k]: fan-in, residual branches at half gain
+        gain = 0.5 if name.endswith(("main.6.weight", "out_proj.weight")) else 1.0
+        return rn() * (gain / math.sqrt(shape[1] * shape[2] * shape[3]))
+    if len(shape) == 1 and name.endswith(".bias"):           # small and non-zero
+        return 0.05 * rn()
     if len(shape) == 2:
         fan_in = shape[1]
         gain = 0.5 if name.endswith(_RESIDUAL_OUT) else 1.0

@@ -1,0 +1,167 @@
+"""Tensor-level wrappers over the C ABI of the image_v1 U-Net kernels (csrc/conv_x3.hip, csrc/unet_f32.hip; contracts: include/kdiff_hip.h)
+-- the module's counterpart of ``ops``, as ``augmentation`` and ``data`` have theirs.
+
+Activations are fp32 NHWC, token-major: a 2-D tensor ``[B * H * W, C]`` whose row stride may exceed C (a column range of a wider buffer:
+``buf[:, :C]`` and ``buf[:, C:]`` are the two halves of a skip concatenation, written in place by their producers).  Column 0 of such a view
+must stay 16-byte aligned.  ROCm tensors only; there is no CPU path.
+"""
+import weakref
+
+import torch
+
+from . import _native as nat
+from .ops import _chk, _p, _stream
+
+
+def _rows(t, name, chan=None):
+    """A token-major activation: 2-D fp32 on the device, unit column stride; returns its row stride."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a tensor, got {type(t)}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: the HIP path needs a tensor on a ROCm device (got {t.device}); there is no CPU fallback")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected torch.float32, got {t.dtype}")
+    if t.dim() != 2 or t.stride(1) != 1 or (chan is not None and t.shape[1] != chan):
+        raise ValueError(f"{name}: expected [tokens, {chan or 'C'}] with unit column stride (got {tuple(t.shape)}, strides {t.stride()})")
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+    if ld < t.shape[1]:
+        raise ValueError(f"{name}: row stride {ld} shorter than the row")
+    return ld
+
+
+def _tokens(x, B, H, W, name):
+    if x.shape[0] != B * H * W:
+        raise ValueError(f"{name}: {x.shape[0]} rows for batch {B} x {H} x {W}")
+
+
+_packed = {}
+
+
+def pack_conv(weight, cache=True):
+    """Packed split-bf16 image of a conv weight [C_out, C_in, ks, ks] (``kd_pack_conv_x3``), cached per tensor object and ``_version``."""
+    cache = cache and not weight.is_inference()
+    key = id(weight)
+    ent = _packed.get(key) if cache else None
+    if ent is not None:
+        ref, version, meta, img = ent
+        if ref() is weight and version == weight._version and meta == (tuple(weight.shape), weight.data_ptr()):
+            return img
+    if _chk(weight, "weight").dim() != 4 or weight.shape[2] != weight.shape[3]:
+        raise ValueError(f"pack_conv: weight is [C_out, C_in, ks, ks] (got {tuple(weight.shape)})")
+    c_out, c_in, ks, _ = weight.shape
+    img = torch.empty(4 * ks * ks * c_out * c_in, device=weight.device, dtype=torch.uint8)
+    nat.check(nat.lib().kd_pack_conv_x3(_p(weight), _p(img), c_out, c_in, ks, _stream()), "kd_pack_conv_x3")
+    if cache:
+        def gone(ref, key=key):
+            ent = _packed.get(key)
+            if ent is not None and ent[0] is ref:
+                del _packed[key]
+        _packed[key] = (weakref.ref(weight, gone), weight._version, (tuple(weight.shape), weight.data_ptr()), img)
+    return img
+
+
+def conv2d(x, weight, B, H, W, bias=None, residual=None, out=None, packed=None):
+    """conv2d(x, weight, padding=ks // 2) + bias + residual on tokens x [B*H*W, C_in] -> [B*H*W, C_out] (``kd_conv2d_x3``), ks 1 or 3.
+    ``out`` must not overlap x."""
+    c_out, c_in, ks, _ = weight.shape
+    ldx = _rows(x, "x", c_in)
+    _tokens(x, B, H, W, "conv2d")
+    out = torch.empty(x.shape[0], c_out, device=x.device, dtype=torch.float32) if out is None else out
+    ldy = _rows(out, "out", c_out)
+    ldr = _rows(residual, "residual", c_out) if residual is not None else 0
+    if out.shape[0] != x.shape[0] or (residual is not None and residual.shape[0] != x.shape[0]):
+        raise ValueError("conv2d: out and residual have the rows of x")
+    packed = pack_conv(weight) if packed is None else packed
+    nat.check(nat.lib().kd_conv2d_x3(_p(x), ldx, _p(packed), _p(None if bias is None else _chk(bias, "bias")), _p(residual), ldr, _p(out), ldy,
+                                     B, H, W, c_in, c_out, ks, _stream()), "kd_conv2d_x3")
+    return out
+
+
+def groupnorm_stats(x, B, groups, eps=1e-5, out=None):
+    """stats [B, groups, 4] = (mean_hi, mean_lo, rstd, 0) of tokens x [B*HW, C] (``kd_groupnorm_stats_f32``)."""
+    ldx = _rows(x, "x")
+    hw, chan = x.shape[0] // B, x.shape[1]
+    out = torch.empty(B, groups, 4, device=x.device, dtype=torch.float32) if out is None else out
+    if tuple(_chk(out, "stats").shape) != (B, groups, 4) or hw * B != x.shape[0]:
+        raise ValueError(f"groupnorm_stats: stats {tuple(out.shape)} / rows {x.shape[0]} for batch {B}, {groups} groups")
+    nat.check(nat.lib().kd_groupnorm_stats_f32(_p(x), ldx, _p(out), B, hw, chan, groups, float(eps), _stream()), "kd_groupnorm_stats_f32")
+    return out
+
+
+def adagn_apply(x, stats, wb, gelu=False, out=None):
+    """(x - mean) rstd (1 + w) + b per sample, then optionally exact GELU (``kd_adagn_apply_f32``); wb [B, >= 2 C] with unit column stride holds
+    (w, b) of each sample in its first 2 C columns."""
+    ldx = _rows(x, "x")
+    B, groups = stats.shape[:2]
+    hw, chan = x.shape[0] // B, x.shape[1]
+    wbs = _rows(wb, "wb")
+    if wb.shape[0] != B or wb.shape[1] != 2 * chan:
+        raise ValueError(f"adagn_apply: wb {tuple(wb.shape)} != {(B, 2 * chan)}")
+    out = torch.empty(x.shape[0], chan, device=x.device, dtype=torch.float32) if out is None else out
+    ldy = _rows(out, "out", chan)
+    nat.check(nat.lib().kd_adagn_apply_f32(_p(x), ldx, _p(_chk(stats, "stats")), _p(wb), wbs, _p(out), ldy, B, hw, chan, groups, int(bool(gelu)),
+                                           _stream()), "kd_adagn_apply_f32")
+    return out
+
+
+def _resample(entry, x, B, H, W, out, Ho, Wo):
+    ldx = _rows(x, "x")
+    _tokens(x, B, H, W, entry)
+    chan = x.shape[1]
+    out = torch.empty(B * Ho * Wo, chan, device=x.device, dtype=torch.float32) if out is None else out
+    ldy = _rows(out, "out", chan)
+    if out.shape[0] != B * Ho * Wo:
+        raise ValueError(f"{entry}: out has {out.shape[0]} rows, expected {B * Ho * Wo}")
+    nat.check(getattr(nat.lib(), entry)(_p(x), ldx, _p(out), ldy, B, H, W, chan, _stream()), entry)
+    return out
+
+
+def down2(x, B, H, W, out=None):
+    """Downsample2d('linear', 'reflect') on tokens: [B*H*W, C] -> [B*(H/2)*(W/2), C] (``kd_down2_f32``)."""
+    return _resample("kd_down2_f32", x, B, H, W, out, H // 2, W // 2)
+
+
+def up2(x, B, H, W, out=None):
+    """Upsample2d('linear', 'reflect') on tokens: [B*H*W, C] -> [B*2H*2W, C] (``kd_up2_f32``)."""
+    return _resample("kd_up2_f32", x, B, H, W, out, 2 * H, 2 * W)
+
+
+def unet_in(image, weight, bias=None, sigma=None, sigma_data=1.0, out=None):
+    """proj_in: NCHW image -> tokens [B*H*W, C] through weight [C, C_img(, 1, 1)]; with ``sigma`` the image is scaled by c_in first."""
+    B, c_img, H, W = _chk(image, "image").shape
+    chan = weight.shape[0]
+    out = torch.empty(B * H * W, chan, device=image.device, dtype=torch.float32) if out is None else out
+    ldy = _rows(out, "out", chan)
+    nat.check(nat.lib().kd_unet_in_f32(_p(image), _p(_chk(weight, "weight")), _p(None if bias is None else _chk(bias, "bias")),
+                                       _p(None if sigma is None else _chk(sigma, "sigma")), float(sigma_data), _p(out), ldy, B, H * W, c_img, chan,
+                                       _stream()), "kd_unet_in_f32")
+    return out
+
+
+def unet_out(x, weight, bias, shape, image=None, sigma=None, sigma_data=1.0, out=None):
+    """proj_out: tokens [B*H*W, C] -> NCHW ``shape`` through weight [C_img, C(, 1, 1)]; with ``sigma`` (and the input ``image``) the result is
+    F c_out + image c_skip."""
+    B, c_img, H, W = shape
+    ldx = _rows(x, "x", weight.shape[1])
+    _tokens(x, B, H, W, "unet_out")
+    out = torch.empty(shape, device=x.device, dtype=torch.float32) if out is None else out
+    if tuple(_chk(out, "out").shape) != tuple(shape) or weight.shape[0] != c_img:
+        raise ValueError(f"unet_out: out {tuple(out.shape)} / weight {tuple(weight.shape)} for {tuple(shape)}")
+    nat.check(nat.lib().kd_unet_out_f32(_p(x), ldx, _p(_chk(weight, "weight")), _p(None if bias is None else _chk(bias, "bias")),
+                                        _p(None if image is None else _chk(image, "image")), _p(None if sigma is None else _chk(sigma, "sigma")),
+                                        float(sigma_data), _p(out), B, H * W, c_img, x.shape[1], _stream()), "kd_unet_out_f32")
+    return out
+
+
+def cond_mlp(x, weight, bias=None, add=None, gelu=False, out=None):
+    """act(x W^T + bias + add) for a few rows in exact fp32 (``kd_cond_mlp_f32``): x [R, K], weight [N, K] -> [R, N]."""
+    R, K = _chk(x, "x").shape
+    N = weight.shape[0]
+    if _chk(weight, "weight").shape[1] != K:
+        raise ValueError(f"cond_mlp: weight {tuple(weight.shape)} for x {tuple(x.shape)}")
+    out = torch.empty(R, N, device=x.device, dtype=torch.float32) if out is None else out
+    if tuple(_chk(out, "out").shape) != (R, N) or (add is not None and tuple(_chk(add, "add").shape) != (R, N)):
+        raise ValueError(f"cond_mlp: out / add must be {(R, N)}")
+    nat.check(nat.lib().kd_cond_mlp_f32(_p(x), _p(weight), _p(None if bias is None else _chk(bias, "bias")), _p(add), _p(out), R, N, K,
+                                        int(bool(gelu)), _stream()), "kd_cond_mlp_f32")
+    return out

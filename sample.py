@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Samples from k-diffusion image_transformer_v2 models on MI355X (drop-in for the reference's sample.py).
+"""Samples from k-diffusion image_transformer_v2 and image_v1 (U-Net) models on MI355X (drop-in for the reference's sample.py).
 
 Keeps the reference CLI (sample.py:19-30: --batch-size --checkpoint --config -n --prefix --steps, output
 ``{prefix}_{i:05}.png``) and its flow (load_config -> make_model -> load safetensors -> Denoiser ->
