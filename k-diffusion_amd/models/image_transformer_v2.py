@@ -23,10 +23,6 @@ The plan (workspace + prebuilt launch descriptors) is cached per input shape.  T
 CPU path: calling ``forward`` without a ROCm device or without the built library raises.
 """
 import ctypes as C
-import gc
-import itertools
-import operator
-import weakref
 import os
 import math
 from dataclasses import dataclass
@@ -37,6 +33,7 @@ from torch import nn
 
 from .. import _native as nat
 from .. import ops
+from .. import weights
 from . import axial_rope
 
 D_HEAD = 64
@@ -49,14 +46,6 @@ MAX_PLANS = 16     # cached launch plans (one per batch / size / conditioning ki
 # environment switches of the kernel routing (name, default): read in _plan_for, part of the plan key, passed to route_layer
 PLAN_SWITCHES = (("KDIFF_ATTN_BLOCK", "1"), ("KDIFF_PROJ_BLOCK", "1"), ("KDIFF_FFN_OUT", "all"), ("KDIFF_RUN_LIST", "1"), ("KDIFF_ATTN_FFN", "1"))
 CLASS_IDS_KEPT = 4            # range-checked class_cond tensors remembered per plan (cond / uncond pairs of a guidance wrapper)
-
-
-_untracked = itertools.count(-1, -1)
-
-def _ver(t):
-    """Version counter of a tensor, or a value that never repeats for tensors made under torch.inference_mode() (they carry no
-    counter, so an in-place change cannot be seen: such a tensor is never recognised as 'the same data as last time')."""
-    return next(_untracked) if t.is_inference() else t._version
 
 
 # ---------------------------------------------------------------------------------- configuration
@@ -460,7 +449,7 @@ class _Schedule:
     """Scale tables of a whole sigma schedule: rows of ``sigma_table`` ([n, B], one row per model call) -> tables[i]."""
 
     def __init__(self, sigma_table, others, ident_others, tables, done):
-        self.base, self.version, self.n, self.B = sigma_table.data_ptr(), _ver(sigma_table), sigma_table.shape[0], sigma_table.shape[1]
+        self.base, self.version, (self.n, self.B) = weights.ident(sigma_table)
         self.ident_others, self.tables, self.done = ident_others, tables, done
         self.waited = set()       # streams (handles) that have waited for ``done`` once: everything they run later is ordered behind it
         # the record keeps the hinted tensors alive, so their addresses cannot be handed to other tensors while it exists
@@ -468,7 +457,7 @@ class _Schedule:
 
     def row_of(self, sigma):
         """Index of the table row ``sigma`` is a view of, or None."""
-        if sigma.dtype != torch.float32 or sigma.numel() != self.B or not sigma.is_contiguous() or _ver(sigma) != self.version:
+        if sigma.dtype != torch.float32 or sigma.numel() != self.B or not sigma.is_contiguous() or weights.version(sigma) != self.version:
             return None
         off = sigma.data_ptr() - self.base
         if off < 0 or off % (4 * self.B) or off // (4 * self.B) >= self.n:
@@ -482,7 +471,7 @@ class _Plan:
     def release(self):
         """Give the workspaces back NOW: a plan's launch lists and conditioning chains close over the plan and over each other (reference
         cycles), so dropping the last outside reference would leave ~20 MB per image allocated until Python's cycle collector happens to run.
-        The callers (eviction, ``_drop_plans``: rare events) run the collector once behind this for the helper objects' own cycles."""
+        The caller (``weights.PlanCache``: eviction, ``_drop_plans``, rare events) runs the collector once behind this for the helper objects' own cycles."""
         self.__dict__.clear()
 
     def __init__(self, model, B, H, W, grids, has_aug, has_class, has_mapping_cond, device, mode, switches):
@@ -753,17 +742,6 @@ class _Plan:
         self.calls = calls
 
 
-def _weak_epoch_bump(model):
-    """load_state_dict post-hook that bumps ``model``'s weights epoch without holding the model alive."""
-    ref = weakref.ref(model)
-
-    def hook(*_args):
-        m = ref()
-        if m is not None:
-            m._fp_epoch += 1
-    return hook
-
-
 # ---------------------------------------------------------------------------------- the model
 
 def _wants_input_grad(x):
@@ -864,10 +842,9 @@ class ImageTransformerDenoiserModelV2(nn.Module):
                                      for a, b in zip(levels[:-1], levels[1:])])
         self.out_norm = _rms_scale(levels[0].width)
         self.patch_out = _Holder(proj=_linear_weight(out_channels * ph * pw, levels[0].width, zero=True))
-        self._plans, self._fingerprint, self._packed, self._derived, self._plans_epoch = {}, None, {}, {}, None
-        self._fp_dicts, self._fp_names, self._fp_objs, self._fp_tensors, self._fp_tracked, self._fp_epoch = (), (), (), (), (), 0
-        self._fp_hooked = weakref.WeakSet()
-        self._fp_sized, self._fp_sizes = (), ()
+        self._watch, self._plan_cache = weights.WeightWatch(self), weights.PlanCache()
+        self._plans = self._plan_cache.plans                # the plain dict, by key, most recently used last
+        self._fingerprint, self._packed, self._derived, self._plans_epoch = None, {}, {}, None
         self._dropout_on, self._dropout_gen = False, None
         self.wgrad_arithmetic = None
 
@@ -892,7 +869,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         version counters, so an in-place edit of a source builds them again (tensors made under torch.inference_mode() carry no counter:
         ``invalidate()``).  The entry keeps its sources alive, so their ids cannot be recycled under it.  The store goes with ``_packed``
         whenever the weights change, and at ``invalidate()``.  (A lookup does not read ``_weights_fingerprint``: 25 - 30 us per call.)"""
-        key = (tag, *[(id(t), None if t.is_inference() else t._version) for t in sources])
+        key = (tag, *[weights.ident(t, never_same=False) for t in sources])
         ent = self._derived.get(key)
         if ent is None:
             if len(self._derived) >= DERIVED_KEPT:
@@ -916,24 +893,15 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         return self._derive(("rope", li, grids[0], device, revs), (freqs,), build)
 
     def _drop_plans(self):
-        """All cached plans go, workspaces at once (``_Plan.release``).  The device is idle first: a plan's side-stream work may still be
-        reading buffers the allocator would hand out again."""
-        if self._plans:
-            dev = next(iter(self._plans))[6]
-            if getattr(dev, "type", "cpu") == "cuda":
-                torch.cuda.synchronize(dev)
-            for plan in self._plans.values():
-                plan.release()
-            self._plans = {}
-            gc.collect()
-        self._plans = {}
+        """All cached plans go, workspaces at once (``_Plan.release``), each plan's device idle first."""
+        self._plan_cache.drop_all()
 
     def invalidate(self):
         """Drop the plans and packed weight images at the next call.  Needed only after an IN-PLACE edit of weights that were created
         under torch.inference_mode() outside load_state_dict / .to(): such tensors carry no version counter, so the edit leaves no trace
         (_weights_fingerprint sees everything else by itself).  The tensors the dual and backward passes derive from the weights
         (``_derive``) go at once."""
-        self._fp_epoch += 1
+        self._watch.bump()
         self._derived = {}
 
     def _apply(self, fn, *args, **kwargs):
@@ -941,7 +909,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         # torch.__future__.set_overwrite_module_params_on_conversion(True), new Parameters in the dicts (seen through the slot check);
         # the epoch covers inference-mode tensors converted in place
         out = super()._apply(fn, *args, **kwargs)
-        self._fp_epoch += 1
+        self._watch.bump()
         return out
 
     def _packed_image(self, W, N, K, geglu, bf16=False):
@@ -955,39 +923,8 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         return ent[1]
 
     def _weights_fingerprint(self):
-        """(address, version) of every parameter and buffer (behind a per-model epoch): a changed entry drops the plans and the packed
-        weight images.  Read on every model call, so the LIST of tensors is kept -- torch's module traversal (parameters() / buffers() over
-        ~90 sub-modules) took 0.3 - 0.4 ms per call, more than the launches of a batch-1 forward.  What makes the kept list safe is a
-        per-call identity check of every SLOT the tree has -- each (module._parameters | _buffers | _modules dict, name) still holds the
-        object it held when the list was built, and each of those dicts still has the size it had (a parameter / buffer / sub-module ADDED
-        to an existing module) -- which is ~300 dict reads in C (a few microseconds), needs no traversal and sees the ways a tensor can be
-        swapped: attribute assignment, register_*, del + re-register, a replaced sub-module, and direct writes into
-        ``module._parameters[name]`` (torch.func.functional_call / stateless._reparametrize_module swap parameters that way, past every
-        registration hook).  In-place edits move the tensors' version counters; .to() moves their addresses; load_state_dict / _apply /
-        invalidate() bump the epoch (which also covers inference-mode tensors, whose edits leave no version trace).  No process-wide
-        hooks: only this model's own tree is looked at."""
-        if not (self._fp_objs and all(map(operator.is_, map(dict.get, self._fp_dicts, self._fp_names), self._fp_objs))
-                and tuple(map(len, self._fp_sized)) == self._fp_sizes):      # (sizes: a slot ADDED to a recorded dict is no recorded slot)
-            dicts, names, objs, ts, sized = [], [], [], [], []
-            for mod in self.modules():
-                if mod not in self._fp_hooked:       # a (sub-)module's load_state_dict rewrites weights in place: bump the epoch (inference-mode tensors)
-                    self._fp_hooked.add(mod)
-                    mod.register_load_state_dict_post_hook(_weak_epoch_bump(self))      # (weak: a sub-module shared with another model does not pin this one)
-                for d, is_tensor in ((mod._parameters, True), (mod._buffers, True), (mod._modules, False)):
-                    sized.append(d)
-                    for name, obj in d.items():
-                        dicts.append(d), names.append(name), objs.append(obj)
-                        if is_tensor and obj is not None:
-                            ts.append(obj)
-            seen, uniq = set(), []
-            for t in ts:                     # tied tensors once, like parameters() / buffers()
-                if id(t) not in seen:
-                    seen.add(id(t))
-                    uniq.append(t)
-            self._fp_dicts, self._fp_names, self._fp_objs = tuple(dicts), tuple(names), tuple(objs)
-            self._fp_sized, self._fp_sizes = tuple(sized), tuple(map(len, sized))
-            self._fp_tensors, self._fp_tracked = tuple(uniq), tuple(not t.is_inference() for t in uniq)
-        return (self._fp_epoch, *[(t.data_ptr(), t._version if tr else 0) for t, tr in zip(self._fp_tensors, self._fp_tracked)])
+        """``weights.WeightWatch.fingerprint`` of this model's tree: read on every model call."""
+        return self._watch.fingerprint()
 
     def _param_tags(self, name):
         """The reference's parameter tags (image_transformer_v2.py:59-84): "wd" on the weights of the projections, "mapping" on the mapping
@@ -1150,8 +1087,9 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         for sch in plan.schedules:                # this call's scales were computed with its whole sigma schedule
             i = sch.row_of(sigma) if sch.ident_others == ident[1:] else None
             if i is not None:
-                # the table was computed once, ahead of the loop, on the side stream: ONE wait per (schedule, stream) orders every later
-                # forward on that stream behind it (a wait packet per forward cost ~3 us of idle queue each: profiles/r06_launch_gaps_*.txt)
+                # the table was computed once, ahead of the loop, on the stream that was current in prefetch_schedule: ONE wait per
+                # (schedule, stream) orders every later forward on that stream behind it (a wait packet per forward cost ~3 us of idle
+                # queue each: profiles/r06_launch_gaps_*.txt)
                 if cur.cuda_stream not in sch.waited:
                     cur.wait_event(sch.done)
                     sch.waited.add(cur.cuda_stream)
@@ -1205,22 +1143,18 @@ class ImageTransformerDenoiserModelV2(nn.Module):
             self._plans_epoch = nat.option_epoch
         key = (B, H, W, aug_cond is not None, has_class, self.mapping_cond_in_proj is not None, x.device, nat.default_precision()) \
             + tuple(os.environ.get(k, d) for k, d in PLAN_SWITCHES)
-        plan = self._plans.get(key)
-        if plan is not None and len(self._plans) > 1:
-            self._plans[key] = self._plans.pop(key)                # most recently used last (dicts keep insertion order)
+        plan = self._plan_cache.get(key)
         if plan is None and create:
             grids = self._token_grids(x)
-            if len(self._plans) >= MAX_PLANS:
-                # a plan owns the workspaces of its shape (~20 MB per 256 x 256 image in the fp32 modes): a caller that walks through
-                # batch sizes would otherwise keep them all.  The least recently used one goes; its side-stream work (conditioning
-                # prefetch) may still be in flight in buffers the allocator would hand out again at once, hence the device-wide wait
-                # (rare: only when a NEW shape arrives with MAX_PLANS shapes cached).
-                torch.cuda.synchronize(x.device)
-                self._plans.pop(next(iter(self._plans))).release()
-                gc.collect()
-            with torch.inference_mode(False):     # (workspaces made under inference_mode could not be written in place outside it later)
-                plan = self._plans[key] = _Plan(self, B, H, W, grids, key[3], has_class, key[5], x.device, key[7],
-                                                dict(zip((name for name, _ in PLAN_SWITCHES), key[8:])))
+
+            def build():
+                with torch.inference_mode(False):     # (workspaces made under inference_mode could not be written in place outside it later)
+                    return _Plan(self, B, H, W, grids, key[3], has_class, key[5], x.device, key[7],
+                                 dict(zip((name for name, _ in PLAN_SWITCHES), key[8:])))
+            # a plan owns the workspaces of its shape (~20 MB per 256 x 256 image in the fp32 modes): a caller that walks through batch
+            # sizes would otherwise keep them all.  With MAX_PLANS shapes cached the least recently used one goes first, behind a wait
+            # for its whole device (rare: only when a NEW shape arrives then).
+            plan = self._plan_cache.put(key, build, MAX_PLANS)
         if plan is not None and has_class and class_cond is not None:
             # nn.Embedding raises on an out-of-range id (on every call); the HIP kernel would read past the table.  Checked whenever
             # the ids are a tensor this plan has not seen in this state (address, version): one device->host read per new id
@@ -1228,13 +1162,12 @@ class ImageTransformerDenoiserModelV2(nn.Module):
             # (tensors made under torch.inference_mode() carry no version counter: they cannot be recognised as unchanged and are
             # re-checked on every call.  A few identities are remembered, so alternating id tensors -- cond / uncond calls of a
             # guidance wrapper -- stay sync-free as well.)
-            tracked = not class_cond.is_inference()
-            ident = (class_cond.data_ptr(), _ver(class_cond), tuple(class_cond.shape))
-            if not tracked or ident not in plan.class_checked:
+            ident = weights.ident(class_cond)
+            if ident not in plan.class_checked:
                 lo, hi = (int(class_cond.min()), int(class_cond.max())) if class_cond.numel() else (0, 0)
                 if lo < 0 or hi >= self.class_emb.weight.shape[0]:
                     raise IndexError(f"class_cond ids must lie in [0, {self.class_emb.weight.shape[0] - 1}] (got {lo}..{hi})")
-                if tracked:
+                if not class_cond.is_inference():
                     plan.class_checked[ident] = class_cond        # (kept alive: the address cannot be recycled under the record)
                     while len(plan.class_checked) > CLASS_IDS_KEPT:
                         del plan.class_checked[next(iter(plan.class_checked))]
@@ -1242,7 +1175,7 @@ class ImageTransformerDenoiserModelV2(nn.Module):
 
     # ---- conditioning ahead of time ---------------------------------------------------------------
     def _cond_identity(self, sigma, aug_cond, class_cond, mapping_cond):
-        return tuple(None if t is None else (t.data_ptr(), _ver(t), tuple(t.shape)) for t in (sigma, aug_cond, class_cond, mapping_cond))
+        return tuple(map(weights.ident, (sigma, aug_cond, class_cond, mapping_cond)))
 
     def _hint_usable(self, x_like, class_cond, mapping_cond):
         if not x_like.is_cuda or x_like.dim() != 4:

@@ -24,9 +24,11 @@ from torch import nn
 
 from .. import ops
 from .. import unet_ops as uo
+from .. import weights
 from ..augmentation import KarrasAugmentWrapper
 
 _LINEAR = [1 / 8, 3 / 8, 3 / 8, 1 / 8]
+MAX_PLANS = 8      # cached launch plans (one per batch / size / device) per model: least recently used beyond that
 
 
 class _AdaGN(nn.Module):
@@ -288,7 +290,8 @@ class ImageDenoiserModelV1(nn.Module):
             mods = _block_layers(depths[i], feats_in, my_c_in, channels[i], channels[max(0, i - 1)], self_attn_depths[i], dropout_rate)
             u_blocks.append(nn.Sequential(*mods, _Resample(True) if i > 0 else nn.Identity()))
         self.u_net = _UNet(d_blocks, reversed(u_blocks))
-        self._plans, self._plans_fp = {}, None
+        self._watch, self._plan_cache, self._fingerprint = weights.WeightWatch(self), weights.PlanCache(), None
+        self._plans = self._plan_cache.plans
 
     def param_groups(self, base_lr=2e-4):
         """image_v1.py:117-133: the weights of ``mapping`` and ``u_net`` decay, everything else does not."""
@@ -308,28 +311,24 @@ class ImageDenoiserModelV1(nn.Module):
 
     # ---- launch plans ---------------------------------------------------------------------------------------------------------------------
     def _weights_fingerprint(self):
-        return tuple((id(t), t.data_ptr(), 0 if t.is_inference() else t._version) for t in list(self.parameters()) + list(self.buffers()))
+        return self._watch.fingerprint()
 
     def invalidate(self):
-        """Drop the launch plans (needed only after an in-place edit of weights created under torch.inference_mode())."""
-        self._plans, self._plans_fp = {}, None
+        """Drop the launch plans at the next call (needed only after an in-place edit of weights created under torch.inference_mode())."""
+        self._watch.bump()
 
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
-        self._plans, self._plans_fp = {}, None
+        self._watch.bump()
         return out
 
     def _plan(self, B, H, W, device):
         fp = self._weights_fingerprint()
-        if fp != self._plans_fp:
-            self._plans, self._plans_fp = {}, fp
+        if fp != self._fingerprint:
+            self._plan_cache.drop_all()
+            self._fingerprint = fp
         key = (B, H, W, str(device))
-        plan = self._plans.get(key)
-        if plan is None:
-            if len(self._plans) >= 8:
-                self._plans.clear()
-            plan = self._plans[key] = _Plan(self, B, H, W, device)
-        return plan
+        return self._plan_cache.get(key) or self._plan_cache.put(key, lambda: _Plan(self, B, H, W, device), MAX_PLANS)
 
     def _run(self, input, sigma, mapping_cond, sigma_data, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False):
         if unet_cond is not None or cross_cond is not None or cross_cond_padding is not None or return_variance:

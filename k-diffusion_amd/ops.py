@@ -13,13 +13,13 @@ The op names mirror the reference functions they replace
 """
 import ctypes as C
 import os
-import weakref
 
 import math
 
 import torch
 
 from . import _native as nat
+from . import weights
 
 
 def _stream():
@@ -42,47 +42,32 @@ def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-_packed = {}
+_packed = weights.WeakCache()
 
 
 def pack_weight(W, N, K, geglu, cache=True, bf16=False):
     """Packed image of a weight (uint8 tensor): the split-bf16 image of KD_PREC_SPLIT3, or with ``bf16=True`` the plain bf16
-    image of KD_PREC_BF16, or with ``bf16="mx8"`` the e4m3 image + channel scales of kd_gemm_mx8 (``geglu`` 0 / 1 only).  ``geglu``: 0 / False plain, 1 / True GEGLU rows, 2 the k order of the fused FF block's down projection.  Weights are static while sampling, so the image is cached per tensor OBJECT (weak reference +
-    version counter: a new tensor that happens to reuse the address of a freed one never hits a stale image)."""
+    image of KD_PREC_BF16, or with ``bf16="mx8"`` the e4m3 image + channel scales of kd_gemm_mx8 (``geglu`` 0 / 1 only).  ``geglu``: 0 / False plain, 1 / True GEGLU rows, 2 the k order of the fused FF block's down projection.  Weights are static while sampling, so the image is cached per tensor OBJECT
+    (``weights.WeakCache``)."""
     geglu = int(geglu)
-    cache = cache and not W.is_inference()        # (no version counter to tell a rewritten tensor by: never cached)
-    key = (id(W), bf16 if bf16 == "mx8" else bool(bf16), geglu)
-    ent = _packed.get(key) if cache else None
-    if ent is not None:
-        ref, version, meta, img = ent
-        if ref() is W and version == W._version and meta == (tuple(W.shape), N, K, geglu, W.data_ptr()):
-            return img
-    _chk(W, "W")
-    lib = nat.lib()
-    if bf16 == "mx8":
-        size = lib.kd_packed_weight_bytes_mx8(N, K, int(geglu))
-        if size <= 0:
-            raise ValueError(f"kd_pack_weight_mx8: N={N} K={K} is not taken (K must be a multiple of 128)")
-        img = torch.empty(size, device=W.device, dtype=torch.uint8)
-        nat.check(lib.kd_pack_weight_mx8(_p(W), _p(img), N, K, int(geglu), _stream()), "kd_pack_weight_mx8")
-    elif bf16:
-        img = torch.empty(lib.kd_packed_weight_bytes_bf16(N, K, int(geglu)), device=W.device, dtype=torch.uint8)
-        nat.check(lib.kd_pack_weight_bf16(_p(W), _p(img), N, K, int(geglu), _stream()), "kd_pack_weight_bf16")
-    else:
-        img = torch.empty(lib.kd_packed_weight_bytes(N, K, int(geglu)), device=W.device, dtype=torch.uint8)
-        nat.check(lib.kd_pack_weight_bf16x3(_p(W), _p(img), N, K, int(geglu), _stream()), "kd_pack_weight_bf16x3")
-    if cache:
-        if len(_packed) > 512:
-            for k in [k for k, e in _packed.items() if e[0]() is None]:
-                del _packed[k]
-            if len(_packed) > 512:
-                _packed.clear()
-        def gone(ref, key=key):               # the weight died: its image goes with it (plans pack per-plan concatenations of weights)
-            ent = _packed.get(key)
-            if ent is not None and ent[0] is ref:
-                del _packed[key]
-        _packed[key] = (weakref.ref(W, gone), W._version, (tuple(W.shape), N, K, geglu, W.data_ptr()), img)
-    return img
+
+    def build():
+        _chk(W, "W")
+        lib = nat.lib()
+        if bf16 == "mx8":
+            size = lib.kd_packed_weight_bytes_mx8(N, K, geglu)
+            if size <= 0:
+                raise ValueError(f"kd_pack_weight_mx8: N={N} K={K} is not taken (K must be a multiple of 128)")
+            img = torch.empty(size, device=W.device, dtype=torch.uint8)
+            nat.check(lib.kd_pack_weight_mx8(_p(W), _p(img), N, K, geglu, _stream()), "kd_pack_weight_mx8")
+        elif bf16:
+            img = torch.empty(lib.kd_packed_weight_bytes_bf16(N, K, geglu), device=W.device, dtype=torch.uint8)
+            nat.check(lib.kd_pack_weight_bf16(_p(W), _p(img), N, K, geglu, _stream()), "kd_pack_weight_bf16")
+        else:
+            img = torch.empty(lib.kd_packed_weight_bytes(N, K, geglu), device=W.device, dtype=torch.uint8)
+            nat.check(lib.kd_pack_weight_bf16x3(_p(W), _p(img), N, K, geglu, _stream()), "kd_pack_weight_bf16x3")
+        return img
+    return _packed.get(W, (bf16 if bf16 == "mx8" else bool(bf16), geglu), (N, K), build, cache=cache)
 
 
 def gemm(A, W, out, *, M, N, K, a_mode=nat.A_PLAIN, epi=nat.EPI_STORE, norm_scale=None, scale_stride=0,

@@ -5,11 +5,10 @@ Activations are fp32 NHWC, token-major: a 2-D tensor ``[B * H * W, C]`` whose ro
 ``buf[:, :C]`` and ``buf[:, C:]`` are the two halves of a skip concatenation, written in place by their producers).  Column 0 of such a view
 must stay 16-byte aligned.  ROCm tensors only; there is no CPU path.
 """
-import weakref
-
 import torch
 
 from . import _native as nat
+from . import weights
 from .ops import _chk, _p, _stream
 
 
@@ -34,30 +33,19 @@ def _tokens(x, B, H, W, name):
         raise ValueError(f"{name}: {x.shape[0]} rows for batch {B} x {H} x {W}")
 
 
-_packed = {}
+_packed = weights.WeakCache()
 
 
 def pack_conv(weight, cache=True):
-    """Packed split-bf16 image of a conv weight [C_out, C_in, ks, ks] (``kd_pack_conv_x3``), cached per tensor object and ``_version``."""
-    cache = cache and not weight.is_inference()
-    key = id(weight)
-    ent = _packed.get(key) if cache else None
-    if ent is not None:
-        ref, version, meta, img = ent
-        if ref() is weight and version == weight._version and meta == (tuple(weight.shape), weight.data_ptr()):
-            return img
-    if _chk(weight, "weight").dim() != 4 or weight.shape[2] != weight.shape[3]:
-        raise ValueError(f"pack_conv: weight is [C_out, C_in, ks, ks] (got {tuple(weight.shape)})")
-    c_out, c_in, ks, _ = weight.shape
-    img = torch.empty(4 * ks * ks * c_out * c_in, device=weight.device, dtype=torch.uint8)
-    nat.check(nat.lib().kd_pack_conv_x3(_p(weight), _p(img), c_out, c_in, ks, _stream()), "kd_pack_conv_x3")
-    if cache:
-        def gone(ref, key=key):
-            ent = _packed.get(key)
-            if ent is not None and ent[0] is ref:
-                del _packed[key]
-        _packed[key] = (weakref.ref(weight, gone), weight._version, (tuple(weight.shape), weight.data_ptr()), img)
-    return img
+    """Packed split-bf16 image of a conv weight [C_out, C_in, ks, ks] (``kd_pack_conv_x3``), cached per tensor object (``weights.WeakCache``)."""
+    def build():
+        if _chk(weight, "weight").dim() != 4 or weight.shape[2] != weight.shape[3]:
+            raise ValueError(f"pack_conv: weight is [C_out, C_in, ks, ks] (got {tuple(weight.shape)})")
+        c_out, c_in, ks, _ = weight.shape
+        img = torch.empty(4 * ks * ks * c_out * c_in, device=weight.device, dtype=torch.uint8)
+        nat.check(nat.lib().kd_pack_conv_x3(_p(weight), _p(img), c_out, c_in, ks, _stream()), "kd_pack_conv_x3")
+        return img
+    return _packed.get(weight, None, None, build, cache=cache)
 
 
 def conv2d(x, weight, B, H, W, bias=None, residual=None, out=None, packed=None):

@@ -154,7 +154,7 @@ def test_schedule_rows_are_recognised_by_storage_and_version(KD):
         itab = torch.linspace(80.0, 0.1, 6)[:, None].expand(6, 4).contiguous()
     isch = mod._Schedule(itab, (None, None, None), (None, None, None), torch.zeros(6, 4, 8), None)
     assert all(isch.row_of(itab[i]) is None for i in range(6))
-    assert mod._ver(itab) != mod._ver(itab) and mod._ver(table) == mod._ver(table)
+    assert mod.weights.version(itab) != mod.weights.version(itab) and mod.weights.version(table) == mod.weights.version(table)
 
 
 def test_every_option_name_used_in_the_sources_is_registered():
@@ -614,7 +614,7 @@ def test_weights_fingerprint_keeps_its_tensor_list_and_still_sees_every_change()
         assert f2 != f1 and not walked
         m.patch_in.proj.weight = torch.nn.Parameter(torch.zeros_like(m.patch_in.proj.weight), requires_grad=False)      # a new tensor object
         f3 = m._weights_fingerprint()
-        assert f3 != f2 and walked and any(t is m.patch_in.proj.weight for t in m._fp_tensors)
+        assert f3 != f2 and walked and any(t is m.patch_in.proj.weight for t in m._watch.tensors)
         del walked[:]
         p = m.mapping.out_norm.scale
         p.data = p.data.clone()                                                   # same Parameter, other storage (what Module.to() does)
@@ -624,7 +624,7 @@ def test_weights_fingerprint_keeps_its_tensor_list_and_still_sees_every_change()
         old = m.patch_out.proj._parameters["weight"]
         m.patch_out.proj._parameters["weight"] = torch.nn.Parameter(old.detach().clone() + 1.0, requires_grad=False)
         f5 = m._weights_fingerprint()
-        assert f5 != f4 and walked and any(t is m.patch_out.proj._parameters["weight"] for t in m._fp_tensors)
+        assert f5 != f4 and walked and any(t is m.patch_out.proj._parameters["weight"] for t in m._watch.tensors)
         del walked[:]
         # torch.func.functional_call swaps parameters through the dicts for the duration of the call: the model must see the swapped
         # tensors INSIDE the call (plans / packed images built from the real weights must not serve it) and the real ones after it

@@ -442,6 +442,63 @@ def test_sampler_trajectory_matches_restatement(KD):
     assert err < 1e-3 and torch.equal(got, again)
 
 
+def test_changed_weights_are_noticed(KD):
+    """Plans, packed conv images and the AdaGN mapper table follow the weights: after every kind of change the model computes what a fresh
+    model with the same weights computes, bit for bit; an unchanged model plans once."""
+    cfg, _, sd = built("unet_a")
+    (x, sigma, aug), _, _ = forward_reference("unet_a")
+
+    def fresh(state):
+        model = KD.config.make_model(cfg).eval().requires_grad_(False)
+        model.load_state_dict(state)
+        return model.to(DEV)
+
+    def run(model):
+        with torch.no_grad():
+            return model(g(x), g(sigma), **_kw(aug))
+    model = fresh(sd)
+    inner = getattr(model, "inner_model", model)
+    outs = [run(model)]
+    n = len(inner._plans)
+    assert n == 1 and torch.equal(run(model), outs[0]) and len(inner._plans) == n
+
+    def changed(what):
+        outs.append(run(model))
+        assert torch.equal(outs[-1], run(fresh(model.state_dict()))), f"{what}: not what a fresh model with these weights computes"
+        assert not torch.equal(outs[-1], outs[-2]), f"{what}: the output did not move"
+        assert len(inner._plans) == n
+    model.load_state_dict(KD.synth.synth_state_dict(model.state_dict(), seed=ur.SEED + 1))
+    changed("load_state_dict")
+    conv = inner.u_net.d_blocks[0][1].main[2]
+    with torch.no_grad():
+        conv.weight.mul_(1.5)
+    changed("in-place mul_ of a conv weight")
+    conv.weight = torch.nn.Parameter(conv.weight.detach() * 0.5, requires_grad=False)
+    changed("a parameter assigned anew")
+
+
+def test_plans_are_dropped_least_recently_used_first(KD):
+    _, model, _ = built("unet_a")
+    inner = getattr(model, "inner_model", model)
+    bound = KD.models.image_v1.MAX_PLANS
+    assert bound == 8
+    (x, sigma, aug), _, _ = forward_reference("unet_a")
+    x, sigma, aug = (None if t is None else g(t).repeat(4, *[1] * (t.dim() - 1)) for t in (x, sigma, aug))
+
+    def run(b):
+        with torch.no_grad():
+            return model(x[:b], sigma[:b], **({} if aug is None else {"aug_cond": aug[:b]}))
+    first = run(3).clone()
+    for b in range(1, 11):
+        run(b)
+        assert len(inner._plans) <= bound
+    assert [k[0] for k in inner._plans] == list(range(3, 11))          # the most recent eight, oldest first
+    assert torch.equal(run(3), first)                                  # a hit: batch 3 is the most recently used now
+    run(1)
+    assert [k[0] for k in inner._plans] == [5, 6, 7, 8, 9, 10, 3, 1]
+    assert torch.equal(run(4), run(4)) and len(inner._plans) == bound  # a dropped shape is planned again
+
+
 def test_model_refusals_on_the_device(KD):
     _, model, _ = built("unet_b")
     (x, sigma, _), _, _ = forward_reference("unet_b")
