@@ -39,35 +39,13 @@ extern "C" {
 
 int kd_version(void);
 const char* kd_last_error(void);
-/* Tuning / A-B switches of the library (benchmarks and tests; defaults are the shipped configuration).  The library reads no
- * environment variables: the Python package maps its documented KDIFF_* variables onto these calls.  Thread-safe.
- *   fp32 kernels : "skinny" (1) "astat" (1) "ksplit" (1) "astat_max_k" (512) "astat_waves" (4) "astat_storewait" (0)
- *                  "gemm_debug" (0; profiling ablations of benchmarks/: 1 no C stores, 2 no MFMA, 8 GEGLU without erf)
- *                  "x3" (1; 0 = the round-1 / round-2 kernels for KD_PREC_SPLIT3 projections) "x3_splits" (0 = cost model)
- *                  "x3_half" (1; 0 = one workgroup per CU for the K = 256 projections) "x3_res" (0; 1 = the A-stationary kernel for the K = 512
- *                  residual projection) "x3r" (1; gemm_x3r.hip for projections without a norm in front, K >= 256; 0 = round-1
- *                  kernel, 2 = every eligible shape) "x3r_lw" (1; 0 = staging requests inside the compute waves' K loop instead of loader waves)
- *                  "x3r_split" (1; 0 = TokenSplit + lerp on the round-1 tile kernel) "ffn_x3" (1; 0 = kd_ffn_f32_supported answers no) "ffn_x3_half" (1; 0 = one workgroup per CU
- *                  at K = 128) "attn_x3" (1; 0 = the round-1 attention cores also for split-stored operands)
- *                  "attn_ffn_x3" (1; 0 = kd_attn_ffn_f32_supported answers no)
- *                  "x3_min_rows" (512) "x3r_min_rows" (128) "ffn_x3_min_panels_256" (7/8 of the CUs): row counts from which the throughput
- *                  kernels are chosen / advised
- *                  "x3s_max_rows" (4096; 0 = off) the few-rows latency form of the KD_PREC_SPLIT3 projections (gemm_x3s.hip: 32 rows x one
- *                  half tile per workgroup, K split over 8 waves), taken up to that many rows where its cost estimate beats the
- *                  throughput kernel's; "x3s_max_wgs" (-1; >= 0 replaces the estimate by a cap on the grid) "x3s_scale_lds" (0; 1 = the
- *                  AdaRMSNorm scale vector through LDS where a workgroup's rows share it: same results, measured level)
- *   bf16 kernels : "bf16_fast" (1; 0 = generic kernel only) "wstat" (1) "wstat_waves" (0 = per shape) "wstat_max_slices" (24)
- *                  "wstat_prefetch" (0; 1 next-chunk prefetch, 2 software-pipelined tiles) "astat_bf16" (1) "astat_splits" (0 = auto)
- *                  "tiled_bm" (0 = auto, 128, 256) "tiled_lw" (1; 0 = no loader waves in the tiled kernel at one tile per CU) "attn_global_qw" (8) "patch_fast" (1; 0 = patch-in / patch-out through the generic kernel)
- *                  "ffn_fused" (1; 0 = kd_ffn_bf16_supported answers no) "ffn_fused_256" (0) "ffn_bf16_min_rows" (16384: rows from which
- *                  kd_ffn_bf16_supported advises the fused block)
- *                  "b16s_max_rows" (4096; 0 = off) the few-rows latency form of the bf16 projections (gemm_b16s.hip, the bf16 sibling of
- *                  gemm_x3s.hip), taken up to that many rows where its grid is one round of the chip (two behind a norm at <= 512 rows);
- *                  "b16s_max_wgs" (-1; >= 0: a cap on the grid instead)
- *                  "code_warm" (8: the first wave of that many workgroups of a launch -- one per XCD -- reads the kernel's own code
- *                  range into L2 at entry, so that a kernel that has not run for a while does not walk its code through one
- *                  instruction-cache miss after the other; 0 = off.  Pure prefetch: results do not depend on it) */
-/* value == INT_MIN puts the option back to its built-in default. */
+/* Tuning / A-B switches of the library (benchmarks and tests).  kdiff_options.def, next to this header, is the table: one row per option
+ * with its name, its default (the shipped configuration) and what it selects.
+ *   - the library reads no environment variables: the Python package maps KDIFF_OPTIONS="name=value,..." onto these calls;
+ *   - thread-safe; an unknown name is refused with KD_EINVAL;
+ *   - kd_set_option(name, INT_MIN) puts the option back to its default;
+ *   - kd_get_option returns the value the caller set; if there is none, `dflt` -- or, asked with dflt == INT_MIN, the table's default
+ *     (INT_MIN itself where the launcher computes the default from the device: KD_OPT_AUTO in the table). */
 int kd_set_option(const char* name, int value);
 int kd_get_option(const char* name, int dflt);
 

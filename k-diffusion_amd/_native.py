@@ -289,11 +289,10 @@ def lib():
 
 
 # The library reads no environment variables; KDIFF_OPTIONS="name=value,..." is mapped onto kd_set_option here (re-read whenever it changes,
-# so that tests can flip options inside one process).  (Rounds 2 - 5 also mapped eight per-option variables -- KDIFF_SKINNY, KDIFF_ASTAT_WAVES,
-# ... -- onto the same calls; every one of them is reachable through KDIFF_OPTIONS by its library name and they were removed in round 6.)
-_ENV_OPTIONS = {}
-_env_applied = None       # (value of every mapped variable, {name: value} parsed from KDIFF_OPTIONS) as last applied
+# so that tests can flip options inside one process).
+_env_applied = None       # (KDIFF_OPTIONS, {name: value} parsed from it) as last applied
 _programmatic = set()     # option names set through set_option(): the environment sync leaves them alone
+OPTION_DEFAULT = -2 ** 31  # INT_MIN: kd_set_option goes back to the built-in default, kd_get_option returns it (include/kdiff_hip.h)
 option_epoch = 0          # bumped whenever a library option may have changed: captured launch graphs are bound to one epoch
 
 
@@ -307,20 +306,15 @@ def _parse_options(text):
 
 
 def _sync_options(handle):
-    """KDIFF_* variables -> kd_set_option; KDIFF_OPTIONS="name=value,..." sets any library option by name (A-B runs of bench.py).
-    Only what CHANGED since the last call is re-applied: a variable that changed, a KDIFF_OPTIONS entry that changed or appeared,
-    and -- reset to the library default -- an entry that disappeared.  Options set through ``set_option`` are not touched unless
-    the environment names them anew."""
+    """KDIFF_OPTIONS="name=value,..." sets any library option by name (A-B runs of bench.py).  Only what CHANGED since the last call is
+    re-applied: an entry that changed or appeared, and -- reset to the library default -- an entry that disappeared.  Options set
+    through ``set_option`` are not touched unless the environment names them anew."""
     global _env_applied, option_epoch
-    raw = tuple(os.environ.get(k) for k in _ENV_OPTIONS) + (os.environ.get("KDIFF_OPTIONS"),)
+    raw = os.environ.get("KDIFF_OPTIONS")
     if _env_applied is not None and raw == _env_applied[0]:
         return
-    named = _parse_options(raw[-1])
-    old_raw, old_named = _env_applied[1:] if _env_applied is not None else ((None,) * len(_ENV_OPTIONS), {})
-    for (env, (name, dflt)), val, was in zip(_ENV_OPTIONS.items(), raw, old_raw):
-        if val != was and (val not in (None, "") or was not in (None, "")) and (name not in _programmatic or val not in (None, "")):
-            handle.kd_set_option(name.encode(), dflt if val in (None, "") else int(val))
-            _programmatic.discard(name)
+    named = _parse_options(raw)
+    old_named = _env_applied[1] if _env_applied is not None else {}
     for name, val in named.items():
         if old_named.get(name) != val:
             if handle.kd_set_option(name.encode(), val) != 0:
@@ -328,8 +322,8 @@ def _sync_options(handle):
             _programmatic.discard(name)
     for name in old_named:
         if name not in named and name not in _programmatic:
-            handle.kd_set_option(name.encode(), -0x7FFFFFFF - 1)           # INT_MIN: back to the built-in default (kd_set_option)
-    _env_applied = (raw, raw[:-1], named)
+            handle.kd_set_option(name.encode(), OPTION_DEFAULT)
+    _env_applied = (raw, named)
     option_epoch += 1
 
 

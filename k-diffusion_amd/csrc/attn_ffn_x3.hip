@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256, 2) void attn_ffn_x3h_kernel(const x3a::NArgs a
 using namespace kd;
 
 extern "C" int kd_attn_ffn_f32_supported(int batch, int H, int W, int nh, int ks, int K, int d_ff) {
-  if (!option("attn_ffn_x3", 1) || !option("attn_x3", 1) || !option("ffn_x3", 1)) return 0;
+  if (!opt(KD_OPT_attn_ffn_x3) || !opt(KD_OPT_attn_x3) || !opt(KD_OPT_ffn_x3)) return 0;
   if (ks != x3::AF_KS || nh != 2 || K != 128 || d_ff <= 0 || (d_ff & 63)) return 0;
   if (batch <= 0 || H <= 0 || W <= 0 || H % x3a::NA_TH || W % x3a::NA_TW) return 0;
   return kd_ffn_f32_supported(batch * H * W, K, d_ff);
@@ -107,7 +107,7 @@ extern "C" int kd_attn_ffn_f32(const float* qkv, const KdFfn* dp, int batch, int
                 ks, nh, d.K, d.d_ff, H, W);
   if ((long long)batch * H * W != d.M || d.rows_per_sample != H * W || (d.scale_stride & 3))
     return fail(KD_EINVAL, "kd_attn_ffn_f32: M = batch H W, rows_per_sample = H W, scale_stride %% 4 == 0");
-  x3a::NArgs a{qkv, nullptr, batch, H, W, nh, option("code_warm", KD_CODE_WARM_DEFAULT), x3::g_clk};
+  x3a::NArgs a{qkv, nullptr, batch, H, W, nh, code_warm(), x3::g_clk};
   x3::FArgs3 f{};
   f.X = reinterpret_cast<const float*>(d.x); f.Y = reinterpret_cast<float*>(d.out);
   f.Wu = reinterpret_cast<const char*>(d.Wp_up); f.Wd = reinterpret_cast<const char*>(d.Wp_down);

@@ -388,8 +388,8 @@ static int launch_global(const GArgs& a, hipStream_t s) {
 // Called by kd_attn_global_f32 (attn_f32.hip) for prep == 2, KD_PREC_SPLIT3, T = 64 / 128 / 256.  Returns 1 if not taken.
 int attn_global_x3_try(const float* qkv, float* out, int batch, int T, int nh, hipStream_t s, int* rc) {
   using namespace x3a;
-  if (!option("attn_x3", 1) || (T != 64 && T != 128 && T != 256)) return 1;
-  GArgs a{qkv, out, batch, T, nh, option("code_warm", KD_CODE_WARM_DEFAULT), x3::g_clk};
+  if (!opt(KD_OPT_attn_x3) || (T != 64 && T != 128 && T != 256)) return 1;
+  GArgs a{qkv, out, batch, T, nh, code_warm(), x3::g_clk};
   *rc = T == 256 ? launch_global<8>(a, s) : (T == 128 ? launch_global<4>(a, s) : launch_global<2>(a, s));
   return 0;
 }
@@ -410,8 +410,8 @@ static int launch_na(const x3a::NArgs& a, hipStream_t s) {
 // Called by kd_attn_na2d_f32 (attn_f32.hip) for prep == 2 (operands stored split), kernel sizes 3 .. 13 (odd).  Returns 1 if not taken.
 int attn_na2d_x3_try(const float* qkv, float* out, int batch, int H, int W, int nh, int ks, hipStream_t s, int* rc) {
   using namespace x3a;
-  if (!option("attn_x3", 1)) return 1;
-  NArgs a{qkv, out, batch, H, W, nh, option("code_warm", KD_CODE_WARM_DEFAULT), x3::g_clk};
+  if (!opt(KD_OPT_attn_x3)) return 1;
+  NArgs a{qkv, out, batch, H, W, nh, code_warm(), x3::g_clk};
   switch (ks) {
     case 3: *rc = launch_na<3, false>(a, s); return 0;
     case 5: *rc = launch_na<5, false>(a, s); return 0;

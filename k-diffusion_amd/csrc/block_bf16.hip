@@ -444,7 +444,7 @@ using namespace kd::b16;
 // rows_per_sample = the AdaRMSNorm scale table, qk_scale / rope_pos / rope_freq / n_heads) -- except that C receives the ATTENTION OUTPUT
 // [M, n_heads * 64] bf16 instead of qkv.  Shapes: 256 tokens per sample, K = n_heads * 64 in {256, 512}, N = 3 K.
 extern "C" int kd_attn_block_bf16_supported(int tokens_per_sample, int width, int n_heads) {
-  return tokens_per_sample == 256 && (width == 256 || width == 512) && n_heads * 64 == width && option("attn_block_bf16", 1) ? 1 : 0;
+  return tokens_per_sample == 256 && (width == 256 || width == 512) && n_heads * 64 == width && opt(KD_OPT_attn_block_bf16) ? 1 : 0;
 }
 
 extern "C" int kd_attn_block_bf16(const KdGemm* dp, void* stream) {
@@ -457,7 +457,7 @@ extern "C" int kd_attn_block_bf16(const KdGemm* dp, void* stream) {
     return fail(KD_EINVAL, "kd_attn_block_bf16: shape M=%d N=%d K=%d, %d tokens per sample, %d heads is not taken (256 tokens per sample, "
                 "K = 64 heads in {256, 512})", d.M, d.N, d.K, d.rows_per_sample, d.n_heads);
   BArgs a{reinterpret_cast<const u16*>(d.A), reinterpret_cast<const char*>(d.Wp), reinterpret_cast<u16*>(d.C), d.scale, d.scale_stride, d.eps,
-          d.M / 256, d.n_heads, d.qk_scale, d.rope_pos, d.rope_freq, option("code_warm", KD_CODE_WARM_DEFAULT), g_clk};
+          d.M / 256, d.n_heads, d.qk_scale, d.rope_pos, d.rope_freq, code_warm(), g_clk};
   hipStream_t s = (hipStream_t)stream;
   constexpr int LDS = 8 * WBLK + 8 * 512 * 4;          // prologue: 8 wave-private staging slots + 8 scale vectors; later ring + K / V images
   const double flops = 2.0 * d.M * 3.0 * d.K * d.K + 4.0 * (double)a.batch * a.nh * 256.0 * 256.0 * DH;
@@ -477,7 +477,7 @@ extern "C" int kd_attn_block_bf16(const KdGemm* dp, void* stream) {
 // is its own launch), norm = 1 -- and the results are bit-identical to that call.  Rows per sample a multiple of 256, K in {256, 512}, the W rows
 // a multiple of 6 half blocks (d_ff % 192 == 0; 3 K % 384 == 0 holds for both widths).
 extern "C" int kd_proj_block_bf16_supported(int tokens_per_sample, int width, int n, int epi) {
-  if (tokens_per_sample <= 0 || tokens_per_sample % 256 || (width != 256 && width != 512) || !option("proj_block_bf16", 1)) return 0;
+  if (tokens_per_sample <= 0 || tokens_per_sample % 256 || (width != 256 && width != 512) || !opt(KD_OPT_proj_block_bf16)) return 0;
   if (epi == KD_EPI_GEGLU) return n > 0 && n % 192 == 0;
   if (epi == KD_EPI_QKV) return n == 3 * width;
   return 0;
@@ -496,7 +496,7 @@ extern "C" int kd_proj_block_bf16(const KdGemm* dp, void* stream) {
                 "{256, 512}, d_ff a multiple of 192)", d.M, d.N, d.K, d.rows_per_sample);
   const int w_rows = d.epi == KD_EPI_GEGLU ? 2 * d.N : d.N;
   UArgs a{reinterpret_cast<const u16*>(d.A), reinterpret_cast<const char*>(d.Wp), reinterpret_cast<u16*>(d.C), d.scale, d.scale_stride, d.eps,
-          d.M / 256, d.rows_per_sample / 256, w_rows / 384, d.N, d.n_heads, d.qk_scale, d.rope_pos, d.rope_freq, option("code_warm", KD_CODE_WARM_DEFAULT)};
+          d.M / 256, d.rows_per_sample / 256, w_rows / 384, d.N, d.n_heads, d.qk_scale, d.rope_pos, d.rope_freq, code_warm()};
   hipStream_t s = (hipStream_t)stream;
   constexpr int LDS = 8 * WBLK + 8 * 512 * 4;
   const double flops = 2.0 * d.M * (double)w_rows * d.K;

@@ -64,43 +64,42 @@ int cu_count() {
 using namespace kd;
 
 // ---- library options (explicit switches instead of environment variables read inside the library) -------------------------
-// A fixed table of named integers; reads on the launch path are one relaxed atomic load (option names are string literals in
-// the callers: the index is resolved once per call site through a function-local static).
+// include/kdiff_options.def is the table; the launch path reads g_opt through kd::opt (kd_common.h).  g_set only serves kd_get_option.
 namespace kd {
+#define KD_OPTION(name, dflt, doc) {dflt},
+std::atomic<int> g_opt[KD_OPT_COUNT] = {
+#include "../../include/kdiff_options.def"
+};
+#undef KD_OPTION
 namespace {
-struct Opt { const char* name; std::atomic<int> value; std::atomic<bool> set; };
-Opt g_opts[] = {{"skinny", {0}, {false}}, {"astat", {0}, {false}}, {"ksplit", {0}, {false}}, {"astat_max_k", {0}, {false}}, {"astat_waves", {0}, {false}},
-                {"astat_storewait", {0}, {false}}, {"gemm_debug", {0}, {false}}, {"bf16_fast", {0}, {false}}, {"wstat", {0}, {false}},
-                {"wstat_waves", {0}, {false}}, {"wstat_max_slices", {0}, {false}}, {"wstat_prefetch", {0}, {false}}, {"astat_bf16", {0}, {false}},
-                {"astat_splits", {0}, {false}}, {"tiled_bm", {0}, {false}}, {"attn_global_qw", {0}, {false}},
-                {"patch_fast", {0}, {false}}, {"ffn_fused", {0}, {false}}, {"ffn_fused_256", {0}, {false}}, {"astat_rows", {0}, {false}}, {"tiled_deep", {0}, {false}}, {"code_warm", {0}, {false}}, {"ffn_variant", {0}, {false}},
-                {"x3", {0}, {false}}, {"x3_splits", {0}, {false}}, {"ffn_x3", {0}, {false}}, {"ffn_x3_half", {0}, {false}}, {"x3_res", {0}, {false}}, {"attn_x3", {0}, {false}}, {"attn_ffn_x3", {0}, {false}}, {"x3_half", {0}, {false}}, {"x3r", {0}, {false}}, {"x3_unpatch", {0}, {false}}, {"x3r_lw", {0}, {false}}, {"x3r_split", {0}, {false}}, {"tiled_lw", {0}, {false}}, {"x3_min_rows", {0}, {false}}, {"x3r_min_rows", {0}, {false}}, {"ffn_x3_min_panels_256", {0}, {false}}, {"x3s_max_rows", {0}, {false}}, {"x3s_max_wgs", {0}, {false}}, {"x3s_scale_lds", {0}, {false}}, {"b16s_max_rows", {0}, {false}}, {"b16s_max_wgs", {0}, {false}}, {"ffn_bf16_min_rows", {0}, {false}}, {"x3s_trace", {0}, {false}}, {"attn_block_bf16", {0}, {false}}, {"proj_block_bf16", {0}, {false}}, {"mx8", {0}, {false}}, {"mx8_splits", {0}, {false}}, {"mx8_min_rows", {0}, {false}}};
-constexpr int N_OPTS = sizeof(g_opts) / sizeof(g_opts[0]);
-}  // namespace
+#define KD_OPTION(name, dflt, doc) {#name, dflt},
+const struct { const char* name; int dflt; } g_rows[KD_OPT_COUNT] = {
+#include "../../include/kdiff_options.def"
+};
+#undef KD_OPTION
+std::atomic<bool> g_set[KD_OPT_COUNT];
 int option_index(const char* name) {
-  for (int i = 0; i < N_OPTS; ++i)
-    if (!strcmp(g_opts[i].name, name)) return i;
+  for (int i = 0; i < KD_OPT_COUNT; ++i)
+    if (!strcmp(g_rows[i].name, name)) return i;
   return -1;
 }
-int option_at(int idx, int dflt) {
-  if (idx < 0) return dflt;
-  return g_opts[idx].set.load(std::memory_order_relaxed) ? g_opts[idx].value.load(std::memory_order_relaxed) : dflt;
-}
+}  // namespace
 }  // namespace kd
 
 extern "C" int kd_set_option(const char* name, int value) {
   if (!name) return fail(KD_EINVAL, "kd_set_option: null name");
   const int i = option_index(name);
   if (i < 0) return fail(KD_EINVAL, "kd_set_option: unknown option '%s'", name);
-  if (value == INT_MIN) {                 // back to the built-in default of every call site
-    g_opts[i].set.store(false, std::memory_order_relaxed);
-    return KD_OK;
-  }
-  g_opts[i].value.store(value, std::memory_order_relaxed);
-  g_opts[i].set.store(true, std::memory_order_relaxed);
+  g_set[i].store(value != INT_MIN, std::memory_order_relaxed);
+  g_opt[i].store(value != INT_MIN ? value : g_rows[i].dflt, std::memory_order_relaxed);          // INT_MIN: back to the table's default
   return KD_OK;
 }
-extern "C" int kd_get_option(const char* name, int dflt) { return name ? option_at(option_index(name), dflt) : dflt; }
+// the caller-set value, else `dflt`; dflt == INT_MIN asks for the built-in default
+extern "C" int kd_get_option(const char* name, int dflt) {
+  const int i = name ? option_index(name) : -1;
+  if (i < 0) return dflt;
+  return g_set[i].load(std::memory_order_relaxed) || dflt == INT_MIN ? g_opt[i].load(std::memory_order_relaxed) : dflt;
+}
 
 extern "C" int kd_version(void) { return 200; }
 extern "C" const char* kd_last_error(void) { return err_buf(); }

@@ -464,10 +464,10 @@ using namespace kd::b16;
 extern "C" int kd_ffn_bf16_supported(int M, int K, int d_ff) {
   // below ~16k rows the panels do not fill the chip and the two-kernel form (row-parallel over more, smaller units) is faster
   // (option "ffn_bf16_min_rows": A/B runs at small batches)
-  if (!(M >= option("ffn_bf16_min_rows", 16384) && d_ff > 0 && d_ff % 64 == 0 && option("ffn_fused", 1))) return 0;
+  if (!(M >= opt(KD_OPT_ffn_bf16_min_rows) && d_ff > 0 && d_ff % 64 == 0 && opt(KD_OPT_ffn_fused))) return 0;
   // K = 256: correct, but measured level with the two-kernel form (65.1 vs 65.6 us at the level-1 shape; 8 300 clocks per tile for 3 072
   // matrix clocks with one wave per SIMD) -- on request only ("ffn_fused_256")
-  return (K == 128 || (K == 256 && option("ffn_fused_256", 0))) ? 1 : 0;
+  return (K == 128 || (K == 256 && opt(KD_OPT_ffn_fused_256))) ? 1 : 0;
 }
 
 extern "C" int kd_ffn_bf16(const KdFfn* dp, void* stream) {
@@ -483,7 +483,7 @@ extern "C" int kd_ffn_bf16(const KdFfn* dp, void* stream) {
   a.scale = d.scale; a.scale_stride = d.scale_stride; a.rows_per_sample = d.rows_per_sample; a.eps = d.eps;
   a.M = d.M; a.n_tiles = d.d_ff / 64;
   a.clk = g_clk;
-  a.warm = option("code_warm", KD_CODE_WARM_DEFAULT);
+  a.warm = code_warm();
   if (d.attn && d.K != 128) return fail(KD_EINVAL, "kd_ffn_bf16: the fused out projection needs K == 128 (K=%d)", d.K);
   if (d.K == 256) {
     constexpr int LDS256 = 9 * WBLK;
@@ -495,7 +495,7 @@ extern "C" int kd_ffn_bf16(const KdFfn* dp, void* stream) {
   // 1 (default) plain, 3 skewed wave pairs.  Measured equal within noise (64.5 / 68.6 us at the level-0 shape; a third form with
   // one wave per SIMD and the two row blocks' MFMA / GEGLU streams interleaved instruction by instruction took 71 us):
   // profiles/r02_ffn_fused.md -- under this kernel the chip runs against its power limit and re-arranging the same work buys nothing.
-  const int variant = option("ffn_variant", 1);
+  const int variant = opt(KD_OPT_ffn_variant);
   const bool outp = d.attn != nullptr;
   if (outp) {
     if (!d.Wp_out) return fail(KD_EINVAL, "kd_ffn_bf16: attn without Wp_out");

@@ -542,7 +542,7 @@ static int launch_ffn(const FArgs3& a, const char* nm, double flops, double byte
 using namespace kd;
 
 extern "C" int kd_ffn_f32_supported(int M, int K, int d_ff) {
-  if (!option("ffn_x3", 1)) return 0;
+  if (!opt(KD_OPT_ffn_x3)) return 0;
   if (!((K == 128 || K == 256) && d_ff > 0 && d_ff % 64 == 0)) return 0;
   // Where it is the FASTER form.  Width 128 (two workgroups per CU, ~55 us per workgroup): from 16 row panels on.  Width 256 runs ONE workgroup per CU
   // for ~120 us whatever the grid, so below a chip-filling grid the two-launch form (GEGLU projection with n-splits + residual projection, both of which
@@ -552,7 +552,7 @@ extern "C" int kd_ffn_f32_supported(int M, int K, int d_ff) {
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  const int need = option("ffn_x3_min_panels_256", cus - cus / 8);
+  const int need = opt_or(KD_OPT_ffn_x3_min_panels_256, cus - cus / 8);
   return (M + 127) / 128 >= need;
 }
 
@@ -567,7 +567,7 @@ extern "C" int kd_ffn_f32(const KdFfn* dp, void* stream) {
   a.Wu = reinterpret_cast<const char*>(d.Wp_up); a.Wd = reinterpret_cast<const char*>(d.Wp_down);
   a.scale = d.scale; a.scale_stride = d.scale_stride; a.rows_per_sample = d.rows_per_sample; a.eps = d.eps;
   a.M = d.M; a.d_ff = d.d_ff; a.n_tiles = d.d_ff / 64;
-  a.warm = option("code_warm", KD_CODE_WARM_DEFAULT);
+  a.warm = code_warm();
   a.clk = x3::g_clk;
   const double flops = 2.0 * d.M * 3.0 * d.d_ff * d.K;
   const double bytes = 4.0 * (2.0 * d.M * d.K + 3.0 * d.d_ff * d.K);
@@ -579,7 +579,7 @@ extern "C" int kd_ffn_f32(const KdFfn* dp, void* stream) {
     if (d.K == 128) return x3::launch_ffn_half<true>(a, nm, fl2, by2, (hipStream_t)stream);
     return x3::launch_ffn<16, true>(a, nm, fl2, by2, (hipStream_t)stream);
   }
-  if (d.K == 128 && option("ffn_x3_half", 1)) return x3::launch_ffn_half<false>(a, nm, flops, bytes, (hipStream_t)stream);
+  if (d.K == 128 && opt(KD_OPT_ffn_x3_half)) return x3::launch_ffn_half<false>(a, nm, flops, bytes, (hipStream_t)stream);
   if (d.K == 128) return x3::launch_ffn<8>(a, nm, flops, bytes, (hipStream_t)stream);
   return x3::launch_ffn<16>(a, nm, flops, bytes, (hipStream_t)stream);
 }

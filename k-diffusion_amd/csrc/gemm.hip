@@ -611,8 +611,8 @@ extern "C" int kd_gemm_f32(const KdGemm* dp, void* stream) {
   if (d.c_split && !d.C_lo) return fail(KD_EINVAL, "kd_gemm_f32: c_split needs C_lo");
   GemmP e;
   static_cast<KdGemm&>(e) = d;
-  e.debug = option("gemm_debug", 0);
-  e.warm = option("code_warm", KD_CODE_WARM_DEFAULT);
+  e.debug = opt(KD_OPT_gemm_debug);
+  e.warm = code_warm();
   if (e.rows_per_sample <= 0) e.rows_per_sample = e.M;
   // all rows of a 128-row tile share their scale vector: stage it in LDS once per tile
   e.scale_tab = e.norm && e.a_mode == KD_A_PLAIN && e.K <= SCALE_TAB_MAX_K && (e.scale_stride == 0 || e.rows_per_sample % BM == 0);
@@ -624,13 +624,13 @@ extern "C" int kd_gemm_f32(const KdGemm* dp, void* stream) {
     return fail(KD_EINVAL, "kd_gemm_f32: no kernel for pre-split A with epi=%d M=%d N=%d K=%d (K %% 32, N %% 128 (GEGLU: 64))", d.epi, d.M, d.N, d.K);
   }
   {
-    const bool skinny_on = option("skinny", 1) != 0;
+    const bool skinny_on = opt(KD_OPT_skinny) != 0;
     int rc = 0;
     if (skinny_on && !gemm_skinny_try(e, s, &rc)) return rc;   // <= 128 rows (one per sample): the conditioning chain
     if (!gemm_x3s_try(e, s, &rc)) return rc;                   // few rows (small batches), split3: the latency form, gemm_x3s.hip
   }
   {
-    const bool astat_on = option("astat", 1) != 0;
+    const bool astat_on = opt(KD_OPT_astat) != 0;
     int rc = 0;
     if (astat_on && !gemm_x3_try(e, s, &rc)) return rc;        // norm -> wide projection, split3: round-3 A-stationary kernel (gemm_x3.hip)
     if (e.c_split) return fail(KD_EINVAL, "kd_gemm_f32: c_split is produced by the GEGLU projections of gemm_x3.hip (K = 128 / 256, norm) and gemm_x3t.hip (a_split) only");
@@ -642,7 +642,7 @@ extern "C" int kd_gemm_f32(const KdGemm* dp, void* stream) {
   {
     // residual / plain projections whose tiles do not even fill the chip once and that walk a long K: split K inside the
     // workgroup (two wave groups, deterministic in-LDS reduction)
-    const bool ks_on = option("ksplit", 1) != 0;
+    const bool ks_on = opt(KD_OPT_ksplit) != 0;
     const long tiles = (long)((e.M + BM - 1) / BM) * ((e.N + BN - 1) / BN);
     const int nk = (e.K + BK - 1) / BK;
     if (ks_on && e.precision == KD_PREC_SPLIT3 && e.Wp && e.a_mode == KD_A_PLAIN && !e.norm && !e.debug && tiles <= 256 && nk >= 8 && nk % 4 == 0) {

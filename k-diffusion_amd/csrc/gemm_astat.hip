@@ -280,7 +280,7 @@ static int launch(const GemmP& d, hipStream_t s) {
   const CfgName cfg(nm, "splits%d,waves%d", splits, NWV);
   LaunchScope prof(cfg, 2.0 * d.M * n_eff * d.K, 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N), s);
   GemmP e = d;
-  if (option("astat_storewait", 0)) e.debug |= 32;
+  if (opt(KD_OPT_astat_storewait)) e.debug |= 32;
   kd::launch<gemm_astat_kernel<NC, EPI, NWV>>(dim3((unsigned)panels, (unsigned)splits), dim3(64 * NWV), LDS_BYTES, s, e);
   return check_launch("kd_gemm_f32(astat)");
 }
@@ -292,7 +292,7 @@ int gemm_astat_try(const GemmP& d, hipStream_t s, int* rc) {
   using namespace astat;
   if (d.precision != KD_PREC_SPLIT3 || d.a_mode != KD_A_PLAIN || !d.norm || !d.Wp || (d.debug & ~32)) return 1;
   if (d.epi != KD_EPI_STORE && d.epi != KD_EPI_QKV && d.epi != KD_EPI_GEGLU) return 1;
-  const int max_k = option("astat_max_k", 512);    // A/B switch for benchmarks/
+  const int max_k = opt(KD_OPT_astat_max_k);    // A/B switch for benchmarks/
   if ((d.K != 128 && d.K != 256 && d.K != 512) || d.K > max_k) return 1;
   const int ncol = d.epi == KD_EPI_GEGLU ? 64 : 128;
   if (d.N % ncol || d.N / ncol < 2) return 1;                                   // one n-tile: nothing to amortise
@@ -303,7 +303,7 @@ int gemm_astat_try(const GemmP& d, hipStream_t s, int* rc) {
   // (K = 128) and the panel grid still fills the chip.  Measured neutral against two co-resident 4-wave workgroups
   // (level-0 qkv 59 -> 65 us, GEGLU 117 -> 114 us, end to end -0.4 %: profiles/r01_astat_ablation.md), so the 4-wave
   // form stays the default: halving the W bytes into the CU is not what the main loop waits for.
-  const int max_waves = option("astat_waves", 4);
+  const int max_waves = opt(KD_OPT_astat_waves);
   const bool wide = max_waves >= 8 && d.K == 128 && d.M >= 256 * 2 * BM && (d.scale_stride == 0 || d.rows_per_sample % (2 * BM) == 0) &&
                     (d.epi != KD_EPI_QKV || d.rows_per_sample % (2 * BM) == 0);
 #define KD_AS(NCV, EP) if (d.K == NCV * 16 && d.epi == EP) { *rc = launch<NCV, EP, 4>(d, s); return 0; }

@@ -264,14 +264,14 @@ namespace b16 {
 // Options: "b16s_max_rows" (4096; 0 = off), "b16s_max_wgs" (-1; >= 0: a cap on the grid instead of the rule).
 int gemm_b16s_try(const KdGemm& d, hipStream_t s, int* rc) {
   using namespace b16s;
-  if (d.M > option("b16s_max_rows", 4096)) return 1;
+  if (d.M > opt(KD_OPT_b16s_max_rows)) return 1;
   if (d.precision != KD_PREC_BF16 || d.a_mode != KD_A_PLAIN || !d.Wp || d.a_split || d.c_split) return 1;
   if ((d.K & 63) || d.out_add != 0.f) return 1;
   const bool geglu = d.epi == KD_EPI_GEGLU;
   if (d.N % (geglu ? 32 : 64)) return 1;
   const int cus = cu_count();
   const long wgs = (long)((d.M + 31) / 32) * (d.N / (geglu ? 32 : 64));
-  const int cap = option("b16s_max_wgs", -1);
+  const int cap = opt(KD_OPT_b16s_max_wgs);
   if (wgs > (cap >= 0 ? cap : ((d.norm && d.M <= 512) ? 2 * cus : cus))) return 1;
   SArgs a{};
   a.A = reinterpret_cast<const u16*>(d.A); a.Wp = reinterpret_cast<const char*>(d.Wp); a.C = reinterpret_cast<u16*>(d.C);

@@ -283,7 +283,7 @@ static int launch_wstat(const GArgs& a, int lds, const char* nm, double flops, d
 
 // Eligibility + dispatch.  Returns 1 if the descriptor was not taken.
 int gemm_wstat_try(const KdGemm& d, hipStream_t s, int* rc) {
-  if (d.a_mode != KD_A_PLAIN || !d.Wp || !option("wstat", 1)) return 1;
+  if (d.a_mode != KD_A_PLAIN || !d.Wp || !opt(KD_OPT_wstat)) return 1;
   if (d.epi != KD_EPI_STORE && d.epi != KD_EPI_QKV && d.epi != KD_EPI_GEGLU && d.epi != KD_EPI_RESIDUAL) return 1;
   if (d.K != 128 && d.K != 256 && d.K != 384 && d.K != 512) return 1;
   if ((d.N & 31) || d.M < 2048) return 1;
@@ -300,7 +300,7 @@ int gemm_wstat_try(const KdGemm& d, hipStream_t s, int* rc) {
   const int n_slices = (n_tiles + max_tiles - 1) / max_tiles;
   // every slice re-reads (and, with a norm, re-normalises) A: mostly L2 / MALL hits, cheap next to a weight ring with barriers,
   // but a slice count near the CU count leaves too few row groups
-  if (n_slices > option("wstat_max_slices", 24) || n_slices * 4 > cu_count()) return 1;
+  if (n_slices > opt(KD_OPT_wstat_max_slices) || n_slices * 4 > cu_count()) return 1;
   const int tps = (n_tiles + n_slices - 1) / n_slices;
   GArgs a{};
   a.A = reinterpret_cast<const u16*>(d.A); a.Wp = reinterpret_cast<const char*>(d.Wp);
@@ -309,7 +309,7 @@ int gemm_wstat_try(const KdGemm& d, hipStream_t s, int* rc) {
   a.M = d.M; a.N = d.N; a.n_tiles = n_tiles; a.tiles_per_slice = tps; a.n_slices = n_slices;
   a.n_heads = d.n_heads; a.qk_scale = d.qk_scale; a.pos = d.rope_pos; a.freq = d.rope_freq;
   a.clk = g_clk;
-  a.warm = option("code_warm", KD_CODE_WARM_DEFAULT);
+  a.warm = code_warm();
   const int lds = tps * nk * WBLK;
   const double n_eff = geglu ? 2.0 * d.N : (double)d.N;
   const double flops = 2.0 * d.M * n_eff * d.K;
@@ -318,7 +318,7 @@ int gemm_wstat_try(const KdGemm& d, hipStream_t s, int* rc) {
   // 0 plain (default), 1 next-chunk prefetch, 2 software-pipelined tiles (qkv / GEGLU at K = 128).  All three measure the same
   // within noise (profiles/r02_wstat_ablation.md): under these kernels the chip runs at 1.6-2.2 GHz (s_memtime / s_memrealtime),
   // i.e. against its power limit, where re-arranging the same work buys nothing
-  const int pf = option("wstat_prefetch", 0);
+  const int pf = opt(KD_OPT_wstat_prefetch);
 #define KD_WS(NCV, EP, NO, NWV)                                                                                        \
   {                                                                                                                    \
     constexpr bool can_pipe = NCV == 8 && (EP == KD_EPI_QKV || EP == KD_EPI_GEGLU);                                    \
@@ -335,7 +335,7 @@ int gemm_wstat_try(const KdGemm& d, hipStream_t s, int* rc) {
     if (d.epi == KD_EPI_STORE) KD_WS(NCV, KD_EPI_STORE, false, NWV)               \
     if (d.epi == KD_EPI_RESIDUAL) KD_WS(NCV, KD_EPI_RESIDUAL, false, NWV)         \
   }
-  const int ww = option("wstat_waves", 0);        // 0: per-shape default (8 waves: 2 per SIMD, up to 256 registers each)
+  const int ww = opt(KD_OPT_wstat_waves);        // 0: per-shape default (8 waves: 2 per SIMD, up to 256 registers each)
   if (d.K == 128 && ww == 12) KD_WS_ALL(8, 12)
   if (d.K == 128 && ww == 4) KD_WS_ALL(8, 4)
   if (d.K == 128) KD_WS_ALL(8, 8)
@@ -628,21 +628,21 @@ int gemm_tiled_try(const KdGemm& d, hipStream_t s, int* rc) {
   a.C = reinterpret_cast<u16*>(d.C); a.R = reinterpret_cast<const u16*>(d.R); a.fac = d.fac;
   a.M = d.M; a.N = d.N; a.K = d.K; a.n_tiles_n = (d.N + 127) / 128; a.nk = d.K / 64;
   a.gh = d.gh; a.gw = d.gw; a.cin = d.K >> 2;
-  a.warm = option("code_warm", KD_CODE_WARM_DEFAULT);
+  a.warm = code_warm();
   const double flops = 2.0 * d.M * (double)d.N * d.K;
   const double bytes = 2.0 * ((double)d.M * d.K + (double)d.N * d.K + (double)d.M * d.N) + (d.epi != KD_EPI_STORE ? 2.0 * d.M * d.N : 0.0);
   const ProfName nm("gemm_tiled", "gemm_bf16_tiled<a%d,e%d> M=%d N=%d K=%d", d.a_mode, d.epi, d.M, d.N, d.K);
   // 256-row tiles halve the weight traffic per flop; worth it once they still give every CU a workgroup
   const long tiles256 = (long)((d.M + 255) / 256) * a.n_tiles_n, tiles128 = (long)((d.M + 127) / 128) * a.n_tiles_n;
-  const int bmt = option("tiled_bm", 0);
+  const int bmt = opt(KD_OPT_tiled_bm);
   const bool big = bmt ? bmt == 256 : tiles256 >= cu_count();
   // 4-slot ring for grids of at most one tile per CU: measured no better than the 2-slot form (level-2 shapes 10.2 vs 9.5 us,
   // 21.5 vs 21.5: the block latency is not what those steps wait for) -- on request only
-  const bool deep = !big && tiles128 <= cu_count() && option("tiled_deep", 0);
+  const bool deep = !big && tiles128 <= cu_count() && opt(KD_OPT_tiled_deep);
   // round 4: grids of at most ONE tile per CU (the level-2 shapes) on the loader-wave form (4-slot ring, 4 compute + 4 staging waves)
   // (from 12 K steps on: with fewer the launch's fixed cost decides and the smaller 2-slot form is ahead -- level-2 out projection 13.8 vs 14.2 us,
   // the 256-wide MNIST / CIFAR levels +4 us per launch: profiles/r04_tiled_bf16_bench.log, r04_small_batch.log)
-  const bool lw = !big && tiles128 <= cu_count() && d.K >= 768 && option("tiled_lw", 1);
+  const bool lw = !big && tiles128 <= cu_count() && d.K >= 768 && opt(KD_OPT_tiled_lw);
 #define KD_TL(AM, EP)                                                                       \
   if (d.a_mode == AM && d.epi == EP) {                                                      \
     *rc = big ? launch_tiled<AM, EP, 2>(a, nm, flops, bytes, s)                             \
@@ -913,7 +913,7 @@ static int launch_astat(const GArgs& a, const char* nm, double flops, double byt
   // panels x n-splits: 128-row panels, two workgroups per CU, n-tiles split until the grid fills them ("astat_rows" = 256: the
   // 256-row / one-workgroup-per-CU form).
   // n-splits of a panel: best_n_splits with the row prologue at about one n-tile's worth of time (profiles/r02_astat_timeline.md)
-  const int forced = option("astat_splits", 0), rows = option("astat_rows", 0);
+  const int forced = opt(KD_OPT_astat_splits), rows = opt(KD_OPT_astat_rows);
   const int p256 = (a.M + 255) / 256, s256 = best_n_splits(p256, a.n_tiles, cu_count(), 1);
   // measured (harness "astat", profiles/r02_harness_astat_rows.log): the 256-row form is never faster (L1 qkv 30.4 vs 28.2 us, L2 qkv
   // 47.0 vs 38.6, the GEGLU shapes equal) -- the L2 -> LDS stream it halves is not what limits these kernels -- so it runs on request only
@@ -924,7 +924,7 @@ static int launch_astat(const GArgs& a, const char* nm, double flops, double byt
 }
 
 int gemm_astat_try(const KdGemm& d, hipStream_t s, int* rc) {
-  if (d.a_mode != KD_A_PLAIN || !d.Wp || !d.norm || !option("astat_bf16", 1)) return 1;
+  if (d.a_mode != KD_A_PLAIN || !d.Wp || !d.norm || !opt(KD_OPT_astat_bf16)) return 1;
   if (d.epi != KD_EPI_STORE && d.epi != KD_EPI_QKV && d.epi != KD_EPI_GEGLU) return 1;
   if (d.K != 256 && d.K != 512) return 1;
   if (d.epi == KD_EPI_STORE && d.out_add != 0.f) return 1;
@@ -938,7 +938,7 @@ int gemm_astat_try(const KdGemm& d, hipStream_t s, int* rc) {
   a.M = d.M; a.N = d.N; a.n_tiles = d.N / ncol;
   a.n_heads = d.n_heads; a.qk_scale = d.qk_scale; a.pos = d.rope_pos; a.freq = d.rope_freq;
   a.clk = g_clk;
-  a.warm = option("code_warm", KD_CODE_WARM_DEFAULT);
+  a.warm = code_warm();
   const double n_eff = geglu ? 2.0 * d.N : (double)d.N;
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 2.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N);
@@ -1302,7 +1302,7 @@ extern "C" int kd_gemm_bf16(const KdGemm* dp, void* stream) {
   int rc = 0;
   // shape-driven choice (benchmarks/hip_harness, profiles/r02_*): level-0 shapes (K = 128, and K = 384 with N = 128) park the
   // weight; norm projections at K = 256 / 512 keep A in registers and stream the weight; the rest is tiled
-  if (!option("bf16_fast", 1)) {
+  if (!opt(KD_OPT_bf16_fast)) {
     if (!b16::gemm_generic_try(d, s, &rc)) return rc;
     return fail(KD_EINVAL, "kd_gemm_bf16: no generic kernel for a_mode=%d epi=%d N=%d", d.a_mode, d.epi, d.N);
   }

@@ -518,7 +518,7 @@ extern "C" int kd_pack_weight_mx8(const float* W, void* out, int N, int K, int g
 //   norm = 0, a_split = 1 (epi = KD_EPI_STORE / KD_EPI_RESIDUAL; K in {256, 512, 768, 1536}, N a multiple of 128): A is such an e4m3 tensor
 //            (A = [M, K] bytes, A_lo = [M, K / 32] scale bytes): the tiled kernel, both operands by LDS-DMA (the fp8 mode's down projection).
 extern "C" int kd_gemm_mx8_supported(int M, int N, int K, int epi, int norm) {
-  if (M < 128 || !option("mx8", 1)) return 0;
+  if (M < 128 || !opt(KD_OPT_mx8)) return 0;
   if (!norm) return (epi == KD_EPI_STORE || epi == KD_EPI_RESIDUAL) && (K == 256 || K == 512 || K == 768 || K == 1536) && N > 0 && N % 128 == 0;
   if (K != 256 && K != 512) return 0;
   if (epi == KD_EPI_GEGLU) return N > 0 && N % 64 == 0;
@@ -535,7 +535,7 @@ static int mx8_tiled(const KdGemm& d, hipStream_t s) {
   const int n_tiles_n = d.N / 128, nkb = d.K / 128;
   TArgs8 a{reinterpret_cast<const unsigned char*>(d.A), reinterpret_cast<const unsigned*>(d.A_lo), reinterpret_cast<const char*>(d.Wp),
            reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(d.Wp) + (size_t)n_tiles_n * nkb * WBLK), reinterpret_cast<u16*>(d.C),
-           reinterpret_cast<const u16*>(d.R), d.M, d.N, d.K, n_tiles_n, option("code_warm", KD_CODE_WARM_DEFAULT)};
+           reinterpret_cast<const u16*>(d.R), d.M, d.N, d.K, n_tiles_n, code_warm()};
   const long tiles = (long)((d.M + 127) / 128) * n_tiles_n;
   const bool deep = tiles <= cu_count();              // at most one tile per CU: a 4-slot ring instead of two workgroups per CU
   const double flops = 2.0 * d.M * (double)d.N * d.K;
@@ -574,10 +574,10 @@ extern "C" int kd_gemm_mx8(const KdGemm* dp, void* stream) {
           reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(d.Wp) + (size_t)n_tiles * nkb * WBLK), reinterpret_cast<u16*>(d.C),
           reinterpret_cast<unsigned char*>(d.C), reinterpret_cast<unsigned char*>(d.C_lo),
           d.scale, d.scale_stride, d.rows_per_sample, d.eps, d.M, d.N, n_tiles, 1,
-          d.n_heads, d.qk_scale, d.rope_pos, d.rope_freq, option("code_warm", KD_CODE_WARM_DEFAULT), g_clk};
+          d.n_heads, d.qk_scale, d.rope_pos, d.rope_freq, code_warm(), g_clk};
   // n-splits of a panel: two workgroups per CU, a row prologue costs about two n-tiles
   const int panels = (d.M + 127) / 128, best = best_n_splits(panels, n_tiles, 2 * cu_count(), 2);
-  const int forced = option("mx8_splits", 0);
+  const int forced = opt(KD_OPT_mx8_splits);
   a.n_splits = forced > 0 && forced <= n_tiles ? forced : best;
   if ((n_tiles + a.n_splits - 1) / a.n_splits > 64) return fail(KD_EINVAL, "kd_gemm_mx8: more than 64 n-tiles per workgroup (N=%d)", d.N);
   hipStream_t s = (hipStream_t)stream;

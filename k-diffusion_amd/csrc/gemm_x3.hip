@@ -726,7 +726,7 @@ static int launch(const XArgs& a0, const char* nm, double flops, double bytes, h
   constexpr int K = NC * 16, NSTG = NC <= 8 ? 4 : 8;
   constexpr int LDS = NSTG * STG + 4 * (K * 4 < 1024 ? 1024 : K * 4) + 4 * 2048 + 1024;     // ring + scale vectors + store strips + per-head constants
   const int panels = (a0.M + 127) / 128, best = best_n_splits(panels, a0.n_tiles, (NC <= 8 ? 2 : 1) * cu_count(), 1);
-  const int forced = force_splits ? force_splits : option("x3_splits", 0);
+  const int forced = force_splits ? force_splits : opt(KD_OPT_x3_splits);
   XArgs a = a0;
   a.n_splits = forced > 0 && forced <= a0.n_tiles ? forced : best;      // (any count up to n_tiles: panel_split hands out proportional, non-empty shares)
   const CfgName cfg(nm, "splits%d", a.n_splits);
@@ -740,7 +740,7 @@ static int launch_half(const XArgs& a0, const char* nm, double flops, double byt
   constexpr int LDS = 4 * STG + 4 * 1024 + 4 * 2048 + 1024;
   // the same cost model as launch() with two resident workgroups per CU; a prologue costs about two half tiles
   const int panels = (a0.M + 127) / 128, best = best_n_splits(panels, a0.n_tiles, 2 * cu_count(), 2);
-  const int forced = option("x3_splits", 0);
+  const int forced = opt(KD_OPT_x3_splits);
   XArgs a = a0;
   a.n_splits = forced > 0 && forced <= a0.n_tiles && a0.n_tiles % forced == 0 ? forced : best;
   const CfgName cfg(nm, "splits%d", a.n_splits);
@@ -754,18 +754,18 @@ static int launch_half(const XArgs& a0, const char* nm, double flops, double byt
 // Eligibility + dispatch (called by kd_gemm_f32 ahead of the round-1 A-stationary kernel).  Returns 1 if the descriptor was not taken.
 int gemm_x3_try(const GemmP& d, hipStream_t s, int* rc) {
   using namespace x3;
-  if (!option("x3", 1)) return 1;
+  if (!opt(KD_OPT_x3)) return 1;
   if (d.precision != KD_PREC_SPLIT3 || d.a_mode != KD_A_PLAIN || !d.Wp || d.debug) return 1;
   const bool unpatch = d.epi == KD_EPI_UNPATCH_NCHW;
-  if (unpatch && (d.K != 128 || !d.norm || d.ph != 4 || d.pw != 4 || d.N != 16 * d.chan || d.N > 64 || !option("x3_unpatch", 1))) return 1;
+  if (unpatch && (d.K != 128 || !d.norm || d.ph != 4 || d.pw != 4 || d.N != 16 * d.chan || d.N > 64 || !opt(KD_OPT_x3_unpatch))) return 1;
   if (d.epi != KD_EPI_STORE && d.epi != KD_EPI_QKV && d.epi != KD_EPI_GEGLU && d.epi != KD_EPI_RESIDUAL && !unpatch) return 1;
   // norm -> wide projection, or (round 3) the plain residual projection behind the attention core: C = R + A W^T
   // (on request, option "x3_res": gemm_x3r.hip takes that shape by default, 24.2 us.  K = 512 only: 25.3 vs 27.1 us at the headline shape; at K = 128 it is level with the round-1 tile kernel (both at the memory roof) and
   // at K = 256 slower, 32.0 vs 26.4 us -- a workgroup there pays a whole row prologue for one or two n-tiles: benchmarks/x3_bench.py)
-  if (d.epi == KD_EPI_RESIDUAL ? (d.norm || !d.R || d.K != 512 || !option("x3_res", 0)) : !d.norm) return 1;
+  if (d.epi == KD_EPI_RESIDUAL ? (d.norm || !d.R || d.K != 512 || !opt(KD_OPT_x3_res)) : !d.norm) return 1;
   if (d.K != 128 && d.K != 256 && d.K != 512) return 1;
   const int ncol = d.epi == KD_EPI_GEGLU ? 64 : 128;
-  if ((!unpatch && d.N % ncol) || d.M < option("x3_min_rows", 512) || (d.norm && d.rows_per_sample <= 0)) return 1;
+  if ((!unpatch && d.N % ncol) || d.M < opt(KD_OPT_x3_min_rows) || (d.norm && d.rows_per_sample <= 0)) return 1;
   if (d.epi == KD_EPI_QKV && (!d.rope_pos || !d.rope_freq || d.n_heads > 16)) return 1;   // tables only / many heads: round-1 kernel
   if (d.c_split && (d.epi != KD_EPI_GEGLU || !d.C_lo || (d.N & 31))) return 1;
   XArgs a{};
@@ -781,7 +781,7 @@ int gemm_x3_try(const GemmP& d, hipStream_t s, int* rc) {
   const double n_eff = d.epi == KD_EPI_GEGLU ? 2.0 * d.N : (double)d.N;
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N * (d.epi == KD_EPI_RESIDUAL || (unpatch && d.sigma) ? 2 : 1));
-  const bool half = d.K == 256 && d.epi != KD_EPI_RESIDUAL && !d.c_split && option("x3_half", 1);      // two workgroups per CU, half tiles
+  const bool half = d.K == 256 && d.epi != KD_EPI_RESIDUAL && !d.c_split && opt(KD_OPT_x3_half);      // two workgroups per CU, half tiles
   const ProfName nm("gemm_x3_astat", half ? "gemm_x3_astat<e%d,h> M=%d N=%d K=%d" : "gemm_x3_astat<e%d> M=%d N=%d K=%d", d.epi, d.M, d.N, d.K);
   if (half) {
     a.n_tiles = d.N / (d.epi == KD_EPI_GEGLU ? 32 : 64);

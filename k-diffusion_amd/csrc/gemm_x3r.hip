@@ -318,8 +318,8 @@ template <int AMODE, int EPI>
 static int launch(const RArgs& a, const char* nm, double flops, double bytes, hipStream_t s) {
   // (the in-kernel time stamps of kd_prof_clock_buffer are their own instantiation: run-time `if (probe)` blocks inside the K loop split
   // it into several basic blocks, which the instruction scheduler does not cross)
-  if (a.clk) return option("x3r_lw", 1) ? launch_lw<AMODE, EPI, true, true>(a, nm, flops, bytes, s) : launch_lw<AMODE, EPI, false, true>(a, nm, flops, bytes, s);
-  return option("x3r_lw", 1) ? launch_lw<AMODE, EPI, true, false>(a, nm, flops, bytes, s) : launch_lw<AMODE, EPI, false, false>(a, nm, flops, bytes, s);
+  if (a.clk) return opt(KD_OPT_x3r_lw) ? launch_lw<AMODE, EPI, true, true>(a, nm, flops, bytes, s) : launch_lw<AMODE, EPI, false, true>(a, nm, flops, bytes, s);
+  return opt(KD_OPT_x3r_lw) ? launch_lw<AMODE, EPI, true, false>(a, nm, flops, bytes, s) : launch_lw<AMODE, EPI, false, false>(a, nm, flops, bytes, s);
 }
 
 }  // namespace x3r
@@ -327,14 +327,14 @@ static int launch(const RArgs& a, const char* nm, double flops, double bytes, hi
 // Eligibility + dispatch (called by kd_gemm_f32 ahead of the round-1 tile kernel).  Returns 1 if the descriptor was not taken.
 int gemm_x3r_try(const GemmP& d, hipStream_t s, int* rc) {
   using namespace x3r;
-  const int mode = option("x3r", 1);
+  const int mode = opt(KD_OPT_x3r);
   if (!mode) return 1;
   if (d.precision != KD_PREC_SPLIT3 || d.norm || !d.Wp || d.debug || d.a_split || d.c_split) return 1;
   if (d.a_mode != KD_A_PLAIN && d.a_mode != KD_A_MERGE2x2) return 1;
   if (d.epi != KD_EPI_STORE && d.epi != KD_EPI_RESIDUAL && d.epi != KD_EPI_SPLIT_LERP) return 1;
-  if (d.epi == KD_EPI_SPLIT_LERP && (d.a_mode != KD_A_PLAIN || !d.R || !d.fac || ((d.N >> 2) & 127) || d.gh <= 0 || d.gw <= 0 || d.M % (d.gh * d.gw) || !option("x3r_split", 1)))
+  if (d.epi == KD_EPI_SPLIT_LERP && (d.a_mode != KD_A_PLAIN || !d.R || !d.fac || ((d.N >> 2) & 127) || d.gh <= 0 || d.gw <= 0 || d.M % (d.gh * d.gw) || !opt(KD_OPT_x3r_split)))
     return 1;                        // (an n-tile inside one quadrant: cout % 128 == 0)
-  if ((d.K & 31) || (d.N & 127) || d.M < option("x3r_min_rows", 128) || d.out_add != 0.f) return 1;
+  if ((d.K & 31) || (d.N & 127) || d.M < opt(KD_OPT_x3r_min_rows) || d.out_add != 0.f) return 1;
   // One workgroup per CU (136 KiB of LDS).  Round 3 took only grids of at most one tile per CU (the level-2 projections and the merge into
   // level 2); with the loader waves and the one-basic-block K loop of round 4 the kernel is level with or ahead of the round-1 tile kernel's
   // two workgroups per CU on every shape with K >= 256 (benchmarks/x3r_bench.py, batch 32: merge into level 1 31 vs 35 us, level-1 out

@@ -401,7 +401,7 @@ int gemm_x3s_try(const GemmP& d, hipStream_t s, int* rc) {
   // against gemm_x3r's 26.9 us; M = 256 qkv: 10.4 against 34.8) and at two rounds where K is short or the rows are few (M = 256 GEGLU of
   // 1536: 17.1 against 29.4), and loses beyond (M = 2048, N = 512, K = 1536 in two rounds: 34.0 against 29.1; M = 1024 GEGLU of 768 in three:
   // 17.4 against 13.9).  Option "x3s_max_wgs" replaces the estimate by a cap on the grid (tests, A/B runs).
-  const int max_rows = option("x3s_max_rows", 4096);
+  const int max_rows = opt(KD_OPT_x3s_max_rows);
   if (d.M > max_rows) return 1;
   if (d.precision != KD_PREC_SPLIT3 || d.a_mode != KD_A_PLAIN || !d.Wp || d.debug || d.a_split) return 1;
   if ((d.K & 31) || d.K < 64) return 1;
@@ -412,10 +412,10 @@ int gemm_x3s_try(const GemmP& d, hipStream_t s, int* rc) {
   // variant (option x3s_scale_lds, off): the scale vector through LDS where a workgroup's 32 rows share it.  A quarter less through the L1,
   // but measured level with the per-lane loads (17.7 / 12.7 / 10.6 against 17.1 / 12.8 / 10.3 us): the kernel waits on latency, not on the L1
   const int rps = d.rows_per_sample > 0 ? d.rows_per_sample : d.M;
-  const int sc = !d.norm ? 0 : (((d.scale_stride == 0 || rps % 32 == 0) && d.K <= SCL_MAX_K && option("x3s_scale_lds", 0)) ? 2 : 1);
+  const int sc = !d.norm ? 0 : (((d.scale_stride == 0 || rps % 32 == 0) && d.K <= SCL_MAX_K && opt(KD_OPT_x3s_scale_lds)) ? 2 : 1);
   const int cus = cu_count();
   const long wgs = (long)((d.M + 31) / 32) * (d.N / (geglu ? 32 : 64));
-  const int cap = option("x3s_max_wgs", -1);
+  const int cap = opt(KD_OPT_x3s_max_wgs);
   if (cap >= 0) {
     if (wgs > cap) return 1;
   } else {
@@ -436,7 +436,7 @@ int gemm_x3s_try(const GemmP& d, hipStream_t s, int* rc) {
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N * (d.epi == KD_EPI_RESIDUAL ? 2 : 1));
   const ProfName nm("gemm_x3s", "gemm_x3s<n%d,e%d> M=%d N=%d K=%d", sc, d.epi, d.M, d.N, d.K);
-  if (option("x3s_trace", 0)) {                 // debugging aid (kd_set_option): one line per launch on stderr, the stream drained in front of it
+  if (opt(KD_OPT_x3s_trace)) {                 // debugging aid (kd_set_option): one line per launch on stderr, the stream drained in front of it
     fprintf(stderr, "x3s: epi=%d norm=%d M=%d N=%d K=%d rps=%d stride=%d heads=%d packed=%d c_split=%d A=%p Wp=%p C=%p R=%p scale=%p pos=%p freq=%p\n", d.epi, d.norm, d.M, d.N, d.K,
             a.rows_per_sample, a.scale_stride, a.n_heads, a.qkv_packed, a.c_split, (const void*)a.A, (const void*)a.Wp, (void*)a.C, (const void*)a.R, (const void*)a.scale, (const void*)a.pos, (const void*)a.freq);
     (void)hipStreamSynchronize(s);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -31,7 +32,7 @@ __device__ __forceinline__ void st16(void* p, const V& v) {
 
 // the public descriptor plus what only the library sets (kept out of the ABI)
 struct GemmP : KdGemm {
-  int warm;         // code warm-up workgroups (code_warm_begin below; option "code_warm")
+  int warm;         // code warm-up workgroups (code_warm_begin below; code_warm())
   int debug;        // benchmarks/ only (kd_set_option("gemm_debug")): 1 no C stores, 2 no MFMA, 8 GEGLU without erf, 32 conservative store wait
   int scale_tab;    // norm scales of a tile's sample staged in LDS
 };
@@ -39,10 +40,19 @@ struct GemmP : KdGemm {
 // ---- error reporting (thread-local message, C ABI returns a code) -------------------------------
 char* err_buf();
 int fail(int code, const char* fmt, ...);
-// kd_set_option() values (tuning / A-B switches), thread-safe; `option("name", dflt)` with a string LITERAL costs one atomic load
-int option_index(const char* name);
-int option_at(int idx, int dflt);
-#define option(name, dflt) ::kd::option_at([]() -> int { static const int idx_ = ::kd::option_index(name); return idx_; }(), (dflt))
+// kd_set_option() values (tuning / A-B switches), thread-safe.  include/kdiff_options.def has one row per option (name, default, doc): it makes
+// the ids here and the slots in common.cpp, which start at the defaults.  opt(KD_OPT_<name>) is one relaxed atomic load.
+#define KD_OPTION(name, dflt, doc) KD_OPT_##name,
+enum {
+#include "../../include/kdiff_options.def"
+  KD_OPT_COUNT
+};
+#undef KD_OPTION
+constexpr int KD_OPT_AUTO = INT_MIN;      // default of a row whose launcher computes it: opt_or(id, computed)
+extern std::atomic<int> g_opt[KD_OPT_COUNT];
+inline int opt(int id) { return g_opt[id].load(std::memory_order_relaxed); }
+inline int opt_or(int id, int computed) { const int v = opt(id); return v == KD_OPT_AUTO ? computed : v; }
+inline int code_warm() { return opt(KD_OPT_code_warm); }      // the `warm` argument of every kernel that warms its code (code_warm_begin below)
 
 // ---- per-launch profiling (bench.py): hipEvent pairs around launches when enabled ---------------
 struct ProfRec { std::string name; hipEvent_t e0, e1; double flops, bytes; };

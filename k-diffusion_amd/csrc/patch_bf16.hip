@@ -243,11 +243,11 @@ static int launch_patch(const PArgs& a, int lds, const char* nm, double flops, d
 
 // Eligibility + dispatch of both kernels.  Returns 1 if the descriptor was not taken.
 int gemm_patch_try(const KdGemm& d, hipStream_t s, int* rc) {
-  if (!option("patch_fast", 1) || !d.Wp || d.pw != 4 || d.ph <= 0 || d.chan <= 0 || d.gh <= 0 || d.gw <= 0) return 1;
+  if (!opt(KD_OPT_patch_fast) || !d.Wp || d.pw != 4 || d.ph <= 0 || d.chan <= 0 || d.gh <= 0 || d.gw <= 0) return 1;
   const int feat = 4 * d.ph * d.chan;
   PArgs a{};
   a.Wp = reinterpret_cast<const char*>(d.Wp);
-  a.warm = option("code_warm", KD_CODE_WARM_DEFAULT);
+  a.warm = code_warm();
   a.scale = d.scale; a.scale_stride = d.scale_stride; a.rows_per_sample = d.rows_per_sample > 0 ? d.rows_per_sample : d.M; a.eps = d.eps;
   a.M = d.M; a.N = d.N; a.K = d.K; a.gh = d.gh; a.gw = d.gw; a.ph = d.ph; a.chan = d.chan;
   a.sigma = d.sigma; a.sigma_data = d.sigma_data;

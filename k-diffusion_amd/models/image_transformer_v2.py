@@ -298,7 +298,7 @@ def _mx8_ok(lib, mode, M, N, K, epi):
     """fp8 mode: this norm -> projection goes to the block-scaled fp8 matrix instruction (kd_gemm_mx8)."""
     # (from 4 096 rows on -- library option mx8_min_rows: below that the few-rows bf16 kernels are ahead -- batch 1: 0.512 against 0.552 ms
     # per forward, profiles/r06_bench_detail_full.json)
-    return mode == nat.PREC_FP8 and M >= lib.kd_get_option(b"mx8_min_rows", 4096) and bool(lib.kd_gemm_mx8_supported(M, N, K, epi, 1))
+    return mode == nat.PREC_FP8 and M >= lib.kd_get_option(b"mx8_min_rows", nat.OPTION_DEFAULT) and bool(lib.kd_gemm_mx8_supported(M, N, K, epi, 1))
 
 
 def route_layer(lib, mode, B, T, rps, d, d_ff, nh, attn, switches, grid=None, kernel_size=None):

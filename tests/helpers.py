@@ -6,15 +6,38 @@ import struct
 import torch
 
 
+PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "k-diffusion_amd")
+
+
 def source_options():
-    """Every option name the library's dispatch code reads: ``option("name", default)`` in k-diffusion_amd/csrc."""
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "k-diffusion_amd", "csrc")
+    """Every option name the library's dispatch code reads: ``opt(KD_OPT_name)`` / ``opt_or(KD_OPT_name, ...)`` in k-diffusion_amd/csrc."""
+    csrc = os.path.join(PKG, "csrc")
     names = set()
     for fn in os.listdir(csrc):
         if fn.endswith((".hip", ".cpp", ".h")):
-            names |= set(re.findall(r'option\("([a-z0-9_]+)"', open(os.path.join(csrc, fn)).read()))
-    names.discard("name")                      # the usage example in kd_common.h
+            names |= set(re.findall(r"\bopt(?:_or)?\(KD_OPT_([a-z0-9_]+)", open(os.path.join(csrc, fn)).read()))
     return names
+
+
+def package_options():
+    """Every option name the Python package reads through ``kd_get_option``."""
+    names = set()
+    for root, _, files in os.walk(PKG):
+        for fn in files:
+            if fn.endswith(".py"):
+                names |= set(re.findall(r'kd_get_option\(b"([a-z0-9_]+)"', open(os.path.join(root, fn)).read()))
+    return names
+
+
+def table_options():
+    """The rows of include/kdiff_options.def: name -> (default as written, doc text).  Every line that begins with KD_OPTION must parse."""
+    rows = {}
+    for line in open(os.path.join(os.path.dirname(PKG), "include", "kdiff_options.def")):
+        if line.startswith("KD_OPTION"):
+            name, dflt, doc = re.fullmatch(r'KD_OPTION\(([a-z0-9_]+), ([A-Z_]+|-?\d+), "(.*)"\)\n', line).groups()
+            assert name not in rows, name
+            rows[name] = (dflt, doc)
+    return rows
 
 
 def state_dict_shapes(cfg):

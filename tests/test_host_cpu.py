@@ -158,22 +158,42 @@ def test_schedule_rows_are_recognised_by_storage_and_version(KD):
 
 
 def test_every_option_name_used_in_the_sources_is_registered():
-    """kd_set_option refuses unknown names; every name the kernels' dispatch code reads (option("name", default)) and every name
-    the Python layer maps an environment variable to must therefore be in the library's table (checked in a child process: a set
-    option overrides the call sites' defaults for the rest of the process)."""
-    from tests.helpers import source_options
+    """kd_set_option refuses unknown names; every name the kernels' dispatch code reads (opt(KD_OPT_name)) must therefore be settable.
+    include/kdiff_options.def is the one table: its rows are exactly the names that are read, in csrc/ or through kd_get_option in the
+    package, every row says what it selects, and the library starts every option at the row's default, takes a value and goes back
+    (checked in a child process: a set option holds for the rest of the process)."""
+    from tests.helpers import package_options, source_options, table_options
     names = source_options()
     assert {"code_warm", "patch_fast", "ffn_fused", "wstat", "astat"} <= names
+    table = table_options()
+    assert package_options() == {"mx8_min_rows"}
+    assert set(table) == names | package_options(), sorted(set(table) ^ (names | package_options()))          # no dead row, no unread one
+    assert all(doc.strip() for _, doc in table.values())
+    # the two defaults that are no literals: the sentinel comes back as itself; the code warm-up is 8 workgroups or, with a toolchain it
+    # was not validated on, off (kd_common.h)
+    int_min = -2 ** 31
+    symbolic = {"KD_OPT_AUTO": [int_min], "KD_CODE_WARM_DEFAULT": [8, 0]}
+    assert {n for n, (d, _) in table.items() if d in symbolic} == {"ffn_x3_min_panels_256", "code_warm"}
+    kd_common = open(os.path.join(REPO, "k-diffusion_amd", "csrc", "kd_common.h")).read()
+    assert sorted(int(v) for v in re.findall(r"constexpr int KD_CODE_WARM_DEFAULT = (\d+);", kd_common)) == [0, 8]
+    assert "constexpr int KD_OPT_AUTO = INT_MIN;" in kd_common
+    defaults = {n: symbolic.get(d) or [int(d)] for n, (d, _) in table.items()}
     code = (
         "import sys; sys.path.insert(0, %r)\n"
         "import k_diffusion_amd as K\n"
         "lib = K._native.lib()\n"
-        "names = %r + [v[0] for v in K._native._ENV_OPTIONS.values()]\n"
-        "bad = [n for n in names if lib.kd_set_option(n.encode(), 1) != 0]\n"
+        "bad = [n for n in %r if lib.kd_set_option(n.encode(), 1) != 0 or lib.kd_set_option(n.encode(), %d) != 0]\n"
         "assert not bad, bad\n"
         "assert lib.kd_set_option(b'no_such_option', 1) == -1\n"
-    ) % (REPO, sorted(names))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+        "for n, want in %r.items():\n"
+        "    b = n.encode()\n"
+        "    d = lib.kd_get_option(b, %d)\n"
+        "    assert d in want and lib.kd_get_option(b, 5) == 5, (n, d, want)\n"
+        "    assert lib.kd_set_option(b, 7) == 0 and lib.kd_get_option(b, %d) == 7 and lib.kd_get_option(b, 5) == 7, n\n"
+        "    assert lib.kd_set_option(b, %d) == 0 and lib.kd_get_option(b, %d) == d and lib.kd_get_option(b, 5) == 5, n\n"
+    ) % (REPO, sorted(names), int_min, defaults, int_min, int_min, int_min, int_min)
+    env = {k: v for k, v in os.environ.items() if k != "KDIFF_OPTIONS"}
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env)
     assert out.returncode == 0, out.stderr
 
 
@@ -507,7 +527,7 @@ def test_two_rank_gather_over_gloo(KD, tmp_path):
 
 
 def test_option_sync_is_incremental():
-    """KDIFF_* / KDIFF_OPTIONS -> kd_set_option (round-2 advisor): only what changed is re-applied, an entry that disappears from
+    """KDIFF_OPTIONS -> kd_set_option (round-2 advisor): only what changed is re-applied, an entry that disappears from
     KDIFF_OPTIONS goes back to the built-in default, and a value set through set_option survives changes of OTHER variables.
     Runs in a child process: options are process-global."""
     code = (

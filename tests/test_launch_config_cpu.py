@@ -1,4 +1,4 @@
-"""Completeness of tests/test_launch_config_gpu.py, without a GPU: every ``option("name", ...)`` the dispatch code reads is forced by a row of
+"""Completeness of tests/test_launch_config_gpu.py, without a GPU: every option the dispatch code reads (``opt(KD_OPT_name)``) is forced by a row of
 that file's tables, set around a kernel launch by a named existing GPU test, or exempt because it selects no arithmetic path -- an option added
 later without a row fails here.  Also: the rows name registered options only, the `` cfg=`` matcher refuses the right kernel under another
 configuration (fake ops on the CPU, as tests/test_guard_cpu.py does for the guard protocol), and the switches that act through a

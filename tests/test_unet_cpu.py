@@ -151,5 +151,5 @@ def test_signatures_and_header_agree_for_the_new_entry_points(KD):
     # the new kernels read no library option
     csrc = os.path.join(REPO, "k-diffusion_amd", "csrc")
     for fn in ("conv_x3.hip", "unet_f32.hip"):
-        assert not re.findall(r'option\("', open(os.path.join(csrc, fn)).read()), fn
+        assert not re.findall(r"\bopt(?:_or)?\(|\bcode_warm\(\)", open(os.path.join(csrc, fn)).read()), fn
     assert source_options()
