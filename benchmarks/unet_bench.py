@@ -8,6 +8,8 @@ forward on the device (torch's conv / group-norm / SDPA kernels, depthwise resam
 
 ``--profile`` instead runs 3 warm-up + 5 HIP forwards of ONE model and nothing else, for a kernel trace of its own:
     rocprofv3 --kernel-trace --stats -d <dir> -- python benchmarks/unet_bench.py --profile cifar
+``--dual`` instead times the dual (primal + tangent) pass ``forward_jvp`` of ``log_likelihood`` at batch B against the forward at batch B and
+the forward at batch 2 B (the dual pass stacks the tangent behind the primal: 2 B samples in every buffer), same warm-up and sampling.
 Prints one JSON line per model.
 """
 import argparse
@@ -56,6 +58,7 @@ def main():
     ap.add_argument("--profile", choices=sorted(MODELS))
     ap.add_argument("--models", nargs="*", default=["cifar", "mnist"])
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--dual", action="store_true")
     args = ap.parse_args()
     import k_diffusion_amd as K
     from tests import unet_ref as ur
@@ -79,6 +82,23 @@ def main():
                 for _ in range(8):
                     hip()
                 torch.cuda.synchronize()
+                continue
+            if args.dual:
+                v = (torch.randint(0, 2, x.shape, generator=g).float() * 2 - 1).to(dev)
+                x2, sigma2, aug2 = (torch.cat([t, t]) for t in (x, sigma, aug))
+                sides = {"forward_ms": hip, "forward_2b_ms": lambda: model(x2, sigma2, aug_cond=aug2),
+                         "dual_ms": lambda: model.forward_jvp(x, sigma, v, aug_cond=aug)}
+                for _ in range(10):
+                    for fn in sides.values():
+                        fn()
+                torch.cuda.synchronize()
+                times = {k: [] for k in sides}
+                for _ in range(7):
+                    for k, fn in sides.items():
+                        times[k].append(timed(fn))
+                line = {"model": name, "batch": B, **{k: [statistics.median(t), min(t), max(t)] for k, t in times.items()},
+                        "dual_launches": len(model.inner_model._plan(B, H, W, x.device, dual=True).calls) + 8}
+                print(json.dumps(line), flush=True)
                 continue
             sd_dev = ur.prepare(sd, torch.float32, dev)
             ref = lambda: ur.forward(sd_dev, x, sigma, aug_cond=aug, dtype=torch.float32, device=dev, grouped_resample=True, prepared=True)

@@ -640,7 +640,7 @@ int kd_mt_lerp_f32(const KdMtTensor* table, const int* chunks, int n_chunks, dou
 int kd_sigma_density_f32(int kind, const void* u, int u_f64, const void* normal, void* out, int out_f64, long long n, int row_len, int group,
                          int groups, const double* params, void* stream);
 
-/* ---- image_v1 U-Net (k_diffusion/models/image_v1.py), forward only (csrc/conv_x3.hip, csrc/unet_f32.hip) ----
+/* ---- image_v1 U-Net (k_diffusion/models/image_v1.py), forward and dual (forward-mode JVP) pass (csrc/conv_x3.hip, csrc/unet_f32.hip) ----
  * Activations are fp32 NHWC, token-major [batch * H * W, C]; every `ld*` is a row stride in floats (>= the row's channels, a multiple of 4),
  * so an operand may be one column range of a wider buffer (the halves of a skip concatenation).  Rows are 16-byte aligned.  The kernels read
  * no library option, use no atomics, and give the same bits on every run.
@@ -654,6 +654,15 @@ int kd_sigma_density_f32(int kind, const void* u, int u_f64, const void* normal,
  *                     mean_hi + mean_lo is the fp64 mean, rstd = 1 / sqrt(biased variance + eps) (F.group_norm), sums in fp64.
  * kd_adagn_apply_f32  y = (x - mean) * rstd * (1 + w_b) + b_b with w_b = wb[b * wb_stride + c], b_b = wb[b * wb_stride + chan + c] (the two
  *                     chunks of AdaGN's mapper output), then the exact (erf) GELU if `gelu`.  y may be x.
+ * kd_conv2d_x3_stacked   kd_conv2d_x3 on a batch whose samples b >= bias_batch get no bias (0 <= bias_batch <= batch): the dual pass stacks
+ *                     the tangent behind the primal as samples batch / 2 .. batch - 1, and the tangent of conv(x) + bias has no bias.  Same
+ *                     kernel and accumulation order: a sample's output has the bits kd_conv2d_x3 gives it with or without the bias.
+ * kd_groupnorm_stats_jvp_f32   stats as kd_groupnorm_stats_f32 writes them (same bits) and jstats [batch, groups, 4] = {mean_dot, rstd_dot, 0,
+ *                     0}, their tangents along x_dot (row stride ldxd): mean_dot = sum x_dot / n, rstd_dot = -rstd^3 sum (x - mean) x_dot / n, x
+ *                     centred with the fp64 mean, sums in fp64 in a fixed order.  Groups of a multiple of 4 channels.
+ * kd_adagn_apply_jvp_f32   y as kd_adagn_apply_f32 (same bits) and its tangent with the conditioning held fixed: xh_dot = (x_dot - mean_dot) *
+ *                     rstd + (x - mean) * rstd_dot, pre_dot = xh_dot * (1 + w_b), y_dot = pre_dot, or with `gelu` pre_dot * (Phi(pre) + pre *
+ *                     phi(pre)) (exact erf form).  y may be x together with y_dot being x_dot.
  * kd_down2_f32 / kd_up2_f32   Downsample2d / Upsample2d with the 'linear' kernel and 'reflect' padding: [H, W] -> [H / 2, W / 2] (H, W even) and
  *                     [H, W] -> [2 H, 2 W]; H, W >= 2.  y must not overlap x.
  * kd_unet_in_f32      y[pixel][n] = bias[n] + sum_k w[n][k] * img[b][k][pixel] * c_in(b) for an NCHW image of c_img channels; c_in(b) =
@@ -665,9 +674,15 @@ int kd_sigma_density_f32(int kind, const void* u, int u_f64, const void* normal,
 int kd_pack_conv_x3(const float* w, void* out, int c_out, int c_in, int ks, void* stream);
 int kd_conv2d_x3(const float* x, int ldx, const void* wp, const float* bias, const float* res, int ldr, float* y, int ldy, int batch, int H, int W,
                  int c_in, int c_out, int ks, void* stream);
+int kd_conv2d_x3_stacked(const float* x, int ldx, const void* wp, const float* bias, const float* res, int ldr, float* y, int ldy, int batch, int H,
+                         int W, int c_in, int c_out, int ks, int bias_batch, void* stream);
 int kd_groupnorm_stats_f32(const float* x, int ldx, float* stats, int batch, int hw, int chan, int groups, float eps, void* stream);
+int kd_groupnorm_stats_jvp_f32(const float* x, int ldx, const float* x_dot, int ldxd, float* stats, float* jstats, int batch, int hw, int chan,
+                               int groups, float eps, void* stream);
 int kd_adagn_apply_f32(const float* x, int ldx, const float* stats, const float* wb, int wb_stride, float* y, int ldy, int batch, int hw, int chan,
                        int groups, int gelu, void* stream);
+int kd_adagn_apply_jvp_f32(const float* x, int ldx, const float* x_dot, int ldxd, const float* stats, const float* jstats, const float* wb,
+                           int wb_stride, float* y, int ldy, float* y_dot, int ldyd, int batch, int hw, int chan, int groups, int gelu, void* stream);
 int kd_down2_f32(const float* x, int ldx, float* y, int ldy, int batch, int H, int W, int chan, void* stream);
 int kd_up2_f32(const float* x, int ldx, float* y, int ldy, int batch, int H, int W, int chan, void* stream);
 int kd_unet_in_f32(const float* img, const float* w, const float* bias, const float* sigma, float sigma_data, float* y, int ldy, int batch, int hw,

@@ -182,7 +182,10 @@ SIGNATURES = {
     "kd_class_dropout_i64": [_vp, _vp, _f, _i, _vp, _i, _vp],
     "kd_pack_conv_x3": [_vp, _vp, _i, _i, _i, _vp],
     "kd_conv2d_x3": [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "kd_conv2d_x3_stacked": [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "kd_groupnorm_stats_f32": [_vp, _i, _vp, _i, _i, _i, _i, _f, _vp],
+    "kd_groupnorm_stats_jvp_f32": [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp],
+    "kd_adagn_apply_jvp_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "kd_adagn_apply_f32": [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "kd_down2_f32": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "kd_up2_f32": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],

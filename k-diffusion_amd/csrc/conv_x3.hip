@@ -16,6 +16,9 @@
 // 16 pixels (r & 3) + 8 (r >> 2) + 4 (lane >> 5): every accumulator register is stored as two 128-byte row segments.  The epilogue adds the
 // bias and a residual (with its own row stride) and writes through the output's row stride -- the two halves of a skip concatenation are
 // column ranges of one buffer.  No atomics: the accumulation order is fixed, a second run gives the same bits.
+//
+// kd_conv2d_x3_stacked is the same kernel for the dual pass of log_likelihood, whose batch is [primal | tangent]: only the samples below
+// bias_batch get the bias.  A workgroup's sample index decides it, so an output's accumulation order -- and its bits -- are kd_conv2d_x3's.
 #include "x3_common.h"
 
 namespace kd {
@@ -39,6 +42,7 @@ struct ConvP {
   int ldx, ldr, ldy;
   int H, W, c_in, c_out;
   int ty_n, tx_n, n_tiles;
+  int bias_batch;                 // samples b < bias_batch get the bias (a stacked [primal | tangent] batch: the tangent of conv(x) + bias has none)
 };
 
 __global__ __launch_bounds__(256) void pack_conv_kernel(const float* __restrict__ w, u16* __restrict__ out, int c_out, int c_in, int taps) {
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(const ConvP p) {
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int n = n0 + (wn * NB + nb) * 32 + r;
-    const float bv = p.bias ? p.bias[n] : 0.f;
+    const float bv = (p.bias && b < p.bias_batch) ? p.bias[n] : 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int po = 32 * wm + mfma32_row(i, lane);
@@ -170,15 +174,16 @@ extern "C" int kd_pack_conv_x3(const float* w, void* out, int c_out, int c_in, i
   return check_launch("kd_pack_conv_x3");
 }
 
-extern "C" int kd_conv2d_x3(const float* x, int ldx, const void* wp, const float* bias, const float* res, int ldr, float* y, int ldy,
-                            int batch, int H, int W, int c_in, int c_out, int ks, void* stream) {
+// bias_batch: the samples that get the bias (kd_conv2d_x3: all of them)
+static int conv2d_x3(const float* x, int ldx, const void* wp, const float* bias, const float* res, int ldr, float* y, int ldy, int batch, int H, int W,
+                     int c_in, int c_out, int ks, int bias_batch, void* stream) {
   if (!x || !wp || !y || batch <= 0 || H <= 0 || W <= 0) return fail(KD_EINVAL, "kd_conv2d_x3: bad arguments");
   if (ks != 1 && ks != 3) return fail(KD_EINVAL, "kd_conv2d_x3: kernel size %d (1 or 3)", ks);
   if (c_in <= 0 || c_out <= 0 || (c_in % 64) || (c_out % 64))
     return fail(KD_EINVAL, "kd_conv2d_x3: c_in = %d and c_out = %d must be multiples of 64", c_in, c_out);
   if (ldx < c_in || (ldx & 3) || ldy < c_out || (res && ldr < c_out)) return fail(KD_EINVAL, "kd_conv2d_x3: a row stride is shorter than its row (or ldx is no multiple of 4)");
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wp)) & 15) return fail(KD_EINVAL, "kd_conv2d_x3: x and the packed weight must be 16-byte aligned");
-  ConvP p{x, (const u16*)wp, bias, res, y, ldx, ldr, ldy, H, W, c_in, c_out, (H + PATCH - 1) / PATCH, (W + PATCH - 1) / PATCH, 0};
+  ConvP p{x, (const u16*)wp, bias, res, y, ldx, ldr, ldy, H, W, c_in, c_out, (H + PATCH - 1) / PATCH, (W + PATCH - 1) / PATCH, 0, bias_batch};
   const int nb = (c_out % 128) ? 1 : 2;
   p.n_tiles = c_out / (64 * nb);
   const long n_wg = (long)batch * p.ty_n * p.tx_n * p.n_tiles;
@@ -189,4 +194,15 @@ extern "C" int kd_conv2d_x3(const float* x, int ldx, const void* wp, const float
   LaunchScope prof(nm, 2.0 * m * c_out * ks * ks * c_in, 4.0 * m * (c_in + c_out * (res ? 2 : 1)) + 4.0 * ks * ks * c_in * c_out, s);
   if (ks == 3) return nb == 2 ? launch_conv<3, 2>(p, n_wg, s) : launch_conv<3, 1>(p, n_wg, s);
   return nb == 2 ? launch_conv<1, 2>(p, n_wg, s) : launch_conv<1, 1>(p, n_wg, s);
+}
+
+extern "C" int kd_conv2d_x3(const float* x, int ldx, const void* wp, const float* bias, const float* res, int ldr, float* y, int ldy,
+                            int batch, int H, int W, int c_in, int c_out, int ks, void* stream) {
+  return conv2d_x3(x, ldx, wp, bias, res, ldr, y, ldy, batch, H, W, c_in, c_out, ks, batch, stream);
+}
+
+extern "C" int kd_conv2d_x3_stacked(const float* x, int ldx, const void* wp, const float* bias, const float* res, int ldr, float* y, int ldy,
+                                    int batch, int H, int W, int c_in, int c_out, int ks, int bias_batch, void* stream) {
+  if (bias_batch < 0 || bias_batch > batch) return fail(KD_EINVAL, "kd_conv2d_x3_stacked: bias_batch = %d outside 0 .. batch = %d", bias_batch, batch);
+  return conv2d_x3(x, ldx, wp, bias, res, ldr, y, ldy, batch, H, W, c_in, c_out, ks, bias_batch, stream);
 }

@@ -5,6 +5,8 @@
 //                           (C / G channels x H W), accumulated in fp64 in a fixed order (a large mean does not cancel the variance)
 //   kd_adagn_apply_f32      AdaGN (layers.py:172-175): y = (x - mean) rstd (1 + w_b) + b_b, then optionally the exact (erf) GELU that follows it
 //                           in ResConvBlock (image_v1.py:20,24)
+//   kd_groupnorm_stats_jvp_f32 / kd_adagn_apply_jvp_f32   the same two with their tangents along x_dot (the dual pass of log_likelihood): the
+//                           statistics' tangents {mean_dot, rstd_dot} from a second fp64 pass, then y and y_dot in one streaming pass
 //   kd_down2_f32 / kd_up2_f32   Downsample2d / Upsample2d (layers.py:251-280) for the 'linear' kernel [1, 3, 3, 1] / 8 and 'reflect' padding:
 //                           depthwise and separable, so the stride-2 conv is 4 x 4 taps of k (x) k and the transposed conv is, per axis,
 //                           out[2m] = 3/4 x[m] + 1/4 x[m-1], out[2m+1] = 3/4 x[m] + 1/4 x[m+1] with indices -1 -> 1 and n -> n - 2
@@ -24,22 +26,11 @@ namespace {
 // ---- group norm -----------------------------------------------------------------------------------------------------------------------------
 // one workgroup per (sample, group); stats[(b G + g) 4 ..] = {mean_hi, mean_lo, rstd, 0}: the fp64 mean as two fp32 (x - hi - lo loses nothing
 // to the mean's rounding when the mean is large against the spread)
-__global__ __launch_bounds__(256) void groupnorm_stats_kernel(const float* __restrict__ x, int ldx, float* __restrict__ stats, int hw, int cpg,
-                                                              int groups, float eps) {
-  __shared__ double sh[2][256];
-  const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
-  const float* base = x + (size_t)b * hw * ldx + (size_t)g * cpg;
-  const long n = (long)hw * cpg;
-  double s = 0.0, ss = 0.0;
-  for (long e = threadIdx.x; e < n; e += 256) {
-    const long pix = e / cpg;
-    const int ch = (int)(e - pix * cpg);
-    const double v = (double)base[pix * ldx + ch];
-    s += v;
-    ss += v * v;
-  }
-  sh[0][threadIdx.x] = s;
-  sh[1][threadIdx.x] = ss;
+// The workgroup's sums of two fp64 terms in a fixed order: a binary tree over the 256 threads' partial sums; every thread gets both totals.
+__device__ __forceinline__ void block_sum2(double (*sh)[256], double& a, double& b) {
+  __syncthreads();                                             // an earlier reduction's totals have been read
+  sh[0][threadIdx.x] = a;
+  sh[1][threadIdx.x] = b;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
     if ((int)threadIdx.x < o) {
@@ -48,14 +39,77 @@ __global__ __launch_bounds__(256) void groupnorm_stats_kernel(const float* __res
     }
     __syncthreads();
   }
+  a = sh[0][0];
+  b = sh[1][0];
+}
+
+// mean and 1 / sqrt(biased variance + eps) of one (sample, group), both in fp64: the one reduction of the forward statistics and of the
+// dual pass's, so the two write the same bits
+__device__ __forceinline__ void group_moments(const float* __restrict__ base, int ldx, long n, int cpg, float eps, double (*sh)[256], double& mean,
+                                              double& rstd) {
+  double s = 0.0, ss = 0.0;
+  for (long e = threadIdx.x; e < n; e += 256) {
+    const long pix = e / cpg;
+    const int ch = (int)(e - pix * cpg);
+    const double v = (double)base[pix * ldx + ch];
+    s += v;
+    ss += v * v;
+  }
+  block_sum2(sh, s, ss);
+  mean = s / (double)n;
+  rstd = 1.0 / sqrt(fmax(ss / (double)n - mean * mean, 0.0) + (double)eps);
+}
+
+__device__ __forceinline__ void write_stats(float* __restrict__ o, double mean, double rstd) {
+  const float mh = (float)mean;
+  o[0] = mh;
+  o[1] = (float)(mean - (double)mh);
+  o[2] = (float)rstd;
+  o[3] = 0.f;
+}
+
+__global__ __launch_bounds__(256) void groupnorm_stats_kernel(const float* __restrict__ x, int ldx, float* __restrict__ stats, int hw, int cpg,
+                                                              int groups, float eps) {
+  __shared__ double sh[2][256];
+  const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
+  double mean, rstd;
+  group_moments(x + (size_t)b * hw * ldx + (size_t)g * cpg, ldx, (long)hw * cpg, cpg, eps, sh, mean, rstd);
+  if (threadIdx.x == 0) write_stats(stats + 4 * (size_t)blockIdx.x, mean, rstd);
+}
+
+// The statistics and their tangents along x_dot: jstats[(b G + g) 4 ..] = {mean_dot, rstd_dot, 0, 0} with mean_dot = sum x_dot / n and
+// rstd_dot = -rstd^3 sum (x - mean) x_dot / n.  The second pass centres x with the fp64 mean (a large mean does not cancel the covariance) and
+// reads 16 bytes per lane: thread t takes the float4s t + 256 k of the group's (pixel, 4-channel) grid.
+__global__ __launch_bounds__(256) void groupnorm_stats_jvp_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ xd, int ldxd,
+                                                                  float* __restrict__ stats, float* __restrict__ jstats, int hw, int cpg, int groups,
+                                                                  float eps) {
+  __shared__ double sh[2][256];
+  const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
+  const float* base = x + (size_t)b * hw * ldx + (size_t)g * cpg;
+  const float* based = xd + (size_t)b * hw * ldxd + (size_t)g * cpg;
+  const long n = (long)hw * cpg;
+  double mean, rstd;
+  group_moments(base, ldx, n, cpg, eps, sh, mean, rstd);
+  const int cv = cpg >> 2;
+  double sd = 0.0, cov = 0.0;
+  for (long e = threadIdx.x; e < (long)hw * cv; e += 256) {
+    const long pix = e / cv;
+    const int ch = (int)(e - pix * cv) * 4;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(base + pix * ldx + ch);
+    const f32x4 d = *reinterpret_cast<const f32x4*>(based + pix * ldxd + ch);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      sd += (double)d[u];
+      cov += ((double)v[u] - mean) * (double)d[u];
+    }
+  }
+  block_sum2(sh, sd, cov);
   if (threadIdx.x == 0) {
-    const double mean = sh[0][0] / (double)n;
-    const double var = fmax(sh[1][0] / (double)n - mean * mean, 0.0);
-    const float mh = (float)mean;
-    float* o = stats + 4 * (size_t)blockIdx.x;
-    o[0] = mh;
-    o[1] = (float)(mean - (double)mh);
-    o[2] = (float)(1.0 / sqrt(var + (double)eps));
+    write_stats(stats + 4 * (size_t)blockIdx.x, mean, rstd);
+    float* o = jstats + 4 * (size_t)blockIdx.x;
+    o[0] = (float)(sd / (double)n);
+    o[1] = (float)(-(rstd * rstd * rstd) * (cov / (double)n));
+    o[2] = 0.f;
     o[3] = 0.f;
   }
 }
@@ -80,6 +134,45 @@ __global__ __launch_bounds__(256) void adagn_apply_kernel(const float* __restric
       o[u] = GELU ? gelu_erf(a) : a;
     }
     *reinterpret_cast<f32x4*>(y + pix * ldy + c) = o;
+  }
+}
+
+// AdaGN (+ GELU) and its tangent along x_dot, the conditioning (w, b) held fixed.  The primal lines are adagn_apply_kernel's, so y has its
+// bits.  A thread reads its float4 of x and of x_dot before it writes y and y_dot there: y == x with y_dot == x_dot is in place.
+template <bool GELU>
+__global__ __launch_bounds__(256) void adagn_apply_jvp_kernel(const float* x, int ldx, const float* xd, int ldxd, const float* __restrict__ stats,
+                                                              const float* __restrict__ jstats, const float* __restrict__ wb, int wb_stride, float* y,
+                                                              int ldy, float* yd, int ldyd, int hw, int chan, int cpg, long n_vec) {
+  const int cv = chan >> 2, groups = chan / cpg;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_vec; i += (long)gridDim.x * 256) {
+    const long pix = i / cv;
+    const int c = (int)(i - pix * cv) * 4;
+    const int b = (int)(pix / hw);
+    const f32x4 v = *reinterpret_cast<const f32x4*>(x + pix * ldx + c);
+    const f32x4 d = *reinterpret_cast<const f32x4*>(xd + pix * ldxd + c);
+    const float* wrow = wb + (size_t)b * wb_stride;
+    f32x4 o, od;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const size_t sg = 4 * ((size_t)b * groups + (c + u) / cpg);
+      const float* st = stats + sg;
+      const float* js = jstats + sg;
+      const float xc = (v[u] - st[0]) - st[1];
+      const float t = xc * st[2];
+      const float gain = 1.0f + wrow[c + u];
+      const float a = fmaf(t, gain, wrow[chan + c + u]);
+      const float ad = fmaf(d[u] - js[0], st[2], xc * js[1]) * gain;
+      if (GELU) {
+        const float cdf = 0.5f * (1.0f + erff(a * 0.70710678118654752440f));
+        o[u] = gelu_erf(a);
+        od[u] = ad * (cdf + a * (0.39894228040143267794f * expf(-0.5f * a * a)));
+      } else {
+        o[u] = a;
+        od[u] = ad;
+      }
+    }
+    *reinterpret_cast<f32x4*>(y + pix * ldy + c) = o;
+    *reinterpret_cast<f32x4*>(yd + pix * ldyd + c) = od;
   }
 }
 
@@ -242,6 +335,41 @@ extern "C" int kd_adagn_apply_f32(const float* x, int ldx, const float* stats, c
   if (gelu) launch<adagn_apply_kernel<true>>(dim3(blocks_for(n_vec, 256)), dim3(256), 0, s, x, ldx, stats, wb, wb_stride, y, ldy, hw, chan, chan / groups, n_vec);
   else launch<adagn_apply_kernel<false>>(dim3(blocks_for(n_vec, 256)), dim3(256), 0, s, x, ldx, stats, wb, wb_stride, y, ldy, hw, chan, chan / groups, n_vec);
   return check_launch("kd_adagn_apply_f32");
+}
+
+extern "C" int kd_groupnorm_stats_jvp_f32(const float* x, int ldx, const float* x_dot, int ldxd, float* stats, float* jstats, int batch, int hw,
+                                          int chan, int groups, float eps, void* stream) {
+  if (!x || !x_dot || !stats || !jstats || batch <= 0 || hw <= 0 || chan <= 0 || groups <= 0)
+    return fail(KD_EINVAL, "kd_groupnorm_stats_jvp_f32: bad arguments");
+  if ((chan % groups) || ((chan / groups) & 3))
+    return fail(KD_EINVAL, "kd_groupnorm_stats_jvp_f32: %d channels in %d groups: groups of a multiple of 4 channels", chan, groups);
+  if (ldx < chan || ldxd < chan || (ldx & 3) || (ldxd & 3) || misaligned(x) || misaligned(x_dot))
+    return fail(KD_EINVAL, "kd_groupnorm_stats_jvp_f32: row strides must cover the %d channels and keep rows 16-byte aligned", chan);
+  if ((long)batch * groups > 0x7FFFFFFFl) return fail(KD_EINVAL, "kd_groupnorm_stats_jvp_f32: too many (sample, group) pairs");
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope prof("groupnorm_stats_jvp_f32", 0, 12.0 * batch * hw * chan, s);
+  launch<groupnorm_stats_jvp_kernel>(dim3((unsigned)(batch * groups)), dim3(256), 0, s, x, ldx, x_dot, ldxd, stats, jstats, hw, chan / groups, groups,
+                                     eps);
+  return check_launch("kd_groupnorm_stats_jvp_f32");
+}
+
+extern "C" int kd_adagn_apply_jvp_f32(const float* x, int ldx, const float* x_dot, int ldxd, const float* stats, const float* jstats, const float* wb,
+                                      int wb_stride, float* y, int ldy, float* y_dot, int ldyd, int batch, int hw, int chan, int groups, int gelu,
+                                      void* stream) {
+  if (!x || !x_dot || !stats || !jstats || !wb || !y || !y_dot || batch <= 0 || hw <= 0 || chan <= 0 || groups <= 0)
+    return fail(KD_EINVAL, "kd_adagn_apply_jvp_f32: bad arguments");
+  if ((chan % groups) || (chan & 3)) return fail(KD_EINVAL, "kd_adagn_apply_jvp_f32: %d channels: a multiple of 4 and of the %d groups", chan, groups);
+  if (ldx < chan || ldxd < chan || ldy < chan || ldyd < chan || ((ldx | ldxd | ldy | ldyd) & 3) || wb_stride < 2 * chan || misaligned(x) ||
+      misaligned(x_dot) || misaligned(y) || misaligned(y_dot))
+    return fail(KD_EINVAL, "kd_adagn_apply_jvp_f32: row strides must cover the channels and keep rows 16-byte aligned; wb rows hold 2 C values");
+  if (y == x_dot || y_dot == x || y == y_dot) return fail(KD_EINVAL, "kd_adagn_apply_jvp_f32: in place means y == x and y_dot == x_dot, not crossed");
+  const long n_vec = (long)batch * hw * (chan >> 2);
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope prof("adagn_apply_jvp_f32", 0, 16.0 * batch * hw * chan, s);
+  const dim3 grid(blocks_for(n_vec, 256));
+  if (gelu) launch<adagn_apply_jvp_kernel<true>>(grid, dim3(256), 0, s, x, ldx, x_dot, ldxd, stats, jstats, wb, wb_stride, y, ldy, y_dot, ldyd, hw, chan, chan / groups, n_vec);
+  else launch<adagn_apply_jvp_kernel<false>>(grid, dim3(256), 0, s, x, ldx, x_dot, ldxd, stats, jstats, wb, wb_stride, y, ldy, y_dot, ldyd, hw, chan, chan / groups, n_vec);
+  return check_launch("kd_adagn_apply_jvp_f32");
 }
 
 static int resample_check(const char* what, const float* x, int ldx, float* y, int ldy, int batch, int H, int W, int chan, bool down) {

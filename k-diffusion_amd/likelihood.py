@@ -8,7 +8,8 @@ probe ``v = randint_like(x, 2) * 2 - 1`` drawn like the reference (same global R
 sigma_max^2) + ll(sigma_max).
 
 Divergence term.  The reference takes v . (v^T J) with autograd through the model.  The HIP path takes v^T (J v) forward instead: one
-dual pass ``forward_jvp(x, sigma, v)`` per evaluation (``layers.Denoiser.forward_jvp``, models/jvp.py), then kd_ll_div_f32.  A model
+dual pass ``forward_jvp(x, sigma, v)`` per evaluation (``layers.Denoiser.forward_jvp``; models/jvp.py for the hourglass transformer,
+``models.image_v1.ImageDenoiserModelV1.forward_jvp`` for the U-Net), then kd_ll_div_f32.  A model
 without ``forward_jvp`` that is NOT an object of this package -- a user's own differentiable torch callable -- runs the reference's
 autograd formulation verbatim; an object of this package without a JVP rule (the ``external`` wrappers, ``sampling.make_cfg_model_fn``)
 raises NotImplementedError.  Either way the solver's vector arithmetic is HIP (kd_rk_combine_f32 / kd_rk_error_f32): ROCm tensors only.

@@ -11,9 +11,13 @@ kernel launches over fp32 NHWC token buffers ``[B H W, C]``, built once per (bat
 * ``torch.cat([x, skip], 1)`` is two column ranges of one buffer which their producers write through the row stride;
 * self-attention is ``ops.attn_global`` on the qkv convolution's output as it stands; SDPA's scale 1 / 8 (heads of 64) is folded into the q
   rows of the packed qkv weight and bias, which is exact;
-* with ``forward_preconditioned`` the Karras scalings ride in ``proj_in`` / ``proj_out``.
+* with ``forward_preconditioned`` the Karras scalings ride in ``proj_in`` / ``proj_out``;
+* ``forward_jvp`` (the dual pass of ``likelihood.log_likelihood``) is the same walk over buffers of 2 B samples, the tangent stacked behind the
+  primal: the linear kernels run once over both, a stacked convolution gives its bias to the primal samples only
+  (``kd_conv2d_x3_stacked``), AdaGN has dual kernels (``kd_groupnorm_stats_jvp_f32``, ``kd_adagn_apply_jvp_f32``) and attention is
+  ``ops.attn_global_jvp``.  Its primal output has the forward's bits.
 
-Scope: the forward pass in fp32-grade (split-bf16x3) arithmetic whatever ``KDIFF_GEMM`` says, ``patch_size == 1``, ``skip_stages == 0``, no
+Scope: the forward pass and its forward-mode derivative in fp32-grade (split-bf16x3) arithmetic whatever ``KDIFF_GEMM`` says, ``patch_size == 1``, ``skip_stages == 0``, no
 variance output, no cross attention, no ``unet_cond``, channels that are multiples of 64, even H and W at every downsample.  Anything else is
 refused in the constructor; training (grad mode with something that requires grad) raises NotImplementedError.
 """
@@ -119,9 +123,14 @@ class _MappingNet(nn.Sequential):
 
 
 class _Plan:
-    """Buffers and the fixed launch list of one (batch, H, W): ``head`` / ``tail`` take the call's own tensors, ``calls`` is everything between."""
+    """Buffers and the fixed launch list of one (batch, H, W): ``head`` / ``tail`` take the call's own tensors, ``calls`` is everything between.
 
-    def __init__(self, model, B, H, W, device):
+    ``dual``: the list of the dual (primal + tangent) pass.  Every activation buffer holds ``S = 2 B`` samples, the primal's rows first and the
+    tangent's after (``lo`` / ``hi``), and the linear kernels -- convolutions, resampling -- run once over all of them: they treat samples
+    independently.  Only the bias (primal samples alone), AdaGN (its dual kernels) and attention (``ops.attn_global_jvp`` on the two halves)
+    tell the halves apart."""
+
+    def __init__(self, model, B, H, W, device, dual=False):
         n, ch = len(model.depths), model.channels
         sizes = [(H >> i, W >> i) for i in range(n)]
         for i in range(n - 1):
@@ -130,6 +139,14 @@ class _Plan:
         f32 = dict(device=device, dtype=torch.float32)
         feats = model.feats_in
         self.B, self.calls, pool = B, [], {}
+        S = 2 * B if dual else B                                        # samples in every activation buffer
+        bias_batch = B if dual else None
+
+        def lo(t):
+            return t[:t.shape[0] // 2]
+
+        def hi(t):
+            return t[t.shape[0] // 2:]
         self.ff, self.e, self.h1, self.h2 = (torch.empty(B, feats, **f32) for _ in range(4))
 
         def alloc(rows, cols):
@@ -154,11 +171,17 @@ class _Plan:
         def adagn(norm, x, out, gelu):
             stats = torch.empty(B, norm.num_groups, 4, **f32)
             wb = self.table[:, offsets[norm]:offsets[norm] + 2 * norm.c_out]
+            if dual:
+                jstats = torch.empty_like(stats)
+                emit(partial(uo.groupnorm_stats_jvp, lo(x), hi(x), B, norm.num_groups, norm.eps, out=stats, out_dot=jstats))
+                emit(partial(uo.adagn_apply_jvp, lo(x), hi(x), stats, jstats, wb, gelu=gelu, out=lo(out), out_dot=hi(out)))
+                return
             emit(partial(uo.groupnorm_stats, x, B, norm.num_groups, norm.eps, out=stats))
             emit(partial(uo.adagn_apply, x, stats, wb, gelu=gelu, out=out))
 
-        def conv(x, weight, hw, bias=None, residual=None, out=None):
-            emit(partial(uo.conv2d, x, weight, B, hw[0], hw[1], bias=bias, residual=residual, out=out, packed=uo.pack_conv(weight)))
+        def conv(x, weight, hw, bias=None, residual=None, out=None, packed=None):
+            emit(partial(uo.conv2d, x, weight, S, hw[0], hw[1], bias=bias, residual=residual, out=out,
+                         packed=uo.pack_conv(weight) if packed is None else packed, bias_batch=None if bias is None else bias_batch))
 
         def res_block(layer, x, y, hw):
             rows = x.shape[0]
@@ -186,10 +209,16 @@ class _Plan:
             wq[:C] *= 0.125
             bq[:C] *= 0.125
             qkv = alloc(rows, 3 * C)
-            emit(partial(uo.conv2d, t1, wq, B, hw[0], hw[1], bias=bq, out=qkv, packed=uo.pack_conv(wq, cache=False)))
+            conv(t1, wq, hw, bias=bq, out=qkv, packed=uo.pack_conv(wq, cache=False))
             free(t1)
             a = alloc(rows, C)
-            emit(partial(ops.attn_global, qkv.view(B, hw[0] * hw[1], 3 * C), layer.n_head, out=a.view(B, hw[0] * hw[1], C)))
+            q3, a3 = qkv.view(S, hw[0] * hw[1], 3 * C), a.view(S, hw[0] * hw[1], C)
+            if dual:
+                # the tangent from the fp32 dual kernel; its primal output is then overwritten by the forward's own kernel, so that the dual
+                # pass's primal has the forward's bits
+                emit(partial(ops.attn_global_jvp, q3[:B], q3[B:], layer.n_head, out=a3[:B], out_dot=a3[B:]))
+                q3, a3 = q3[:B], a3[:B]
+            emit(partial(ops.attn_global, q3, layer.n_head, out=a3))
             free(qkv)
             conv(a, layer.out_proj.weight, hw, bias=layer.out_proj.bias, residual=x, out=y)
             free(a)
@@ -197,14 +226,14 @@ class _Plan:
         def run_layer(layer, x, y, hw):
             (res_block if isinstance(layer, _ResConvBlock) else attention)(layer, x, y, hw)
 
-        self.t0 = cur = alloc(B * H * W, ch[0])
+        self.t0 = cur = alloc(S * H * W, ch[0])
         cats = [None] * n
         for i, block in enumerate(model.u_net.d_blocks):
             hw = sizes[i]
-            rows = B * hw[0] * hw[1]
+            rows = S * hw[0] * hw[1]
             if i > 0:
                 nxt = alloc(rows, ch[i - 1])
-                emit(partial(uo.down2, cur, B, sizes[i - 1][0], sizes[i - 1][1], out=nxt))
+                emit(partial(uo.down2, cur, S, sizes[i - 1][0], sizes[i - 1][1], out=nxt))
                 cur = nxt
             layers = list(block)[1:]
             for j, layer in enumerate(layers):
@@ -219,7 +248,7 @@ class _Plan:
         for k, block in enumerate(model.u_net.u_blocks):
             i = n - 1 - k
             hw = sizes[i]
-            rows = B * hw[0] * hw[1]
+            rows = S * hw[0] * hw[1]
             if i < n - 1:
                 cur = cats[i]                                           # [upsampled | skip], both halves written by now
             for layer in list(block)[:-1]:
@@ -228,14 +257,15 @@ class _Plan:
                 free(cur)
                 cur = dst
             if i > 0:
-                emit(partial(uo.up2, cur, B, hw[0], hw[1], out=cats[i - 1][:, :ch[i - 1]]))
+                emit(partial(uo.up2, cur, S, hw[0], hw[1], out=cats[i - 1][:, :ch[i - 1]]))
                 free(cur)
         self.last = cur
 
 
 class AugmentWrapperV1(KarrasAugmentWrapper):
     """``KarrasAugmentWrapper`` around the U-Net (config.py:169-170) that also hands ``Denoiser.forward`` the inner model's fused
-    ``forward_preconditioned``, with the same conditioning rule: ``aug_cond`` (zeros [B, 9] when none is given) in front of ``mapping_cond``."""
+    ``forward_preconditioned`` -- and ``Denoiser.forward_jvp`` its ``forward_jvp`` -- with the same conditioning rule: ``aug_cond`` (zeros
+    [B, 9] when none is given) in front of ``mapping_cond``."""
 
     def forward_preconditioned(self, input, sigma, sigma_data, aug_cond=None, mapping_cond=None, **kwargs):
         cond = input.new_zeros([input.shape[0], 9]) if aug_cond is None else aug_cond
@@ -243,10 +273,17 @@ class AugmentWrapperV1(KarrasAugmentWrapper):
             cond = torch.cat([cond, mapping_cond], dim=1)
         return self.inner_model.forward_preconditioned(input, sigma, sigma_data, mapping_cond=cond, **kwargs)
 
+    def forward_jvp(self, input, sigma, tangent, sigma_data=None, aug_cond=None, mapping_cond=None, **kwargs):
+        """The inner model's ``forward_jvp`` under the conditioning rule of ``forward_preconditioned``."""
+        cond = input.new_zeros([input.shape[0], 9]) if aug_cond is None else aug_cond
+        if mapping_cond is not None:
+            cond = torch.cat([cond, mapping_cond], dim=1)
+        return self.inner_model.forward_jvp(input, sigma, tangent, mapping_cond=cond, sigma_data=sigma_data, **kwargs)
+
 
 class ImageDenoiserModelV1(nn.Module):
-    """image_v1.py:89-176 with the reference's constructor signature, attributes, state_dict and ``param_groups``; forward only (see the
-    module docstring for the scope)."""
+    """image_v1.py:89-176 with the reference's constructor signature, attributes, state_dict and ``param_groups``; the forward and its
+    forward-mode derivative, no backward pass (see the module docstring for the scope)."""
 
     def __init__(self, c_in, feats_in, depths, channels, self_attn_depths, cross_attn_depths=None, mapping_cond_dim=0, unet_cond_dim=0,
                  cross_cond_dim=0, dropout_rate=0., patch_size=1, skip_stages=0, has_variance=False):
@@ -292,6 +329,7 @@ class ImageDenoiserModelV1(nn.Module):
         self.u_net = _UNet(d_blocks, reversed(u_blocks))
         self._watch, self._plan_cache, self._fingerprint = weights.WeightWatch(self), weights.PlanCache(), None
         self._plans = self._plan_cache.plans
+        self._dual_cache = weights.PlanCache()         # the dual pass's plans: forward_jvp leaves ``_plans`` and its eviction order alone
 
     def param_groups(self, base_lr=2e-4):
         """image_v1.py:117-133: the weights of ``mapping`` and ``u_net`` decay, everything else does not."""
@@ -322,18 +360,21 @@ class ImageDenoiserModelV1(nn.Module):
         self._watch.bump()
         return out
 
-    def _plan(self, B, H, W, device):
+    def _plan(self, B, H, W, device, dual=False):
         fp = self._weights_fingerprint()
         if fp != self._fingerprint:
             self._plan_cache.drop_all()
+            self._dual_cache.drop_all()
             self._fingerprint = fp
         key = (B, H, W, str(device))
-        return self._plan_cache.get(key) or self._plan_cache.put(key, lambda: _Plan(self, B, H, W, device), MAX_PLANS)
+        cache = self._dual_cache if dual else self._plan_cache
+        return cache.get(key) or cache.put(key, lambda: _Plan(self, B, H, W, device, dual), MAX_PLANS)
 
-    def _run(self, input, sigma, mapping_cond, sigma_data, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False):
+    def _run(self, input, sigma, mapping_cond, sigma_data, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False,
+             tangent=None, dual=False):
         if unet_cond is not None or cross_cond is not None or cross_cond_padding is not None or return_variance:
             raise ValueError("image_v1: unet_cond, cross_cond and return_variance are not supported on the HIP path")
-        tensors = [t for t in (input, sigma, mapping_cond) if isinstance(t, torch.Tensor)]
+        tensors = [t for t in (input, sigma, mapping_cond, tangent) if isinstance(t, torch.Tensor)]
         if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("image_v1: sampling only -- the U-Net has no backward pass on the HIP path; call it under torch.no_grad() "
                                       "(and model.requires_grad_(False))")
@@ -341,6 +382,8 @@ class ImageDenoiserModelV1(nn.Module):
             raise NotImplementedError("image_v1: sampling only -- dropout is a training quantity; call model.eval()")
         if not isinstance(input, torch.Tensor) or input.dim() != 4 or input.shape[1] != self.c_in:
             raise ValueError(f"image_v1: input is [B, {self.c_in}, H, W] (got {tuple(getattr(input, 'shape', ()))})")
+        if dual and (not isinstance(tangent, torch.Tensor) or tangent.shape != input.shape):
+            raise ValueError(f"image_v1: tangent has the input's shape {tuple(input.shape)} (got {tuple(getattr(tangent, 'shape', ()))})")
         if not input.is_cuda:
             raise RuntimeError(f"image_v1 runs on the HIP path only: move the model and inputs to a ROCm device (got {input.device}); there is no "
                                f"CPU fallback")
@@ -351,10 +394,15 @@ class ImageDenoiserModelV1(nn.Module):
         has_cond = hasattr(self, "mapping_cond")
         if mapping_cond is not None and not has_cond:
             raise ValueError("image_v1: mapping_cond given, but the model was built with mapping_cond_dim=0")
+        if dual:
+            if tangent.device != input.device:
+                raise RuntimeError(f"image_v1: tangent is on {tangent.device}, input on {input.device}")
+            if tangent.dtype != torch.float32:
+                raise TypeError(f"image_v1: tangent is fp32 like the input (got {tangent.dtype})")
         x = input.contiguous()
         B, _, H, W = x.shape
         sigma = sigma.to(device=x.device, dtype=torch.float32).reshape(-1).expand(B).contiguous()
-        plan = self._plan(B, H, W, x.device)
+        plan = self._plan(B, H, W, x.device, dual)
         e = ops.fourier_sigma(sigma, self.timestep_embed.weight, out=plan.ff)
         if mapping_cond is not None:
             mc = mapping_cond.to(device=x.device, dtype=torch.float32).contiguous()
@@ -365,11 +413,19 @@ class ImageDenoiserModelV1(nn.Module):
         h = uo.cond_mlp(h, self.mapping[2].weight, self.mapping[2].bias, gelu=True, out=plan.h2)
         uo.cond_mlp(h, plan.map_w, plan.map_b, out=plan.table)
         pre = sigma_data is not None
-        uo.unet_in(x, self.proj_in.weight, self.proj_in.bias, sigma if pre else None, sigma_data if pre else 1.0, out=plan.t0)
+        scale = dict(sigma=sigma if pre else None, sigma_data=sigma_data if pre else 1.0)
+        rows = B * H * W
+        t0, last = (plan.t0[:rows], plan.last[:rows]) if dual else (plan.t0, plan.last)
+        uo.unet_in(x, self.proj_in.weight, self.proj_in.bias, out=t0, **scale)
+        if dual:                                       # the tangent of both projections: no bias, x_dot in the image's place
+            x_dot = tangent.contiguous()
+            uo.unet_in(x_dot, self.proj_in.weight, None, out=plan.t0[rows:], **scale)
         for call in plan.calls:
             call()
-        return uo.unet_out(plan.last, self.proj_out.weight, self.proj_out.bias, tuple(x.shape), image=x if pre else None,
-                           sigma=sigma if pre else None, sigma_data=sigma_data if pre else 1.0)
+        out = uo.unet_out(last, self.proj_out.weight, self.proj_out.bias, tuple(x.shape), image=x if pre else None, **scale)
+        if not dual:
+            return out
+        return out, uo.unet_out(plan.last[rows:], self.proj_out.weight, None, tuple(x.shape), image=x_dot if pre else None, **scale)
 
     def forward(self, input, sigma, mapping_cond=None, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False):
         """F(input, sigma): [B, C, H, W] fp32 on a ROCm device -> [B, C, H, W] (image_v1.py:135-157)."""
@@ -379,3 +435,10 @@ class ImageDenoiserModelV1(nn.Module):
         """D(x, sigma) = F(x c_in, sigma) c_out + x c_skip (k_diffusion/layers.py:88-90) with c_in folded into ``proj_in`` and c_out / c_skip
         into ``proj_out``: what ``Denoiser.forward`` calls."""
         return self._run(input, sigma, mapping_cond, float(sigma_data), **kwargs)
+
+    def forward_jvp(self, input, sigma, tangent, mapping_cond=None, sigma_data=None, **kwargs):
+        """(out, out_dot): F(input, sigma) -- or D(input, sigma) with ``sigma_data``, the scalings folded in as in ``forward_preconditioned`` --
+        and its forward-mode derivative along ``tangent``, sigma and the conditioning held fixed: what ``Denoiser.forward_jvp`` and
+        ``likelihood.log_likelihood`` call.  One dual pass over [primal | tangent] buffers (``_Plan``); it builds no autograd graph, and the
+        refusals are the forward's."""
+        return self._run(input, sigma, mapping_cond, None if sigma_data is None else float(sigma_data), tangent=tangent, dual=True, **kwargs)

@@ -622,18 +622,22 @@ def qk_prep_jvp_(qkv, qkv_dot, scale_h, cos_t, sin_t, nh, eps=1e-6):
     return qkv, qkv_dot
 
 
-def _attn_jvp_out(qkv, qkv_dot, nh):
+def _attn_jvp_out(qkv, qkv_dot, nh, out=None, out_dot=None):
     _qkv_dims(qkv, nh)
     if qkv_dot.shape != qkv.shape:
         raise ValueError(f"tangent shape {tuple(qkv_dot.shape)} != primal shape {tuple(qkv.shape)}")
     _chk(qkv, "qkv"), _chk(qkv_dot, "qkv_dot")
-    out = torch.empty(*qkv.shape[:-1], nh * 64, device=qkv.device, dtype=torch.float32)
-    return out, torch.empty_like(out)
+    shape = (*qkv.shape[:-1], nh * 64)
+    out = torch.empty(shape, device=qkv.device, dtype=torch.float32) if out is None else out
+    out_dot = torch.empty(shape, device=qkv.device, dtype=torch.float32) if out_dot is None else out_dot
+    if tuple(_chk(out, "out").shape) != shape or tuple(_chk(out_dot, "out_dot").shape) != shape:
+        raise ValueError(f"out {tuple(out.shape)} and out_dot {tuple(out_dot.shape)} must be {shape}")
+    return out, out_dot
 
 
-def attn_global_jvp(qkv, qkv_dot, nh):
+def attn_global_jvp(qkv, qkv_dot, nh, out=None, out_dot=None):
     """Dense softmax attention (:383, :392) on prepared q, k and its tangent: qkv [B, T..., 3*nh*64] -> (o, o_dot) [B, T..., nh*64]."""
-    out, od = _attn_jvp_out(qkv, qkv_dot, nh)
+    out, od = _attn_jvp_out(qkv, qkv_dot, nh, out, out_dot)
     B = qkv.shape[0]
     T = qkv.numel() // (B * 3 * nh * 64)
     nat.check(nat.lib().kd_attn_global_jvp_f32(_p(qkv), _p(qkv_dot), _p(out), _p(od), B, T, nh, _stream()), "kd_attn_global_jvp_f32")

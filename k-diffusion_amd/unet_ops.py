@@ -48,9 +48,10 @@ def pack_conv(weight, cache=True):
     return _packed.get(weight, None, None, build, cache=cache)
 
 
-def conv2d(x, weight, B, H, W, bias=None, residual=None, out=None, packed=None):
+def conv2d(x, weight, B, H, W, bias=None, residual=None, out=None, packed=None, bias_batch=None):
     """conv2d(x, weight, padding=ks // 2) + bias + residual on tokens x [B*H*W, C_in] -> [B*H*W, C_out] (``kd_conv2d_x3``), ks 1 or 3.
-    ``out`` must not overlap x."""
+    ``out`` must not overlap x.  With ``bias_batch`` only the samples b < bias_batch get the bias (``kd_conv2d_x3_stacked``: a dual pass's
+    batch is [primal | tangent], and the tangent of conv(x) + bias has no bias)."""
     c_out, c_in, ks, _ = weight.shape
     ldx = _rows(x, "x", c_in)
     _tokens(x, B, H, W, "conv2d")
@@ -60,8 +61,11 @@ def conv2d(x, weight, B, H, W, bias=None, residual=None, out=None, packed=None):
     if out.shape[0] != x.shape[0] or (residual is not None and residual.shape[0] != x.shape[0]):
         raise ValueError("conv2d: out and residual have the rows of x")
     packed = pack_conv(weight) if packed is None else packed
-    nat.check(nat.lib().kd_conv2d_x3(_p(x), ldx, _p(packed), _p(None if bias is None else _chk(bias, "bias")), _p(residual), ldr, _p(out), ldy,
-                                     B, H, W, c_in, c_out, ks, _stream()), "kd_conv2d_x3")
+    args = (_p(x), ldx, _p(packed), _p(None if bias is None else _chk(bias, "bias")), _p(residual), ldr, _p(out), ldy, B, H, W, c_in, c_out, ks)
+    if bias_batch is None:
+        nat.check(nat.lib().kd_conv2d_x3(*args, _stream()), "kd_conv2d_x3")
+    else:
+        nat.check(nat.lib().kd_conv2d_x3_stacked(*args, int(bias_batch), _stream()), "kd_conv2d_x3_stacked")
     return out
 
 
@@ -90,6 +94,50 @@ def adagn_apply(x, stats, wb, gelu=False, out=None):
     nat.check(nat.lib().kd_adagn_apply_f32(_p(x), ldx, _p(_chk(stats, "stats")), _p(wb), wbs, _p(out), ldy, B, hw, chan, groups, int(bool(gelu)),
                                            _stream()), "kd_adagn_apply_f32")
     return out
+
+
+def _dual(x, x_dot, name):
+    """Row strides of a primal and its tangent, which has the primal's shape."""
+    ldx, ldxd = _rows(x, name), _rows(x_dot, name + "_dot")
+    if x_dot.shape != x.shape:
+        raise ValueError(f"{name}_dot: tangent shape {tuple(x_dot.shape)} != primal shape {tuple(x.shape)}")
+    return ldx, ldxd
+
+
+def groupnorm_stats_jvp(x, x_dot, B, groups, eps=1e-5, out=None, out_dot=None):
+    """(stats, jstats): ``groupnorm_stats(x)`` with the same bits, and jstats [B, groups, 4] = (mean_dot, rstd_dot, 0, 0), the statistics'
+    tangents along x_dot (``kd_groupnorm_stats_jvp_f32``)."""
+    ldx, ldxd = _dual(x, x_dot, "x")
+    hw, chan = x.shape[0] // B, x.shape[1]
+    out = torch.empty(B, groups, 4, device=x.device, dtype=torch.float32) if out is None else out
+    out_dot = torch.empty(B, groups, 4, device=x.device, dtype=torch.float32) if out_dot is None else out_dot
+    if tuple(_chk(out, "stats").shape) != (B, groups, 4) or tuple(_chk(out_dot, "jstats").shape) != (B, groups, 4) or hw * B != x.shape[0]:
+        raise ValueError(f"groupnorm_stats_jvp: stats {tuple(out.shape)}, jstats {tuple(out_dot.shape)} / rows {x.shape[0]} for batch {B}, "
+                         f"{groups} groups")
+    nat.check(nat.lib().kd_groupnorm_stats_jvp_f32(_p(x), ldx, _p(x_dot), ldxd, _p(out), _p(out_dot), B, hw, chan, groups, float(eps), _stream()),
+              "kd_groupnorm_stats_jvp_f32")
+    return out, out_dot
+
+
+def adagn_apply_jvp(x, x_dot, stats, jstats, wb, gelu=False, out=None, out_dot=None):
+    """(y, y_dot): ``adagn_apply(x, stats, wb, gelu)`` with the same bits, and its tangent along x_dot with the conditioning ``wb`` held fixed
+    (``kd_adagn_apply_jvp_f32``).  ``out`` may be x together with ``out_dot`` being x_dot (in place)."""
+    ldx, ldxd = _dual(x, x_dot, "x")
+    B, groups = stats.shape[:2]
+    hw, chan = x.shape[0] // B, x.shape[1]
+    wbs = _rows(wb, "wb")
+    if wb.shape[0] != B or wb.shape[1] != 2 * chan:
+        raise ValueError(f"adagn_apply_jvp: wb {tuple(wb.shape)} != {(B, 2 * chan)}")
+    if tuple(_chk(jstats, "jstats").shape) != tuple(_chk(stats, "stats").shape) or hw * B != x.shape[0]:
+        raise ValueError(f"adagn_apply_jvp: stats {tuple(stats.shape)}, jstats {tuple(jstats.shape)} / rows {x.shape[0]} for batch {B}")
+    out = torch.empty(x.shape[0], chan, device=x.device, dtype=torch.float32) if out is None else out
+    out_dot = torch.empty(x.shape[0], chan, device=x.device, dtype=torch.float32) if out_dot is None else out_dot
+    ldy, ldyd = _dual(out, out_dot, "out")
+    if out.shape != x.shape:
+        raise ValueError(f"adagn_apply_jvp: out {tuple(out.shape)} != x {tuple(x.shape)}")
+    nat.check(nat.lib().kd_adagn_apply_jvp_f32(_p(x), ldx, _p(x_dot), ldxd, _p(stats), _p(jstats), _p(wb), wbs, _p(out), ldy, _p(out_dot), ldyd, B, hw,
+                                               chan, groups, int(bool(gelu)), _stream()), "kd_adagn_apply_jvp_f32")
+    return out, out_dot
 
 
 def _resample(entry, x, B, H, W, out, Ho, Wo):
