@@ -717,16 +717,10 @@ int kd_prof_clock_buffer(void* dev_ptr);
 
 /* A forward's launch list in ONE host call (round 4).  The Python mirror used to issue the 58 - 66 launches of a model call one ctypes call
  * at a time; kd_run_list walks an array of calls and invokes the entry point each one names with the arguments it carries, in order, on
- * `stream`; it stops at the first failure, returns that entry point's code and stores the index in *failed (if not NULL).  Descriptors are
- * passed by ADDRESS (p[0]) and read at the call, so a caller may keep patching them between runs.  Arguments of the other entry points:
- * their pointer arguments in declaration order in p[], their int arguments in declaration order in i[], their one float (eps) in f.
- *   KD_OP_GEMM_F32 / KD_OP_GEMM_BF16 : p[0] = const KdGemm*          KD_OP_FFN_F32 / KD_OP_FFN_BF16 : p[0] = const KdFfn*
- *   KD_OP_ATTN_GLOBAL_F32 : p = qkv, out, scale_h, cos_t, sin_t; i = batch, T, nh, prep, precision; f = eps
- *   KD_OP_ATTN_WINDOW_F32 : p as above; i = batch, H, W, nh, ws, shift, prep, precision        KD_OP_ATTN_NA2D_F32 : i = batch, H, W, nh, ks, prep, precision
- *   KD_OP_ATTN_GLOBAL_BF16 : p = qkv, out; i = batch, T, nh      KD_OP_ATTN_WINDOW_BF16 : i = batch, H, W, nh, ws, shift      KD_OP_ATTN_NA2D_BF16 : i = batch, H, W, nh, ks
- *   KD_OP_NORM_SPLIT_F32 : p = x, scale, hi, lo; i = scale_stride, rows_per_sample, M, K; f = eps
- *   KD_OP_ATTN_BLOCK_BF16 / KD_OP_PROJ_BLOCK_BF16 / KD_OP_GEMM_MX8 : p[0] = const KdGemm*
- *   KD_OP_ATTN_FFN_F32 : p = qkv, const KdFfn*; i = batch, H, W, nh, ks */
+ * `stream`; it stops at the first failure, returns that entry point's code and stores the index in *failed (if not NULL).  A KdCall carries
+ * the arguments of the entry point KD_OP_X names (kd_x) by one rule: its pointer arguments in declaration order in p[], its int arguments in
+ * declaration order in i[], its one float (eps) in f; the trailing stream is the list's.  Descriptors (KdGemm, KdFfn) go in by ADDRESS like any
+ * other pointer and are read at the call, so a caller may keep patching them between runs. */
 enum { KD_OP_GEMM_F32 = 0, KD_OP_GEMM_BF16 = 1, KD_OP_FFN_F32 = 2, KD_OP_FFN_BF16 = 3,
        KD_OP_ATTN_GLOBAL_F32 = 4, KD_OP_ATTN_WINDOW_F32 = 5, KD_OP_ATTN_NA2D_F32 = 6,
        KD_OP_ATTN_GLOBAL_BF16 = 7, KD_OP_ATTN_WINDOW_BF16 = 8, KD_OP_ATTN_NA2D_BF16 = 9, KD_OP_NORM_SPLIT_F32 = 10,

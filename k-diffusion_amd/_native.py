@@ -6,16 +6,34 @@ The library is built in-tree by ``__graft_entry__.build()`` / ``make -C k-diffus
 import ctypes as C
 import os
 
+from ._abi import HeaderError, parse
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KDIFF_HIP_LIB") or os.path.join(_HERE, "csrc", "libkdiff_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_hip.h")
 
-# enums (include/kdiff_hip.h)
-A_PLAIN, A_MERGE2x2, A_PATCH_NCHW = 0, 1, 2
-EPI_STORE, EPI_RESIDUAL, EPI_GEGLU, EPI_SPLIT_LERP, EPI_UNPATCH_NCHW, EPI_QKV = 0, 1, 2, 3, 4, 5
-PREC_EXACT, PREC_SPLIT3, PREC_BF16 = 0, 1, 2
-PC_ONE, PC_SKIP, PC_OUT, PC_IN = 0, 1, 2, 3          # kd_precond_vjp_f32's Karras scalings (KD_PC_*)
-WG_PLAIN, WG_MERGE2x2, WG_PATCH_NCHW = 0, 1, 2      # kd_wgrad_f32's operand gathers (KD_WG_*)
-LW_KARRAS, LW_SOFT_MIN_SNR, LW_SNR, LW_GIVEN = 0, 1, 2, 3   # kd_loss_f32's weightings (KD_LW_*)
+
+class NativeLibraryError(RuntimeError):
+    pass
+
+
+# The header is the one declaration of the ABI: every entry point's argument and return types (SIGNATURES, RESTYPES), the descriptor
+# structs (KdGemm, KdFfn, KdCall, KdMtTensor, KdAdamGroup) and every KD_X enum constant / integer #define as X (A_PLAIN, EPI_QKV,
+# STEP_TO_D, MT_CHUNK, OP_GEMM_F32, ...) are read from it here (_abi.parse states the type rule)
+try:
+    with open(HEADER_PATH) as _header:
+        _parsed = parse(_header.read())
+except OSError as e:
+    raise NativeLibraryError(f"{HEADER_PATH}: the C ABI header the package binds from cannot be read ({e})") from e
+SIGNATURES, RESTYPES = _parsed.signatures, _parsed.restypes
+globals().update(_parsed.structs)
+globals().update({name[3:]: value for name, value in _parsed.constants.items()})
+# entry points a kd_run_list entry can name: KD_OP_X names kd_x
+RUN_LIST_OPS = {"kd_" + name[6:].lower(): value for name, value in _parsed.constants.items() if name.startswith("KD_OP_")}
+if not set(RUN_LIST_OPS) <= set(SIGNATURES):
+    raise HeaderError(f"KD_OP_* without an entry point: {sorted(set(RUN_LIST_OPS) - set(SIGNATURES))}")
+_i, _f = C.c_int, C.c_float                  # the kinds encode_call tells apart (the parser hands out these very objects)
+
 # PREC_FP8 is a mode of the NETWORK, not a KdGemm.precision value: the bf16 mode with the AdaRMSNorm -> wide projections of the K = 256 / 512
 # levels on the block-scaled fp8 matrix instruction (kd_gemm_mx8); every descriptor of such a plan says KD_PREC_BF16
 PREC_FP8 = 3
@@ -45,188 +63,6 @@ def kernel_precision():
 
 def precision_name(p):
     return {v: k for k, v in _MODES.items()}[p]
-(STEP_EULER, STEP_HEUN_PRED, STEP_HEUN_CORR, STEP_DPMPP_2M1, STEP_DPMPP_2M2, STEP_ADD_NOISE, STEP_LERP2, STEP_AXPY,
- STEP_EULER_FROM, STEP_AXPBY, STEP_ADD_DIFF, STEP_TO_D) = range(12)
-
-
-class KdGemm(C.Structure):
-    _fields_ = [
-        ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
-        ("a_mode", C.c_int), ("epi", C.c_int), ("norm", C.c_int),
-        ("rows_per_sample", C.c_int), ("scale_stride", C.c_int),
-        ("gh", C.c_int), ("gw", C.c_int), ("ph", C.c_int), ("pw", C.c_int), ("chan", C.c_int),
-        ("eps", C.c_float), ("out_add", C.c_float), ("sigma_data", C.c_float),
-        ("A", C.c_void_p), ("W", C.c_void_p), ("C", C.c_void_p), ("R", C.c_void_p),
-        ("scale", C.c_void_p), ("sigma", C.c_void_p), ("fac", C.c_void_p),
-        ("precision", C.c_int), ("Wp", C.c_void_p),
-        ("n_heads", C.c_int), ("qk_scale", C.c_void_p), ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p),
-        ("qkv_packed", C.c_int), ("rope_pos", C.c_void_p), ("rope_freq", C.c_void_p),
-        ("a_split", C.c_int), ("c_split", C.c_int), ("A_lo", C.c_void_p), ("C_lo", C.c_void_p),
-        ("per_row", C.c_int),
-    ]
-
-
-class KdFfn(C.Structure):
-    """include/kdiff_hip.h KdFfn: the fused feed-forward block (FeedForwardBlock.forward, image_transformer_v2.py:487-493)."""
-    _fields_ = [
-        ("x", C.c_void_p), ("out", C.c_void_p), ("scale", C.c_void_p),
-        ("scale_stride", C.c_int), ("rows_per_sample", C.c_int), ("eps", C.c_float),
-        ("Wp_up", C.c_void_p), ("Wp_down", C.c_void_p),
-        ("M", C.c_int), ("K", C.c_int), ("d_ff", C.c_int),
-        ("attn", C.c_void_p), ("Wp_out", C.c_void_p),
-    ]
-
-
-class KdCall(C.Structure):
-    """include/kdiff_hip.h KdCall: one launch of a kd_run_list list (entry point + its arguments)."""
-    _fields_ = [("op", C.c_int), ("f", C.c_float), ("p", C.c_void_p * 5), ("i", C.c_int * 8)]
-
-
-class KdMtTensor(C.Structure):
-    """include/kdiff_hip.h KdMtTensor: one parameter of a multi-tensor launch (csrc/optim_f32.hip)."""
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("ema", C.c_void_p),
-                ("n", C.c_longlong), ("group", C.c_int), ("reserved", C.c_int)]
-
-
-class KdAdamGroup(C.Structure):
-    """include/kdiff_hip.h KdAdamGroup: the constants of one AdamW group for one step (fp64, computed by the host)."""
-    _fields_ = [("lr", C.c_double), ("wd", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
-                ("bc1", C.c_double), ("bc2", C.c_double)]
-
-
-MT_CHUNK = 8192                                      # KD_MT_CHUNK
-(DENSITY_LOGNORMAL, DENSITY_LOGLOGISTIC, DENSITY_LOGUNIFORM, DENSITY_V_DIFFUSION, DENSITY_COSINE_INTERPOLATED,
- DENSITY_SPLIT_LOGNORMAL) = range(6)                 # KD_DENSITY_*
-
-_vp, _i, _f, _ll, _d = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_double
-_u, _ull = C.c_uint, C.c_ulonglong
-
-# name -> argtypes; every symbol declared in include/kdiff_hip.h
-SIGNATURES = {
-    "kd_version": [],
-    "kd_last_error": [],
-    "kd_set_option": [C.c_char_p, _i],
-    "kd_get_option": [C.c_char_p, _i],
-    "kd_gemm_f32": [C.POINTER(KdGemm), _vp],
-    "kd_gemm_bf16": [C.POINTER(KdGemm), _vp],
-    "kd_packed_weight_bytes_bf16": [_i, _i, _i],
-    "kd_pack_weight_bf16": [_vp, _vp, _i, _i, _i, _vp],
-    "kd_ffn_bf16_supported": [_i, _i, _i],
-    "kd_ffn_bf16": [_vp, _vp],
-    "kd_ffn_f32_supported": [_i, _i, _i],
-    "kd_ffn_f32": [_vp, _vp],
-    "kd_attn_ffn_f32_supported": [_i, _i, _i, _i, _i, _i, _i],
-    "kd_attn_ffn_f32": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "kd_attn_global_bf16": [_vp, _vp, _i, _i, _i, _vp],
-    "kd_attn_window_bf16": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "kd_attn_na2d_bf16": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "kd_attn_block_bf16_supported": [_i, _i, _i],
-    "kd_attn_block_bf16": [C.POINTER(KdGemm), _vp],
-    "kd_proj_block_bf16_supported": [_i, _i, _i, _i],
-    "kd_proj_block_bf16": [C.POINTER(KdGemm), _vp],
-    "kd_packed_weight_bytes_mx8": [_i, _i, _i],
-    "kd_pack_weight_mx8": [_vp, _vp, _i, _i, _i, _vp],
-    "kd_gemm_mx8_supported": [_i, _i, _i, _i, _i],
-    "kd_gemm_mx8": [C.POINTER(KdGemm), _vp],
-    "kd_packed_weight_bytes": [_i, _i, _i],
-    "kd_pack_weight_bf16x3": [_vp, _vp, _i, _i, _i, _vp],
-    "kd_rmsnorm_f32": [_vp, _vp, _vp, _i, _i, _f, _vp],
-    "kd_fourier_sigma_f32": [_vp, _vp, _vp, _i, _i, _vp],
-    "kd_fourier_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],
-    "kd_cond_sum_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp],
-    "kd_qk_prep_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
-    "kd_attn_global_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp],
-    "kd_attn_window_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp],
-    "kd_attn_na2d_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp],
-    "kd_sampler_step_f32": [_i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _ll, _vp],
-    "kd_precond_in_f32": [_vp, _vp, _vp, _f, _i, _ll, _vp],
-    "kd_precond_out_f32": [_vp, _vp, _vp, _vp, _f, _i, _ll, _vp],
-    "kd_rows_affine_f32": [_vp, _vp, _vp, _vp, _vp, _i, _ll, _vp],
-    "kd_sigma_to_t_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],
-    "kd_t_to_sigma_f32": [_vp, _vp, _vp, _i, _i, _vp],
-    "kd_dpm_eps_f32": [_vp, _vp, _vp, _f, _ll, _vp],
-    "kd_dpm_combine_f32": [_vp, _vp, _vp, _vp, _f, _f, _ll, _vp],
-    "kd_dpm_error_partials": [],
-    "kd_dpm_error_f32": [_vp, _vp, _vp, _f, _f, _ll, _vp, _vp],
-    "kd_brownian_f32": [_vp, _vp, _i, _ll, _d, _d, _d, _d, _f, _i, _vp],
-    "kd_brownian_cached_f32": [_vp, _vp, _vp, _i, _i, _vp, _i, _ll, _d, _d, _d, _d, _f, _i, _vp],
-    "kd_randn_f32": [_vp, _vp, _i, _ll, C.c_ulonglong, _f, _vp],
-    "kd_to_uint8": [_vp, _vp, _ll, _vp],
-    "kd_norm_split_f32": [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp],
-    "kd_rmsnorm_jvp_f32": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp],
-    "kd_geglu_jvp_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp],
-    "kd_qk_prep_jvp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
-    "kd_attn_global_jvp_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "kd_attn_window_jvp_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "kd_attn_na2d_jvp_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "kd_ll_div_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _vp],
-    "kd_gauss_logp_f32": [_vp, _f, _vp, _vp, _i, _ll, _vp],
-    "kd_rk_combine_f32": [_vp, _vp, _vp, _vp, _i, _ll, _vp],
-    "kd_rk_error_partials": [],
-    "kd_rk_error_f32": [_vp, _vp, _i, _vp, _vp, _f, _f, _ll, _vp, _vp],
-    "kd_rmsnorm_vjp_f32": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp],
-    "kd_geglu_vjp_f32": [_vp, _vp, _vp, _i, _i, _vp],
-    "kd_geglu_vjp_drop_f32": [_vp, _vp, _vp, _i, _i, _vp, _ull, _u, _f, _vp],
-    "kd_qk_prep_vjp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
-    "kd_attn_global_vjp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "kd_attn_window_vjp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "kd_attn_na2d_vjp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "kd_precond_vjp_f32": [_vp, _i, _vp, _i, _vp, _f, _vp, _i, _ll, _vp],
-    "kd_wgrad_f32": [_vp, _i, _vp, _i, _i, _ll, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
-    "kd_wgrad_drop_f32": [_vp, _i, _vp, _i, _i, _ll, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp,
-                          _vp, _ull, _u, _f, _vp, _vp],
-    "kd_dropout_f32": [_vp, _vp, _ll, _vp, _ull, _u, _f, _vp],
-    "kd_augment_draw_f32": [_vp, _i, _f, _vp, _vp],
-    "kd_augment_warp_f32": [_vp, _vp, _f, _f, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "kd_batch_u8_f32": [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _i, _i, _i, _i, _vp],
-    "kd_class_dropout_i64": [_vp, _vp, _f, _i, _vp, _i, _vp],
-    "kd_pack_conv_x3": [_vp, _vp, _i, _i, _i, _vp],
-    "kd_conv2d_x3": [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "kd_conv2d_x3_stacked": [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "kd_groupnorm_stats_f32": [_vp, _i, _vp, _i, _i, _i, _i, _f, _vp],
-    "kd_groupnorm_stats_jvp_f32": [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    "kd_adagn_apply_jvp_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "kd_adagn_apply_f32": [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "kd_down2_f32": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
-    "kd_up2_f32": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
-    "kd_unet_in_f32": [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _vp],
-    "kd_unet_out_f32": [_vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
-    "kd_cond_mlp_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "kd_row_rrms_f32": [_vp, _vp, _ll, _i, _f, _vp],
-    "kd_colsum_f32": [_vp, _vp, _vp, _vp, _ll, _i, _ll, _i, _vp, _vp, _vp],
-    "kd_attn_scale_grad_f32": [_vp, _vp, _i, _i, _vp, _vp],
-    "kd_class_emb_grad_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "kd_loss_prep_f32": [_vp, _vp, _vp, _f, _vp, _vp, _i, _ll, _vp],
-    "kd_loss_f32": [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _i, _ll, _vp],
-    "kd_loss_vjp_f32": [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _i, _ll, _vp],
-    "kd_mmd_poly_f32": [_vp, _ll, _ll, _vp, _ll, _ll, _i, _i, _i, _vp, _f, _i, _vp, _vp],
-    "kd_poly_kernel_f32": [_vp, _ll, _ll, _vp, _ll, _ll, _i, _i, _i, _vp, _vp],
-    "kd_mmd_mats_f32": [_vp, _vp, _vp, _ll, _ll, _i, _vp, _vp, _vp],
-    "kd_jacobi_sweep_f64": [_vp, _vp, _i, _i, _d, _vp, _vp, _vp],
-    "kd_sym_lower_f64": [_vp, _i, _vp, _vp, _i, _i, _d, _vp],
-    "kd_row_sqrt_norm_f64": [_vp, _ll, _i, _vp, _vp],
-    "kd_gemm_tn_f64": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
-    "kd_center_f32": [_vp, _vp, _ll, _i, _vp, _vp, _vp],
-    "kd_transpose_f64": [_vp, _vp, _i, _i, _vp],
-    "kd_sqrtm_vjp_div_f64": [_vp, _vp, _i, _i, _vp, _vp],
-    "kd_f32_to_f64": [_vp, _vp, _ll, _vp],
-    "kd_fid_finish_f32": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
-    "kd_mt_sqnorm_f32": [_vp, _vp, _i, _f, _vp, _vp, _vp],
-    "kd_mt_adamw_ema_f32": [_vp, _vp, _i, _vp, _i, _vp, _d, _i, _i, _vp],
-    "kd_mt_lerp_f32": [_vp, _vp, _i, _d, _vp],
-    "kd_sigma_density_f32": [_i, _vp, _i, _vp, _vp, _i, _ll, _i, _i, _i, _vp, _vp],
-    "kd_prof_enable": [_i],
-    "kd_prof_count": [],
-    "kd_prof_get": [_i, C.c_char_p, _i, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double)],
-    "kd_prof_reset": [],
-    "kd_prof_clock_buffer": [_vp],
-    "kd_run_list": [C.POINTER(KdCall), _i, _vp, C.POINTER(C.c_int)],
-}
-
-# entry points a kd_run_list entry can name (include/kdiff_hip.h: KD_OP_*)
-RUN_LIST_OPS = {"kd_gemm_f32": 0, "kd_gemm_bf16": 1, "kd_ffn_f32": 2, "kd_ffn_bf16": 3, "kd_attn_global_f32": 4, "kd_attn_window_f32": 5,
-                "kd_attn_na2d_f32": 6, "kd_attn_global_bf16": 7, "kd_attn_window_bf16": 8, "kd_attn_na2d_bf16": 9, "kd_norm_split_f32": 10,
-                "kd_attn_block_bf16": 11, "kd_proj_block_bf16": 12, "kd_gemm_mx8": 13, "kd_attn_ffn_f32": 14}
 
 
 def encode_call(call, name, args):
@@ -265,10 +101,6 @@ def encode_call(call, name, args):
 _lib = None
 
 
-class NativeLibraryError(RuntimeError):
-    pass
-
-
 def lib():
     """The loaded shared library (loads on first use; raises loudly if it is not there)."""
     global _lib
@@ -285,7 +117,7 @@ def lib():
             except AttributeError as e:
                 raise NativeLibraryError(f"{LIB_PATH} does not export {name}") from e
             fn.argtypes = argtypes
-            fn.restype = C.c_char_p if name == "kd_last_error" else (C.c_longlong if name.startswith("kd_packed_weight_bytes") else C.c_int)
+            fn.restype = RESTYPES[name]
         _lib = handle
     _sync_options(_lib)
     return _lib
