@@ -86,7 +86,7 @@ __global__ __launch_bounds__(QW * 64, (QW <= 4 && MODE != MODE_WINDOW16) ? 2 : 1
     }
   }
   // ---- masks + softmax over keys -----------------------------------------------------------------------------------------------
-  const int q_region = (MODE != MODE_GLOBAL) ? slot_region<MODE>(min(q_slot, T - 1), wi, wj, a.shift) : 0;
+  const int q_region = (MODE != MODE_GLOBAL) ? slot_region<MODE>(a.shift, min(q_slot, T - 1), wi, wj) : 0;
   if (MODE != MODE_GLOBAL || (T & 31)) {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(QW * 64, (QW <= 4 && MODE != MODE_WINDOW16) ? 2 : 1
           if (t * 32 + 32 > T) S[t][i] += (ks < T) ? 0.f : -INFINITY;
         } else {
           if ((1 << (2 * WinLog2<MODE>::v)) < TP) S[t][i] += (ks < T) ? 0.f : -INFINITY;
-          if (a.shift) S[t][i] += (slot_region<MODE>(min(ks, T - 1), wi, wj, a.shift) == q_region) ? 0.f : -INFINITY;
+          if (a.shift) S[t][i] += (slot_region<MODE>(a.shift, min(ks, T - 1), wi, wj) == q_region) ? 0.f : -INFINITY;
         }
       }
   }
@@ -210,30 +210,18 @@ __global__ __launch_bounds__(GL_QW * 64) void attn_long_bf16_kernel(const DArgs 
 }
 
 // ---- neighbourhood core ---------------------------------------------------------------------------------------------------------------
-// One 256-thread workgroup per (sample, head, 8x16 query tile); KS = kernel size (3, 5, 7, 9).  The (8 + KS - 1) x (16 + KS - 1)
-// key halo of the tile goes to LDS once (K image + V image).  Wave (wy, wx) owns the 4x8 query block at rows 4wy.., columns
-// 8wx..: the clamped windows of its queries lie inside a PR x 16-or-32-column patch of the halo (PR = 4 + KS - 1 rows), walked
-// as local keys kl = PW * r + c (PW = 16 for KS <= 9, else 32) in tiles of 32; keys outside a query's window get a -inf bias
-// from per-lane bit words (one word per tile).  Out-of-image halo positions (images smaller than the halo) are clamped to a real
-// token: they are outside every window, so their probability is exactly 0.
+// One 256-thread workgroup per (sample, head, 8x16 query tile); KS = kernel size (3, 5, 7, 9).  Tile, halo, patch and window validity:
+// attn_geo.h.  The key halo of the tile goes to LDS once; a wave walks its patch as local keys 16 r + c in tiles of 32, and keys outside a
+// query's window meet -inf in a v_min3, so their probability is exactly 0.
 struct NArgs {
   const u16* qkv; u16* out;
   int batch, H, W, nh;
   int warm;                  // code warm-up workgroups (kd_common.h)
 };
-constexpr int NA_TH = 8, NA_TW = 16;
-
-template <int KS>
-struct NaGeo {
-  static constexpr int HR = NA_TH + KS - 1, HC = NA_TW + KS - 1;            // halo
-  static constexpr int PR = 4 + KS - 1;                                      // patch rows of a wave
-  static constexpr int PW = (8 + KS - 1 <= 16) ? 16 : 32;                    // patch width (keys per patch row)
-  static constexpr int NKT = (PR * PW + 31) / 32;                            // key tiles per wave
-  // image rows: a wave's patch may poke past the halo's last key -- the highest row any fragment read touches is
-  // (HR - 1) HC + (HC - (8 + KS - 1)) + 15 = HR HC - KS + 8.  Kept tight: at KS = 7 the image takes 39 KiB (round 6: one image for K, then V), THREE workgroups per CU
-  static constexpr int ROWS = ((HR * HC - KS + 9 + 7) / 8) * 8;
-  static constexpr int LDS = ROWS * 128;                                     // ONE image: K, then V
-};
+// Image sizes (attn_geo.h): rows of 128 bytes, 8 per LDS-DMA instruction, ONE image for K, then V.  Kept tight: at KS = 7 the image takes
+// 39 KiB, THREE workgroups per CU.
+template <int KS> using NaGeo = NaGeoB16<KS>;
+static_assert(NaGeo<3>::LDS == 24576 && NaGeo<5>::LDS == 31744 && NaGeo<7>::LDS == 39936 && NaGeo<9>::LDS == 49152, "image sizes");
 
 // Round 6: K and V go through ONE image -- the V rows are requested behind the barrier that ends the score MFMAs and land behind the
 // softmax -- so a workgroup holds 39 KiB instead of 78 (KS = 7) and THREE of them fit a CU (150 registers): a workgroup is a serial chain
@@ -242,26 +230,20 @@ struct NaGeo {
 template <int KS>
 __global__ __launch_bounds__(256, NaGeo<KS>::LDS <= 53 * 1024 ? 3 : 2) void attn_na2d_bf16_kernel(const NArgs a) {
   using G = NaGeo<KS>;
-  constexpr int HR = G::HR, HC = G::HC, PR = G::PR, PW = G::PW, NKT = G::NKT, ROWS = G::ROWS;
+  constexpr int HC = G::HC, NKT = G::NKT, ROWS = G::ROWS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Kimg = smem;
   char* Vimg = smem;
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, h2 = lane >> 5;
   const auto warm = code_warm_begin<7168>((int)blockIdx.x < a.warm && tid < 64);
   const int wy_ = wid >> 1, wx_ = wid & 1;
-  const int tiles_x = (a.W + NA_TW - 1) / NA_TW, tiles_y = (a.H + NA_TH - 1) / NA_TH;
-  int r = KD_XCD_CHUNK();      // XCD-aware order: neighbouring tiles (overlapping halos) run on ONE L2
-  const int tx = r % tiles_x; r /= tiles_x;
-  const int ty = r % tiles_y; r /= tiles_y;
-  const int head = r % a.nh, b = r / a.nh;
+  KD_NA_TILE(a, KD_XCD_CHUNK())      // tx, ty, head, b; XCD-aware order: neighbouring tiles (overlapping halos) run on ONE L2
   const int T = a.H * a.W;
   const size_t row_bytes = (size_t)3 * a.nh * DH * 2;
   const char* base = reinterpret_cast<const char*>(a.qkv) + (size_t)b * T * row_bytes + head * (DH * 2);
-  const int ty0 = ty * NA_TH, tx0 = tx * NA_TW;
-  const int hy0 = max(0, min(ty0 - KS / 2, a.H - HR)), hx0 = max(0, min(tx0 - KS / 2, a.W - HC));
+  KD_NA_HALO(G, a, ty, tx)      // ty0, tx0, hy0, hx0
 
   // ---- halo rows -> K / V images: image row 8 pc + (lane >> 3) = halo position (y, x), walked 32 rows at a time ----------------
-  static_assert(PW == 16, "kernel sizes up to 9: 16-key patch rows");
   auto stage = [&](bool want_k, bool want_v) {
     int row = 8 * wid + (lane >> 3);
     int y = row / HC, x = row % HC;
@@ -278,32 +260,16 @@ __global__ __launch_bounds__(256, NaGeo<KS>::LDS <= 53 * 1024 ? 3 : 2) void attn
   };
   stage(true, false);
   // ---- this lane's query ------------------------------------------------------------------------------------------------------------
-  const int qy_raw = ty0 + 4 * wy_ + (l31 >> 3), qx_raw = tx0 + 8 * wx_ + (l31 & 7);
-  const bool q_ok = qy_raw < a.H && qx_raw < a.W;
-  const int qy = min(qy_raw, a.H - 1), qx = min(qx_raw, a.W - 1);
-  const int q_tok = qy * a.W + qx;
+  KD_NA_QUERY(a, ty0, tx0, wy_, wx_, l31)      // q_ok, qy, qx, q_tok
   bf16x8 qf[4];
   {
     const u32x4* qp = reinterpret_cast<const u32x4*>(base + (size_t)q_tok * row_bytes + 16 * h2);
 #pragma unroll
     for (int st = 0; st < 4; ++st) qf[st] = __builtin_bit_cast(bf16x8, qp[2 * st]);
   }
-  // clamped window start (NATTEN: start = clamp(i - KS/2, 0, L - KS)) relative to the halo; patch origin of this wave
-  const int wy = max(0, min(qy - KS / 2, a.H - KS)) - hy0, wx = max(0, min(qx - KS / 2, a.W - KS)) - hx0;
-  const int row_lo = min(max(0, min(min(ty0 + 4 * wy_, a.H - 1) - KS / 2, a.H - KS)) - hy0, HR - PR);
-  const int col_lo = min(max(0, min(min(tx0 + 8 * wx_, a.W - 1) - KS / 2, a.W - KS)) - hx0, HC - (8 + KS - 1));
-  const int korg = row_lo * HC + col_lo;          // halo index of patch key (0, 0); local key 16 r + c is image row korg + HC r + c
-  // validity of patch column / patch row for THIS lane's query as +inf (inside the window) / -inf: v_min3 applies both at once.
-  // Accumulator register i of a tile holds local key (i & 3) + 8 (i >> 2) + 4 h2: column (i & 3) + 8 ((i >> 2) & 1) + 4 h2 of patch
-  // row 2 t + (i >> 3).
+  KD_NA_PATCH(G, a, ty0, tx0, hy0, hx0, wy_, wx_, qy, qx)      // korg, r0, c0: this wave's patch, the lane's window inside it
   float colv[8], rowv[2 * NKT];
-  {
-    const int r0 = wy - row_lo, c0 = wx - col_lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) colv[j] = ((unsigned)((j & 3) + 8 * (j >> 2) + 4 * h2 - c0) < (unsigned)KS) ? INFINITY : -INFINITY;
-#pragma unroll
-    for (int p = 0; p < 2 * NKT; ++p) rowv[p] = ((unsigned)(p - r0) < (unsigned)KS) ? INFINITY : -INFINITY;
-  }
+  KD_NA_VALID_WORDS(KS, 2 * NKT, r0, c0, h2, colv, rowv)
   KD_WAIT_VM(0);
   code_warm_end(warm);
   KD_BARRIER();
@@ -316,10 +282,10 @@ __global__ __launch_bounds__(256, NaGeo<KS>::LDS <= 53 * 1024 ? 3 : 2) void attn
     for (int i = 0; i < 16; ++i) S[t][i] = 0.f;
   int ka[NKT];
   {
-    const int kr0 = korg + (l31 >> 4) * HC + (l31 & 15);
+    const int kr0 = KD_NA_K_ROW0(G, korg, l31);
 #pragma unroll
     for (int t = 0; t < NKT; ++t) {
-      const int kr = kr0 + 2 * t * HC;
+      const int kr = na_k_row<G>(kr0, t);
       ka[t] = kr * 128 + ((h2 ^ asw(kr)) << 4);
     }
   }
@@ -356,11 +322,11 @@ __global__ __launch_bounds__(256, NaGeo<KS>::LDS <= 53 * 1024 ? 3 : 2) void attn
   for (int e = 0; e < 2; ++e)
 #pragma unroll
     for (int i = 0; i < 16; ++i) O[e][i] = 0.f;
-  const int vr0 = korg + 4 * h2 + vt_lane_row(lane);
+  const int vr0 = na_v_row0(korg, h2, vt_lane_row(lane));
 #pragma unroll
   for (int t = 0; t < NKT; ++t)
 #pragma unroll
-    for (int u = 0; u < 2; ++u) pv_step(O, Vimg, vt_addr(vr0 + (2 * t + u) * HC, lane), p_frag(S[t], u));
+    for (int u = 0; u < 2; ++u) pv_step(O, Vimg, vt_addr(na_v_row<G>(vr0, t, u), lane), p_frag(S[t], u));
   store_o(a.out + ((size_t)b * T + q_tok) * (a.nh * DH) + head * DH, O, 1.0f / l, h2, q_ok);
 }
 
@@ -376,36 +342,24 @@ __global__ __launch_bounds__(256, NaGeo<KS>::LDS <= 53 * 1024 ? 3 : 2) void attn
 // the V^T reads never straddle two patch rows), tiles of 32 keys, every key's (row, column) by constant division, validity per
 // accumulator register from those.  One workgroup per CU (122 / 145 KiB of halo images), the whole register file per wave.
 // Correctness form for the sizes no shipped config uses; the 3..9 kernel above is the tuned one.
-template <int KS>
-struct NaWide {
-  static constexpr int HR = NA_TH + KS - 1, HC = NA_TW + KS - 1;
-  static constexpr int PR = 4 + KS - 1, PC = 20;                            // patch rows; padded patch width
-  static constexpr int NKT = (PR * PC + 31) / 32;
-  static constexpr int ROWS = ((HR * HC + 2 * PC + 7) / 8) * 8;             // slack: padded columns and the last tile's tail poke past the halo
-  static constexpr int LDS = 2 * ROWS * 128;
-  static_assert(8 + KS - 1 <= PC, "patch width");
-};
+template <int KS> using NaWide = NaWideB16<KS>;      // attn_geo.h; a K image and a V image
+static_assert(NaWide<11>::LDS == 131072 && NaWide<13>::LDS == 153600, "image sizes");
 
 template <int KS>
 __global__ __launch_bounds__(256, 1) void attn_na2d_wide_bf16_kernel(const NArgs a) {
   using G = NaWide<KS>;
-  constexpr int HR = G::HR, HC = G::HC, PR = G::PR, PC = G::PC, NKT = G::NKT, ROWS = G::ROWS;
+  constexpr int HC = G::HC, NKT = G::NKT, ROWS = G::ROWS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Kimg = smem;
   char* Vimg = smem + ROWS * 128;
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, h2 = lane >> 5;
   const auto warm = code_warm_begin<24576>((int)blockIdx.x < a.warm && tid < 64);
   const int wy_ = wid >> 1, wx_ = wid & 1;
-  const int tiles_x = (a.W + NA_TW - 1) / NA_TW, tiles_y = (a.H + NA_TH - 1) / NA_TH;
-  int r = blockIdx.x;
-  const int tx = r % tiles_x; r /= tiles_x;
-  const int ty = r % tiles_y; r /= tiles_y;
-  const int head = r % a.nh, b = r / a.nh;
+  KD_NA_TILE(a, blockIdx.x)      // tx, ty, head, b
   const int T = a.H * a.W;
   const size_t row_bytes = (size_t)3 * a.nh * DH * 2;
   const char* base = reinterpret_cast<const char*>(a.qkv) + (size_t)b * T * row_bytes + head * (DH * 2);
-  const int ty0 = ty * NA_TH, tx0 = tx * NA_TW;
-  const int hy0 = max(0, min(ty0 - KS / 2, a.H - HR)), hx0 = max(0, min(tx0 - KS / 2, a.W - HC));
+  KD_NA_HALO(G, a, ty, tx)      // ty0, tx0, hy0, hx0
   for (int pc = wid; pc < ROWS / 8; pc += 4) {
     const int row = 8 * pc + (lane >> 3);
     const int ky = min(hy0 + row / HC, a.H - 1), kx = min(hx0 + row % HC, a.W - 1);       // rows past the halo: any real token (masked)
@@ -413,22 +367,15 @@ __global__ __launch_bounds__(256, 1) void attn_na2d_wide_bf16_kernel(const NArgs
     glds16(src + a.nh * DH * 2, Kimg + pc * 1024);
     glds16(src + 2 * a.nh * DH * 2, Vimg + pc * 1024);
   }
-  const int qy_raw = ty0 + 4 * wy_ + (l31 >> 3), qx_raw = tx0 + 8 * wx_ + (l31 & 7);
-  const bool q_ok = qy_raw < a.H && qx_raw < a.W;
-  const int qy = min(qy_raw, a.H - 1), qx = min(qx_raw, a.W - 1);
-  const int q_tok = qy * a.W + qx;
+  KD_NA_QUERY(a, ty0, tx0, wy_, wx_, l31)      // q_ok, qy, qx, q_tok
   bf16x8 qf[4];
   {
     const u32x4* qp = reinterpret_cast<const u32x4*>(base + (size_t)q_tok * row_bytes + 16 * h2);
 #pragma unroll
     for (int st = 0; st < 4; ++st) qf[st] = __builtin_bit_cast(bf16x8, qp[2 * st]);
   }
-  const int wy = max(0, min(qy - KS / 2, a.H - KS)) - hy0, wx = max(0, min(qx - KS / 2, a.W - KS)) - hx0;
-  const int row_lo = min(max(0, min(min(ty0 + 4 * wy_, a.H - 1) - KS / 2, a.H - KS)) - hy0, HR - PR);
-  const int col_lo = min(max(0, min(min(tx0 + 8 * wx_, a.W - 1) - KS / 2, a.W - KS)) - hx0, HC - (8 + KS - 1));
-  const int korg = row_lo * HC + col_lo;
-  const int r0 = wy - row_lo, c0 = wx - col_lo;
-  auto img_row = [&](int kl) -> int { return korg + (kl / PC) * HC + (kl % PC); };     // LDS row of local key kl
+  KD_NA_PATCH(G, a, ty0, tx0, hy0, hx0, wy_, wx_, qy, qx)      // korg, r0, c0
+  auto img_row = [&](int kl) -> int { return na_wide_row<G>(korg, kl); };     // LDS row of local key kl
   KD_WAIT_VM(0);
   code_warm_end(warm);
   KD_BARRIER();
@@ -453,9 +400,7 @@ __global__ __launch_bounds__(256, 1) void attn_na2d_wide_bf16_kernel(const NArgs
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int kl = 32 * t + (i & 3) + 8 * (i >> 2) + 4 * h2;
-      const int pr = kl / PC, pcn = kl % PC;
-      const bool valid = (unsigned)(pr - r0) < (unsigned)KS && (unsigned)(pcn - c0) < (unsigned)KS && pr < PR;
-      S[t][i] = valid ? S[t][i] : -INFINITY;
+      S[t][i] = na_wide_valid<G>(kl, r0, c0) ? S[t][i] : -INFINITY;
     }
   const float m = score_max<NKT>(S);
   float l = score_exp<NKT>(S, m);
@@ -490,7 +435,7 @@ __global__ __launch_bounds__(256, 1) void attn_na2d_wide_bf16_kernel(const NArgs
 
 template <int KS>
 static int launch_na_wide(const NArgs& a, hipStream_t s) {
-  const long nb = (long)a.batch * a.nh * ((a.H + NA_TH - 1) / NA_TH) * ((a.W + NA_TW - 1) / NA_TW);
+  const long nb = na_tiles(a.batch, a.nh, a.H, a.W);
   const ProfName nm("attn_na2d_bf16", "attn_na2d_bf16 k%d %dx%d nh=%d", KS, a.H, a.W, a.nh);
   LaunchScope prof(nm, 4.0 * a.batch * (double)a.H * a.W * a.nh * DH * KS * KS, 8.0 * a.batch * (double)a.H * a.W * a.nh * DH, s);
   launch<attn_na2d_wide_bf16_kernel<KS>>(dim3((unsigned)nb), dim3(256), NaWide<KS>::LDS, s, a);
@@ -509,7 +454,7 @@ static int launch_dense(const DArgs& a, long nproblems, const char* name, hipStr
 
 template <int KS>
 static int launch_na(const NArgs& a, hipStream_t s) {
-  const long nb = (long)a.batch * a.nh * ((a.H + NA_TH - 1) / NA_TH) * ((a.W + NA_TW - 1) / NA_TW);
+  const long nb = na_tiles(a.batch, a.nh, a.H, a.W);
   constexpr int LDS = NaGeo<KS>::LDS;
   const ProfName nm("attn_na2d_bf16", "attn_na2d_bf16 k%d %dx%d nh=%d", KS, a.H, a.W, a.nh);
   LaunchScope prof(nm, 4.0 * a.batch * (double)a.H * a.W * a.nh * DH * KS * KS, 8.0 * a.batch * (double)a.H * a.W * a.nh * DH, s);
@@ -545,9 +490,7 @@ extern "C" int kd_attn_global_bf16(const void* qkv, void* out, int batch, int T,
 
 extern "C" int kd_attn_window_bf16(const void* qkv, void* out, int batch, int H, int W, int nh, int ws, int shift, void* stream) {
   if (!qkv || !out || batch <= 0 || nh <= 0 || H <= 0 || W <= 0) return fail(KD_EINVAL, "kd_attn_window_bf16: bad arguments");
-  if (ws != 4 && ws != 8 && ws != 16) return fail(KD_EINVAL, "kd_attn_window_bf16: window_size %d unsupported (4, 8 or 16)", ws);
-  if ((H % ws) || (W % ws)) return fail(KD_EINVAL, "kd_attn_window_bf16: grid %dx%d not divisible by the window", H, W);
-  if (shift < 0 || shift >= ws) return fail(KD_EINVAL, "kd_attn_window_bf16: bad shift %d", shift);
+  if (const int rc = window_check("kd_attn_window_bf16", H, W, ws, shift)) return rc;
   DArgs a{reinterpret_cast<const u16*>(qkv), reinterpret_cast<u16*>(out), batch, H * W, nh, H, W, ws, shift, code_warm()};
   const long nb = (long)batch * nh * (H / ws) * (W / ws);
   hipStream_t s = (hipStream_t)stream;
@@ -558,8 +501,7 @@ extern "C" int kd_attn_window_bf16(const void* qkv, void* out, int batch, int H,
 
 extern "C" int kd_attn_na2d_bf16(const void* qkv, void* out, int batch, int H, int W, int nh, int ks, void* stream) {
   if (!qkv || !out || batch <= 0 || nh <= 0) return fail(KD_EINVAL, "kd_attn_na2d_bf16: bad arguments");
-  if (ks < 3 || ks > 13 || !(ks & 1)) return fail(KD_EINVAL, "kd_attn_na2d_bf16: kernel_size %d unsupported (3, 5, 7, 9, 11 or 13)", ks);
-  if (H < ks || W < ks) return fail(KD_EINVAL, "kd_attn_na2d_bf16: grid %dx%d smaller than the %dx%d neighbourhood", H, W, ks, ks);
+  if (const int rc = na_check("kd_attn_na2d_bf16", ks, H, W)) return rc;
   NArgs a{reinterpret_cast<const u16*>(qkv), reinterpret_cast<u16*>(out), batch, H, W, nh, code_warm()};
   hipStream_t s = (hipStream_t)stream;
   switch (ks) {

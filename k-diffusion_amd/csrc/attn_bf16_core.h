@@ -2,14 +2,14 @@
 // operand images in LDS (swizzle, LDS-DMA helper), the V^T fragment reads, the softmax pieces and the output store.
 #pragma once
 #include "bf16_common.h"
+#include "attn_geo.h"
 
 namespace kd {
 namespace b16 {
 
 constexpr int DH = 64;
 
-enum { MODE_GLOBAL = 0, MODE_WINDOW = 1, MODE_WINDOW4 = 2, MODE_WINDOW16 = 3 };
-template <int MODE> struct WinLog2 { static constexpr int v = MODE == MODE_WINDOW ? 3 : (MODE == MODE_WINDOW4 ? 2 : 4); };
+using namespace geo;          // attn_geo.h: window modes and slot functions, neighbourhood tile and image sizes
 
 struct DArgs {
   const u16* qkv; u16* out;
@@ -17,25 +17,6 @@ struct DArgs {
   int H, W, ws, shift;       // window modes
   int warm;                  // code warm-up workgroups (kd_common.h)
 };
-
-template <int MODE>
-__device__ __forceinline__ int slot_token(const DArgs& a, int slot, int wi, int wj) {
-  if (MODE == MODE_GLOBAL) return slot;
-  constexpr int L = WinLog2<MODE>::v, WS = 1 << L;
-  const int ai = slot >> L, bj = slot & (WS - 1);
-  int i = wi * WS + ai - a.shift; if (i < 0) i += a.H;     // rolled[i] = orig[(i - shift) mod H]  (:274)
-  int j = wj * WS + bj - a.shift; if (j < 0) j += a.W;
-  return i * a.W + j;
-}
-template <int MODE>
-__device__ __forceinline__ int slot_region(int slot, int wi, int wj, int shift) {      // make_shifted_window_masks (:285-316)
-  constexpr int L = WinLog2<MODE>::v, WS = 1 << L;
-  return ((wi == 0 && (slot >> L) < shift) ? 2 : 0) + ((wj == 0 && (slot & (WS - 1)) < shift) ? 1 : 0);
-}
-
-__device__ __forceinline__ void glds16(const void* src, void* dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
 
 // 16-byte chunk swizzle of the K / V images (rows of 128 bytes): chunk q of row r sits at q ^ asw(r).  Bit 2 of the XOR word comes
 // from r bit 1, so the four rows r .. r + 3 of a ds_read_b64_tr_b16 group land in four different 64-byte quarters of the 256-byte
@@ -47,7 +28,6 @@ __device__ __forceinline__ int asw(int row) { return ((row & 2) << 1) | ((row >>
 // V^T fragments of one k-step (8 k-slots = image rows key0 .. key0+3 and key0+8 .. key0+11; features 32 e + (lane & 31), e = 0, 1)
 // through ds_read_b64_tr_b16.  `va` = vt_addr(row key0 + ((lane & 15) >> 2), lane): the e = 1 chunk is `^ 64`, the +8 row is
 // `^ 32` and 1024 bytes further.
-using s16x4 = short __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int vt_lane_row(int lane) { return (lane & 15) >> 2; }
 __device__ __forceinline__ int vt_addr(int r0, int lane) {
   const int c = 2 * ((lane >> 4) & 1) + ((lane & 3) >> 1);
@@ -69,10 +49,6 @@ __device__ __forceinline__ bf16x8 p_frag(const f32x16& S, int u) {
   return __builtin_bit_cast(bf16x8, u32x4{pack_bf16(S[8 * u], S[8 * u + 1]), pack_bf16(S[8 * u + 2], S[8 * u + 3]),
                                           pack_bf16(S[8 * u + 4], S[8 * u + 5]), pack_bf16(S[8 * u + 6], S[8 * u + 7])});
 }
-// v_max3_f32 / v_min3_f32 through the compiler's own pattern (NOT inline asm: the hazard recogniser does not look inside asm
-// operands, and an asm VALU read of a just-written MFMA result misses its wait states -- seen as wrong scores on hardware)
-__device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
-__device__ __forceinline__ float min3f(float a, float b, float c) { return __builtin_fminf(__builtin_fminf(a, b), c); }
 // row maximum of a lane's (masked) scores over NT tiles, both half-waves
 template <int NT>
 __device__ __forceinline__ float score_max(const f32x16 (&S)[NT]) {

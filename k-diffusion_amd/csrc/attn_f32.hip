@@ -21,10 +21,13 @@
 // The neighbourhood core (and, with KD_PREC_SPLIT3, the global / window cores) run on the bf16 MFMA with the 3-term split
 // of every fp32 operand (hi*hi + hi*lo + lo*hi, fp32 accumulate): see attn_na2d_kernel / attn_global_split_kernel below.
 #include "kd_common.h"
+#include "attn_geo.h"
 #include <cstdlib>
 #include <type_traits>
 
 namespace kd {
+
+using namespace geo;      // attn_geo.h: window modes and slot functions, neighbourhood tile, window start and halo origin
 
 constexpr int DH = 64;          // head dim (fixed: every config, k_diffusion/config.py:135-136)
 constexpr int LDS_ROW = DH + 4; // padded LDS row (floats)
@@ -50,10 +53,6 @@ __global__ __launch_bounds__(256) void qk_prep_kernel(float* qkv, const float* s
 }
 
 // ---- dense cores ------------------------------------------------------------------------------------
-// window modes carry log2(window_size) in the template value: 8x8 (the shipped config), 4x4, 16x16 windows
-enum { MODE_GLOBAL = 0, MODE_WINDOW = 1, MODE_WINDOW4 = 2, MODE_WINDOW16 = 3 };
-template <int MODE> struct WinLog2 { static constexpr int v = MODE == MODE_WINDOW ? 3 : (MODE == MODE_WINDOW4 ? 2 : 4); };
-
 struct DenseArgs {
   const float* qkv; float* out;
   const float* scale_h; const float* cos_t; const float* sin_t;
@@ -63,22 +62,7 @@ struct DenseArgs {
   int warm;                  // code warm-up workgroups (kd_common.h)
 };
 
-// slot -> token index inside the sample (or -1), for the problem owned by this block
-template <int MODE>
-__device__ __forceinline__ int slot_token(const DenseArgs& a, int slot, int wi, int wj) {
-  if (MODE == MODE_GLOBAL) return slot < a.T ? slot : -1;
-  constexpr int L = WinLog2<MODE>::v, WS = 1 << L;
-  const int ai = slot >> L, bj = slot & (WS - 1);
-  int i = wi * WS + ai - a.shift; if (i < 0) i += a.H;     // rolled[i] = orig[(i - shift) mod H]  (:274)
-  int j = wj * WS + bj - a.shift; if (j < 0) j += a.W;
-  return i * a.W + j;
-}
-// wrapped-region id of a window slot (make_shifted_window_masks, :285-316)
-template <int MODE>
-__device__ __forceinline__ int slot_region(int slot, int wi, int wj, int shift) {
-  constexpr int L = WinLog2<MODE>::v, WS = 1 << L;
-  return ((wi == 0 && (slot >> L) < shift) ? 2 : 0) + ((wj == 0 && (slot & (WS - 1)) < shift) ? 1 : 0);
-}
+// slot -> token index and wrapped-region id of a window slot: attn_geo.h (slots past the problem's last are -1 here)
 
 template <int MODE, int MAXT, bool PREP>
 __global__ __launch_bounds__(MAXT * 64) void attn_dense_kernel(const DenseArgs a) {
@@ -185,11 +169,11 @@ __global__ __launch_bounds__(MAXT * 64) void attn_dense_kernel(const DenseArgs a
   // The mask enters as an additive bias (0 / -inf) that is recomputed in both passes instead of a
   // select written back into S: hipcc (ROCm 7.2) miscompiles `S[t][r] = ok ? S[t][r] : -inf` on an
   // MFMA accumulator (it overwrites element 0's AGPR with -inf before the conditional copy).
-  const int q_region = (MODE != MODE_GLOBAL) ? slot_region<MODE>(q_slot, wi, wj, a.shift) : 0;
+  const int q_region = (MODE != MODE_GLOBAL) ? slot_region<MODE>(a.shift, q_slot, wi, wj) : 0;
   auto key_bias = [&](int t, int r) -> float {
     const int ks = t * 32 + mfma32_row(r, lane);
     bool ok = ks < n_slots;
-    if (MODE != MODE_GLOBAL && a.shift) ok = ok && (slot_region<MODE>(ks, wi, wj, a.shift) == q_region);
+    if (MODE != MODE_GLOBAL && a.shift) ok = ok && (slot_region<MODE>(a.shift, ks, wi, wj) == q_region);
     return ok ? 0.f : -INFINITY;
   };
   float m = -INFINITY;
@@ -274,7 +258,7 @@ struct NaArgs {
   int warm;                  // code warm-up workgroups (kd_common.h)
 };
 
-constexpr int NA_K = 7, NA_TH = 8, NA_TW = 16;
+constexpr int NA_K = 7;                                              // tile 8 x 16: attn_geo.h
 constexpr int NA_HR = NA_TH + NA_K - 1, NA_HC = NA_TW + NA_K - 1;    // 14 x 22 halo
 constexpr int NA_KEYS = NA_HR * NA_HC;                               // 308
 constexpr int NA_KROWS = 310;                                        // K image rows (a patch may poke 2 keys past the halo)
@@ -331,11 +315,7 @@ __global__ __launch_bounds__(256, 2) void attn_na2d_kernel(const NaArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, h2 = lane >> 5;
   const int wy_ = wid >> 1, wx_ = wid & 1;                            // this wave's 4x8 query block
-  const int tiles_x = (a.W + NA_TW - 1) / NA_TW, tiles_y = (a.H + NA_TH - 1) / NA_TH;
-  int r = KD_XCD_CHUNK();      // XCD-aware order: the halos of neighbouring tiles (2.4x re-read of K and V) hit ONE L2
-  const int tx = r % tiles_x; r /= tiles_x;
-  const int ty = r % tiles_y; r /= tiles_y;
-  const int head = r % a.nh; const int b = r / a.nh;
+  KD_NA_TILE(a, KD_XCD_CHUNK())      // tx, ty, head, b; XCD-aware order: the halos of neighbouring tiles (2.4x re-read of K and V) hit ONE L2
   const int T = a.H * a.W;
   const long row_stride = 3L * a.nh * DH;
   const float* base = a.qkv + (long)b * T * row_stride + head * DH;
@@ -364,10 +344,7 @@ __global__ __launch_bounds__(256, 2) void attn_na2d_kernel(const NaArgs a) {
   const char* kbase_c = reinterpret_cast<const char*>(base + a.nh * DH + 4 * c16);
   const char* vbase_c = reinterpret_cast<const char*>(base + 2 * a.nh * DH + 4 * c16);
   // ---- this lane's query (column l31 of its wave): 32 of its 64 dims, 8-wide chunks 2*step + h2 ----------------
-  const int qy_raw = ty0 + 4 * wy_ + (l31 >> 3), qx_raw = tx0 + 8 * wx_ + (l31 & 7);
-  const bool q_ok = qy_raw < a.H && qx_raw < a.W;
-  const int qy = min(qy_raw, a.H - 1), qx = min(qx_raw, a.W - 1);     // overhanging lanes shadow a real query, never store
-  const int q_tok = qy * a.W + qx;
+  KD_NA_QUERY(a, ty0, tx0, wy_, wx_, l31)      // q_ok, qy, qx, q_tok
   f32x4 qf[8];
   {
     const float* rp = base + (long)q_tok * row_stride;
@@ -445,9 +422,11 @@ __global__ __launch_bounds__(256, 2) void attn_na2d_kernel(const NaArgs a) {
     ql[st] = __builtin_bit_cast(bf16x8, u32x4{l0[0], l0[1], l1[0], l1[1]});
   }
 
-  // clamped window start (NATTEN semantics, dilation 1), relative to the halo origin; origin of this wave's 10x16 key
-  // patch (at the bottom / right border the halo is pulled in, so the patch is clamped into it; the column origin is
-  // rounded down to an even key so that the 8-byte V^T reads stay 4-byte aligned)
+  // clamped window start relative to the halo origin, and this wave's 10x16 key patch.  The patch origin is this kernel's OWN, not
+  // attn_geo.h's KD_NA_PATCH: at the bottom / right border the halo is pulled in, so the patch is clamped into it, and the column origin is
+  // rounded down to an even key so that the 8-byte V^T reads stay 4-byte aligned (hence the bound NA_HC - 14 of a 16-column patch).
+  // The clamps stay spelled with clampi: it is na_start / na_halo_origin (attn_geo.h) in the select form, equal for H, W >= 7, and with
+  // the header's max / min form every instance of this kernel gets another stream (profiles/attn_geometry_refactor.md).
   const int wy = clampi(qy - NA_K / 2, 0, a.H - NA_K) - hy0;
   const int wx = clampi(qx - NA_K / 2, 0, a.W - NA_K) - hx0;
   const int row_lo = min(clampi(min(ty0 + 4 * wy_, a.H - 1) - NA_K / 2, 0, a.H - NA_K) - hy0, NA_HR - 10);
@@ -793,7 +772,7 @@ __global__ __launch_bounds__(NT * 64) void attn_global_split_kernel(const DenseA
     }
   }
 
-  const int q_region = (MODE != MODE_GLOBAL) ? slot_region<MODE>(min(q_slot, T - 1), wi, wj, a.shift) : 0;
+  const int q_region = (MODE != MODE_GLOBAL) ? slot_region<MODE>(a.shift, min(q_slot, T - 1), wi, wj) : 0;
   // ---- softmax over keys (keys >= T masked by an additive -inf) ----------------------------------------------------------------------
   float m = -INFINITY;
 #pragma unroll
@@ -805,7 +784,7 @@ __global__ __launch_bounds__(NT * 64) void attn_global_split_kernel(const DenseA
       } else {
         if ((1 << (2 * WinLog2<MODE>::v)) < TP) S[t][i] += (t * 32 + mfma32_row(i, lane) < T) ? 0.f : -INFINITY;      // 4x4 windows: 16 of 32 slots
         // shifted windows: a key counts only if it lies in the query's wrapped region (:285-316)
-        if (a.shift) S[t][i] += (slot_region<MODE>(min(t * 32 + mfma32_row(i, lane), T - 1), wi, wj, a.shift) == q_region) ? 0.f : -INFINITY;
+        if (a.shift) S[t][i] += (slot_region<MODE>(a.shift, min(t * 32 + mfma32_row(i, lane), T - 1), wi, wj) == q_region) ? 0.f : -INFINITY;
       }
       m = fmaxf(m, S[t][i]);
     }
@@ -1242,9 +1221,7 @@ extern "C" int kd_attn_global_f32(const float* qkv, float* out, int batch, int T
 extern "C" int kd_attn_window_f32(const float* qkv, float* out, int batch, int H, int W, int nh, int ws, int shift, int prep,
                                   const float* scale_h, const float* cos_t, const float* sin_t, float eps, int precision, void* stream) {
   if (!qkv || !out || batch <= 0 || nh <= 0 || H <= 0 || W <= 0) return fail(KD_EINVAL, "kd_attn_window_f32: bad arguments");
-  if (ws != 4 && ws != 8 && ws != 16) return fail(KD_EINVAL, "kd_attn_window_f32: window_size %d unsupported (4, 8 or 16)", ws);
-  if ((H % ws) || (W % ws)) return fail(KD_EINVAL, "kd_attn_window_f32: grid %dx%d not divisible by the window", H, W);
-  if (shift < 0 || shift >= ws) return fail(KD_EINVAL, "kd_attn_window_f32: bad shift %d", shift);
+  if (int e = window_check("kd_attn_window_f32", H, W, ws, shift)) return e;
   if (int e = check_prep(prep, scale_h, cos_t, sin_t, "kd_attn_window_f32")) return e;
   DenseArgs a{qkv, out, scale_h, cos_t, sin_t, batch, H * W, nh, H, W, ws, shift, eps, code_warm()};
   const long nb = (long)batch * nh * (H / ws) * (W / ws);
@@ -1267,8 +1244,7 @@ extern "C" int kd_attn_na2d_f32(const float* qkv, float* out, int batch, int H, 
                                 const float* scale_h, const float* cos_t, const float* sin_t, float eps, int precision, void* stream) {
   (void)precision;
   if (!qkv || !out || batch <= 0 || nh <= 0) return fail(KD_EINVAL, "kd_attn_na2d_f32: bad arguments");
-  if (ks < 3 || ks > 13 || !(ks & 1)) return fail(KD_EINVAL, "kd_attn_na2d_f32: kernel_size %d unsupported (odd sizes 3 .. 13)", ks);
-  if (H < ks || W < ks) return fail(KD_EINVAL, "kd_attn_na2d_f32: grid %dx%d smaller than the %dx%d neighbourhood", H, W, ks, ks);
+  if (int e = na_check("kd_attn_na2d_f32", ks, H, W)) return e;
   if (int e = check_prep(prep, scale_h, cos_t, sin_t, "kd_attn_na2d_f32")) return e;
   hipStream_t s = (hipStream_t)stream;
   if (prep == 2) {        // operands stored split by the qkv projection: the round-3 cores (LDS-DMA halo, transposing V reads), every kernel size
@@ -1280,7 +1256,7 @@ extern "C" int kd_attn_na2d_f32(const float* qkv, float* out, int batch, int H, 
     return fail(KD_EINVAL, "kd_attn_na2d_f32: kernel_size %d needs split-stored operands (prep = 2, KdGemm.qkv_packed) and option attn_x3; "
                            "fp32 operands: kernel_size 7 only", ks);
   NaArgs a{qkv, out, scale_h, cos_t, sin_t, batch, H, W, nh, eps, code_warm()};
-  const long nb = (long)batch * nh * ((H + NA_TH - 1) / NA_TH) * ((W + NA_TW - 1) / NA_TW);
+  const long nb = na_tiles(batch, nh, H, W);
   const ProfName nm("attn_na2d", "attn_na2d %dx%d nh=%d", H, W, nh);
   LaunchScope prof(nm, 4.0 * batch * (double)H * W * nh * DH * ks * ks, 16.0 * batch * (double)H * W * nh * DH, s);
   const bool full = H >= NA_HR && W >= NA_HC;      // every halo key is inside the image

@@ -29,11 +29,7 @@ __global__ __launch_bounds__(256, NaGeo<KS>::LDS <= 80 * 1024 ? 2 : 1) void attn
   const int tid = threadIdx.x, lane = tid & 63, h2 = lane >> 5;
   const auto warm = code_warm_begin<10240>((int)blockIdx.x < a.warm && tid < 64);
   const x3::WgStamp wgs = x3::wg_stamp_begin(a.clk);
-  const int tiles_x = (a.W + NA_TW - 1) / NA_TW, tiles_y = (a.H + NA_TH - 1) / NA_TH;
-  int r = KD_XCD_CHUNK();      // XCD-aware order: neighbouring tiles (overlapping halos) run on ONE L2
-  const int tx = r % tiles_x; r /= tiles_x;
-  const int ty = r % tiles_y; r /= tiles_y;
-  const int head = r % a.nh, b = r / a.nh;
+  KD_NA_TILE(a, KD_XCD_CHUNK())      // tx, ty, head, b (attn_geo.h); XCD-aware order: neighbouring tiles (overlapping halos) run on ONE L2
   na2d_x3_tile<KS>(img, a, tid, b, head, ty, tx, [&]() { code_warm_end(warm); }, [&](bool q_ok, int q_tok, float l, const f32x16 (&O)[2]) {
     if (!q_ok) return;
     const float inv = 1.0f / l;
@@ -53,34 +49,22 @@ __global__ __launch_bounds__(256, NaGeo<KS>::LDS <= 80 * 1024 ? 2 : 1) void attn
 // more, so the patch is walked DENSELY as in attn_bf16.hip's form of these sizes: local key kl = 20 r + c (columns padded to 20, a
 // multiple of 4: the 4-key groups of the V^T reads never straddle two patch rows), tiles of 32 keys, every key's (row, column) by constant
 // division, validity per accumulator register from those.  One workgroup per CU (127 / 150 KiB of halo image: K and V still share it).
-template <int KS>
-struct NaWide {
-  static constexpr int HR = NA_TH + KS - 1, HC = NA_TW + KS - 1;
-  static constexpr int PR = 4 + KS - 1, PC = 20;                            // patch rows; padded patch width
-  static constexpr int NKT = (PR * PC + 31) / 32;
-  static constexpr int ROWS = ((HR * HC + 2 * PC + 3) / 4) * 4;             // slack: padded columns and the last tile's tail poke past the halo
-  static constexpr int LDS = ROWS * ROWB;
-  static_assert(8 + KS - 1 <= PC && LDS <= 160 * 1024, "patch width / LDS");
-};
+template <int KS> using NaWide = geo::NaWideX3<KS>;      // attn_geo.h
+static_assert(NaWide<11>::LDS == 130048 && NaWide<13>::LDS == 153600 && NaWide<13>::LDS <= 160 * 1024, "image sizes");
 
 template <int KS>
 __global__ __launch_bounds__(256, 1) void attn_na2d_x3_wide_kernel(const NArgs a) {
   using G = NaWide<KS>;
-  constexpr int HR = G::HR, HC = G::HC, PR = G::PR, PC = G::PC, NKT = G::NKT, ROWS = G::ROWS;
+  constexpr int HC = G::HC, NKT = G::NKT, ROWS = G::ROWS;
   extern __shared__ __attribute__((aligned(16))) char img[];
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, h2 = lane >> 5;
   const auto warm = code_warm_begin<16384>((int)blockIdx.x < a.warm && tid < 64);
   const int wy_ = wid >> 1, wx_ = wid & 1;
-  const int tiles_x = (a.W + NA_TW - 1) / NA_TW, tiles_y = (a.H + NA_TH - 1) / NA_TH;
-  int r = blockIdx.x;
-  const int tx = r % tiles_x; r /= tiles_x;
-  const int ty = r % tiles_y; r /= tiles_y;
-  const int head = r % a.nh, b = r / a.nh;
+  KD_NA_TILE(a, blockIdx.x)      // tx, ty, head, b
   const int T = a.H * a.W;
   const size_t row_bytes = (size_t)3 * a.nh * DH * 4;
   const char* base = reinterpret_cast<const char*>(a.qkv) + (size_t)b * T * row_bytes + head * (DH * 4);
-  const int ty0 = ty * NA_TH, tx0 = tx * NA_TW;
-  const int hy0 = max(0, min(ty0 - KS / 2, a.H - HR)), hx0 = max(0, min(tx0 - KS / 2, a.W - HC));
+  KD_NA_HALO(G, a, ty, tx)      // ty0, tx0, hy0, hx0
   // image row 4 pc + (lane >> 4) = halo position (row / HC, row % HC); rows past the halo (the slack) take a real token: outside every window
   auto stage = [&](int part_bytes) {
     for (int pc = wid; pc < ROWS / 4; pc += 4) {
@@ -91,10 +75,7 @@ __global__ __launch_bounds__(256, 1) void attn_na2d_x3_wide_kernel(const NArgs a
     }
   };
   stage(a.nh * DH * 4);                                  // K
-  const int qy_raw = ty0 + 4 * wy_ + (l31 >> 3), qx_raw = tx0 + 8 * wx_ + (l31 & 7);
-  const bool q_ok = qy_raw < a.H && qx_raw < a.W;
-  const int qy = min(qy_raw, a.H - 1), qx = min(qx_raw, a.W - 1);
-  const int q_tok = qy * a.W + qx;
+  KD_NA_QUERY(a, ty0, tx0, wy_, wx_, l31)      // q_ok, qy, qx, q_tok
   bf16x8 qh[4], ql[4];
   {
     const u32x4* qp = reinterpret_cast<const u32x4*>(base + (size_t)q_tok * row_bytes + 32 * h2);
@@ -105,12 +86,8 @@ __global__ __launch_bounds__(256, 1) void attn_na2d_x3_wide_kernel(const NArgs a
       ql[st] = __builtin_bit_cast(bf16x8, u32x4{c0[2], c0[3], c1[2], c1[3]});
     }
   }
-  const int wy = max(0, min(qy - KS / 2, a.H - KS)) - hy0, wx = max(0, min(qx - KS / 2, a.W - KS)) - hx0;
-  const int row_lo = min(max(0, min(min(ty0 + 4 * wy_, a.H - 1) - KS / 2, a.H - KS)) - hy0, HR - PR);
-  const int col_lo = min(max(0, min(min(tx0 + 8 * wx_, a.W - 1) - KS / 2, a.W - KS)) - hx0, HC - (8 + KS - 1));
-  const int korg = row_lo * HC + col_lo;
-  const int r0 = wy - row_lo, c0w = wx - col_lo;
-  auto img_row = [&](int kl) -> int { return min(korg + (kl / PC) * HC + (kl % PC), ROWS - 1); };     // image row of local key kl
+  KD_NA_PATCH(G, a, ty0, tx0, hy0, hx0, wy_, wx_, qy, qx)      // korg, r0, c0
+  auto img_row = [&](int kl) -> int { return min(geo::na_wide_row<G>(korg, kl), ROWS - 1); };     // image row of local key kl
   KD_WAIT_VM(0);
   code_warm_end(warm);
   KD_BARRIER();
@@ -146,9 +123,7 @@ __global__ __launch_bounds__(256, 1) void attn_na2d_x3_wide_kernel(const NArgs a
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int kl = 32 * t + (i & 3) + 8 * (i >> 2) + 4 * h2;
-      const int pr = kl / PC, pcn = kl % PC;
-      const bool valid = (unsigned)(pr - r0) < (unsigned)KS && (unsigned)(pcn - c0w) < (unsigned)KS && pr < PR;
-      S[t][i] = valid ? S[t][i] : -INFINITY;
+      S[t][i] = KD_NA_WIDE_VALID(G, kl, r0, c0) ? S[t][i] : -INFINITY;
     }
   float m = -INFINITY;
 #pragma unroll
@@ -398,7 +373,7 @@ template <int KS, bool WIDE>
 static int launch_na(const x3a::NArgs& a, hipStream_t s) {
   using namespace x3a;
   constexpr int lds = WIDE ? NaWide<(WIDE ? KS : 11)>::LDS : NaGeo<(WIDE ? 7 : KS)>::LDS;
-  const long nb = (long)a.batch * a.nh * ((a.H + NA_TH - 1) / NA_TH) * ((a.W + NA_TW - 1) / NA_TW);
+  const long nb = geo::na_tiles(a.batch, a.nh, a.H, a.W);
   const ProfName nm = KS == 7 ? ProfName("attn_na2d_x3", "attn_na2d_x3 %dx%d nh=%d", a.H, a.W, a.nh)
                               : ProfName("attn_na2d_x3", "attn_na2d_x3 k%d %dx%d nh=%d", KS, a.H, a.W, a.nh);
   LaunchScope prof(nm, 4.0 * a.batch * (double)a.H * a.W * a.nh * DH * KS * KS, 16.0 * a.batch * (double)a.H * a.W * a.nh * DH, s);

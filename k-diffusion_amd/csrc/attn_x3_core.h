@@ -3,6 +3,7 @@
 // tile in front of the fused out projection + feed-forward block.  See attn_x3.hip for what the core does and why.
 #pragma once
 #include "x3_common.h"
+#include "attn_geo.h"
 
 namespace kd {
 namespace x3a {
@@ -13,20 +14,13 @@ using b16::u32x2;
 using b16::u32x4;
 
 constexpr int DH = 64;
-constexpr int NA_TH = 8, NA_TW = 16;
+using geo::NA_TH;
+using geo::NA_TW;
 constexpr int ROWB = 256;                                    // bytes of an image row: 64 head dims as 16 chunks [hi4 | lo4]
-// geometry of kernel size KS (3 .. 9): a wave's 4 x 8 queries see a patch of (4 + KS - 1) rows x (8 + KS - 1) <= 16 columns
-template <int KS>
-struct NaGeo {
-  static constexpr int HR = NA_TH + KS - 1, HC = NA_TW + KS - 1;      // key halo of an 8 x 16 query tile (KS = 7: 14 x 22)
-  static constexpr int PR = 4 + KS - 1;                               // patch rows of a wave, 16 keys wide
-  static constexpr int NKT = (PR * 16 + 31) / 32;                     // key tiles of 32 (KS = 7: 5)
-  // image rows, 4 per LDS-DMA instruction: a patch may poke past the halo's last key -- the highest row a fragment read touches is
-  // (HR - 1) HC + (HC - (8 + KS - 1)) + 15 = HR HC - KS + 8
-  static constexpr int ROWS = ((HR * HC - KS + 9 + 3) / 4) * 4;
-  static constexpr int LDS = ROWS * ROWB;                             // KS = 7: 79 872 B, two workgroups per CU (3, 5 too; 9: one)
-  static_assert(8 + KS - 1 <= 16, "16-key patch rows");
-};
+// Image sizes of kernel size KS (3 .. 9), attn_geo.h: rows of 256 bytes, 4 per LDS-DMA instruction, ONE image for K, then V.
+// KS = 7: 79 872 B, two workgroups per CU (3, 5 too; 9: one)
+template <int KS> using NaGeo = geo::NaGeoX3<KS>;
+static_assert(NaGeo<3>::LDS == 48128 && NaGeo<5>::LDS == 62464 && NaGeo<7>::LDS == 79872 && NaGeo<9>::LDS == 98304, "image sizes");
 
 struct NArgs {
   const float* qkv; float* out;
@@ -35,11 +29,10 @@ struct NArgs {
   unsigned long long* clk;       // kd_prof_clock_buffer: per-workgroup entry / exit stamps (x3_common.h: wg_stamp_begin)
 };
 
-#define KD_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-
-__device__ __forceinline__ void glds16(const void* src, void* dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
+using b16::glds16;
+using b16::max3f;
+using b16::min3f;
+using b16::s16x4;
 
 // chunk c (0..15) of an image row sits at slot c ^ rsw(r), r = the row's index in the global core and in the 11 / 13 neighbourhood form, its
 // halo COLUMN in the neighbourhood kernel (sizes 3 .. 9).  rsw swaps the two 2-bit fields of r & 15: 16 consecutive rows (columns) take 16
@@ -49,14 +42,9 @@ __device__ __forceinline__ void glds16(const void* src, void* dst) {
 // masked.)
 __device__ __forceinline__ int rsw(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
-using s16x4 = short __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u32x2 tr_read(const char* img, int addr) {
   return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(img + addr)));
 }
-// v_min3_f32 / v_max3_f32 through the compiler's own patterns (hazards of MFMA results are the compiler's to pad)
-__device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
-__device__ __forceinline__ float min3f(float a, float b, float c) { return __builtin_fminf(__builtin_fminf(a, b), c); }
-
 
 // Tile (ty, tx) of (sample b, head), thread `tid` of the 256: K and V through the image `img` (NaGeo<KS>::LDS bytes), scores, softmax, O^T = V^T P^T.  `mid()` runs
 // once behind the first vector-memory wait (code warm-up), `sink(q_ok, q_tok, l, O)` takes the lane's unnormalised output (its query's
@@ -64,14 +52,13 @@ __device__ __forceinline__ float min3f(float a, float b, float c) { return __bui
 template <int KS, class Mid, class Sink>
 __device__ __forceinline__ void na2d_x3_tile(char* img, const NArgs& a, int tid, int b, int head, int ty, int tx, Mid&& mid, Sink&& sink) {
   using G = NaGeo<KS>;
-  constexpr int HR = G::HR, HC = G::HC, PR = G::PR, NKT = G::NKT, ROWS = G::ROWS;
+  constexpr int HC = G::HC, NKT = G::NKT, ROWS = G::ROWS;
   const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, h2 = lane >> 5;
   const int wy_ = wid >> 1, wx_ = wid & 1;
   const int T = a.H * a.W;
   const size_t row_bytes = (size_t)3 * a.nh * DH * 4;
   const char* base = reinterpret_cast<const char*>(a.qkv) + (size_t)b * T * row_bytes + head * (DH * 4);
-  const int ty0 = ty * NA_TH, tx0 = tx * NA_TW;
-  const int hy0 = max(0, min(ty0 - KS / 2, a.H - HR)), hx0 = max(0, min(tx0 - KS / 2, a.W - HC));
+  KD_NA_HALO(G, a, ty, tx)      // ty0, tx0, hy0, hx0 (attn_geo.h)
 
   // ---- halo rows -> image: image row 4 pc + (lane >> 4) = halo position (y, x), 16 rows per round of the 4 waves.  Rows past the halo's
   // last key and out-of-image positions (images smaller than the halo) take a real token: they lie outside every window.  The byte offsets of
@@ -98,10 +85,7 @@ __device__ __forceinline__ void na2d_x3_tile(char* img, const NArgs& a, int tid,
   };
   stage(a.nh * DH * 4);                                  // K
   // ---- this lane's query: B fragments of the 4 k-steps (head dims 16 st + 8 h2 .. + 7: chunks 4 st + 2 h2, + 1) --------------------------
-  const int qy_raw = ty0 + 4 * wy_ + (l31 >> 3), qx_raw = tx0 + 8 * wx_ + (l31 & 7);
-  const bool q_ok = qy_raw < a.H && qx_raw < a.W;
-  const int qy = min(qy_raw, a.H - 1), qx = min(qx_raw, a.W - 1);
-  const int q_tok = qy * a.W + qx;
+  KD_NA_QUERY(a, ty0, tx0, wy_, wx_, l31)      // q_ok, qy, qx, q_tok
   // Q operands per k-step: a stored chunk is [hi4 | lo4] of 4 head dims.  A K chunk goes into the MFMA AS IT IS READ (k-slots hi0..3, lo0..3 of
   // its 4 dims) against qa = [qhi0..3, qhi0..3] of the same dims: K_hi Q_hi + K_lo Q_hi of those dims in one instruction, no regrouping of the
   // K registers; the third term K_hi Q_lo takes the hi quads of both chunks (the only regrouped fragment: 4 moves per tile and step instead
@@ -117,22 +101,9 @@ __device__ __forceinline__ void na2d_x3_tile(char* img, const NArgs& a, int tid,
       ql[st] = __builtin_bit_cast(bf16x8, u32x4{c0[2], c0[3], c1[2], c1[3]});
     }
   }
-  // clamped window start (NATTEN: start = clamp(i - KS/2, 0, L - KS)) relative to the halo; patch origin of this wave
-  const int wy = max(0, min(qy - KS / 2, a.H - KS)) - hy0, wx = max(0, min(qx - KS / 2, a.W - KS)) - hx0;
-  const int row_lo = min(max(0, min(min(ty0 + 4 * wy_, a.H - 1) - KS / 2, a.H - KS)) - hy0, HR - PR);
-  const int col_lo = min(max(0, min(min(tx0 + 8 * wx_, a.W - 1) - KS / 2, a.W - KS)) - hx0, HC - (8 + KS - 1));
-  const int korg = row_lo * HC + col_lo;          // halo index of patch key (0, 0); local key 16 r + c is image row korg + HC r + c
-  // validity of patch column / patch row for THIS lane's query as +inf (inside the window) / -inf: v_min3 applies both at once.
-  // Accumulator register i of a tile holds local key (i & 3) + 8 (i >> 2) + 4 h2: column (i & 3) + 8 ((i >> 2) & 1) + 4 h2 of patch
-  // row 2 t + (i >> 3).
+  KD_NA_PATCH(G, a, ty0, tx0, hy0, hx0, wy_, wx_, qy, qx)      // col_lo, korg, r0, c0: this wave's patch, the lane's window inside it
   float colv[8], rowv[2 * NKT];
-  {
-    const int r0 = wy - row_lo, c0 = wx - col_lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) colv[j] = ((unsigned)((j & 3) + 8 * (j >> 2) + 4 * h2 - c0) < (unsigned)KS) ? INFINITY : -INFINITY;
-#pragma unroll
-    for (int p = 0; p < 2 * NKT; ++p) rowv[p] = ((unsigned)(p - r0) < (unsigned)KS) ? INFINITY : -INFINITY;
-  }
+  KD_NA_VALID_WORDS(KS, 2 * NKT, r0, c0, h2, colv, rowv)
   KD_WAIT_VM(0);
   mid();
   KD_BARRIER();
@@ -148,7 +119,7 @@ __device__ __forceinline__ void na2d_x3_tile(char* img, const NArgs& a, int tid,
   // instead of ~250 address instructions per wave)
   // The XOR part of an address (chunk pair of the k-step: bits 6 - 7, second chunk of the pair: bit 4) touches only bits below 8 and the tile
   // stride is a multiple of 256: (ka0 + t * stride) ^ m == (ka0 ^ m) + t * stride, so ONE base register per (k-step, chunk) serves every tile.
-  const int kr0 = korg + (l31 >> 4) * HC + (l31 & 15);
+  const int kr0 = KD_NA_K_ROW0(G, korg, l31);
   const int ka0 = kr0 * ROWB + (((2 * h2) ^ rsw(col_lo + (l31 & 15))) << 4);      // chunk 2 h2 of the row; chunk + 1: ^ 16; step st: ^ (st << 6)
 #pragma unroll
   for (int st = 0; st < 4; ++st) {
@@ -227,7 +198,7 @@ __device__ __forceinline__ void na2d_x3_tile(char* img, const NArgs& a, int tid,
   for (int e = 0; e < 2; ++e)
 #pragma unroll
     for (int i = 0; i < 16; ++i) O[e][i] = 0.f;
-  const int vr0 = korg + 4 * h2 + ((lane & 15) >> 2);
+  const int vr0 = geo::na_v_row0(korg, h2, (lane & 15) >> 2);
   const int vc = (lane & 3) + 4 * ((lane >> 4) & 1);
   const int va0 = vr0 * ROWB + ((vc ^ rsw(col_lo + 4 * h2 + ((lane & 15) >> 2))) << 4);
   // four base addresses (feature block e, rows / rows + 8): block e = 1: ^ 128; rows + 8: (^ 32) + 8 rows; the step (t, u) and the lo quad (+ 8)

@@ -143,6 +143,17 @@ __device__ __forceinline__ void qk_prep_blocks(f32x16& a0, f32x16& a1, float rs,
   for (int r = 0; r < 16; ++r) a1[r] *= g;
 }
 
+// ---- small pieces of the attention cores (bf16 and split3) ----------------------------------------------------------------------
+// 16 bytes per lane HBM -> LDS (global_load_lds): the wave's 64 pieces land lane-linear from the wave-uniform `dst`
+__device__ __forceinline__ void glds16(const void* src, void* dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+}
+using s16x4 = short __attribute__((ext_vector_type(4)));      // what ds_read_b64_tr_b16 returns
+// v_max3_f32 / v_min3_f32 through the compiler's own pattern (NOT inline asm: the hazard recogniser does not look inside asm
+// operands, and an asm VALU read of a just-written MFMA result misses its wait states -- seen as wrong scores on hardware)
+__device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
+__device__ __forceinline__ float min3f(float a, float b, float c) { return __builtin_fminf(__builtin_fminf(a, b), c); }
+
 // ---- synchronisation ------------------------------------------------------------------------------------------------------
 #define KD_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #define KD_BARRIER() asm volatile("s_barrier" ::: "memory")

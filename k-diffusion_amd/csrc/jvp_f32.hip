@@ -328,9 +328,7 @@ extern "C" int kd_attn_global_jvp_f32(const float* qkv, const float* qkv_dot, fl
 extern "C" int kd_attn_window_jvp_f32(const float* qkv, const float* qkv_dot, float* out, float* out_dot, int batch, int H, int W, int nh, int ws,
                                       int shift, void* stream) {
   if (!qkv || !qkv_dot || !out || !out_dot || batch <= 0 || H <= 0 || W <= 0 || nh <= 0) return fail(KD_EINVAL, "kd_attn_window_jvp_f32: bad arguments");
-  if (ws != 4 && ws != 8 && ws != 16) return fail(KD_EINVAL, "kd_attn_window_jvp_f32: window_size %d unsupported (4, 8 or 16)", ws);
-  if ((H % ws) || (W % ws)) return fail(KD_EINVAL, "kd_attn_window_jvp_f32: grid %dx%d not divisible by the window", H, W);
-  if (shift < 0 || shift >= ws) return fail(KD_EINVAL, "kd_attn_window_jvp_f32: bad shift %d", shift);
+  if (const int rc = geo::window_check("kd_attn_window_jvp_f32", H, W, ws, shift)) return rc;
   AttnJvpArgs a{qkv, qkv_dot, out, out_dot, batch, nh, H * W, H, W, ws, shift, (H / ws) * (W / ws) * (ws * ws / 16)};
   return launch_attn_jvp<KS_WINDOW>(a, "attn_window_jvp_f32", (hipStream_t)stream);
 }
@@ -338,8 +336,7 @@ extern "C" int kd_attn_window_jvp_f32(const float* qkv, const float* qkv_dot, fl
 extern "C" int kd_attn_na2d_jvp_f32(const float* qkv, const float* qkv_dot, float* out, float* out_dot, int batch, int H, int W, int nh, int ks,
                                     void* stream) {
   if (!qkv || !qkv_dot || !out || !out_dot || batch <= 0 || nh <= 0) return fail(KD_EINVAL, "kd_attn_na2d_jvp_f32: bad arguments");
-  if (ks < 3 || ks > 13 || !(ks & 1)) return fail(KD_EINVAL, "kd_attn_na2d_jvp_f32: kernel_size %d unsupported (odd sizes 3 .. 13)", ks);
-  if (H < ks || W < ks) return fail(KD_EINVAL, "kd_attn_na2d_jvp_f32: grid %dx%d smaller than the %dx%d neighbourhood", H, W, ks, ks);
+  if (const int rc = geo::na_check("kd_attn_na2d_jvp_f32", ks, H, W)) return rc;
   AttnJvpArgs a{qkv, qkv_dot, out, out_dot, batch, nh, H * W, H, W, ks, 0, ((H + 3) / 4) * ((W + 3) / 4)};
   return launch_attn_jvp<KS_NA>(a, "attn_na2d_jvp_f32", (hipStream_t)stream);
 }
