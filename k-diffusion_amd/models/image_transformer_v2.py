@@ -35,12 +35,9 @@ from .. import _native as nat
 from .. import ops
 from .. import weights
 from . import axial_rope
+from .cond_tables import ScaleTables
 
 D_HEAD = 64
-# Largest [steps, B, scale_width] scale table kept per sigma schedule (prefetch_schedule); longer schedules use the per-step chain.
-SCHEDULE_TABLE_MAX_BYTES = 1 << 30
-SCHEDULES_KEPT = 4            # a run of a two-stage solver hints two tables; older records (and their tensors) are dropped
-SCHEDULE_CHAINS_KEPT = 2      # conditioning workspaces kept per plan, by schedule length (least recently used dropped)
 DERIVED_KEPT = 1024  # weight-derived tensors kept per model (_derive: transposed weights, RoPE tables, ...): all dropped beyond that
 MAX_PLANS = 16     # cached launch plans (one per batch / size / conditioning kinds / device / arithmetic mode / switches) per model: least recently used beyond that
 # environment switches of the kernel routing (name, default): read in _plan_for, part of the plan key, passed to route_layer
@@ -445,26 +442,6 @@ class _CondChain:
                 nat.check(rc, ln.what)
 
 
-class _Schedule:
-    """Scale tables of a whole sigma schedule: rows of ``sigma_table`` ([n, B], one row per model call) -> tables[i]."""
-
-    def __init__(self, sigma_table, others, ident_others, tables, done):
-        self.base, self.version, (self.n, self.B) = weights.ident(sigma_table)
-        self.ident_others, self.tables, self.done = ident_others, tables, done
-        self.waited = set()       # streams (handles) that have waited for ``done`` once: everything they run later is ordered behind it
-        # the record keeps the hinted tensors alive, so their addresses cannot be handed to other tensors while it exists
-        self.keep = (sigma_table, others)
-
-    def row_of(self, sigma):
-        """Index of the table row ``sigma`` is a view of, or None."""
-        if sigma.dtype != torch.float32 or sigma.numel() != self.B or not sigma.is_contiguous() or weights.version(sigma) != self.version:
-            return None
-        off = sigma.data_ptr() - self.base
-        if off < 0 or off % (4 * self.B) or off // (4 * self.B) >= self.n:
-            return None
-        return off // (4 * self.B)
-
-
 class _Plan:
     """Workspace + prebuilt launch list for one (batch, H, W, conditioning-kinds) combination."""
 
@@ -521,15 +498,9 @@ class _Plan:
         if wcat is None or wcat.device != device:
             wcat = m._packed["ada_norm_wcat"] = torch.cat([mod.linear.weight.detach() for _, mod in norm_mods], dim=0).contiguous()
         self.wcat = wcat
-        # AdaRMSNorm scale tables, ping-pong: the main chain reads one while the next step's table is being written
-        self.scales = [torch.empty(B, total, **f32), torch.empty(B, total, **f32)]
         self.norm_descs = []                                # (descriptor or _ScaleRef, byte offset into a scale table)
-        self.last_buf, self.prefetched = 1, None            # prefetched: (identity of the conditioning tensors, table, done event)
-        self.side_stream = torch.cuda.Stream(device=device)
-        self.main_entry = torch.cuda.Event()
-        self.schedules, self.schedule_chains = [], {}       # conditioning of whole sigma schedules (prefetch_schedule); chains by length
-        self.scale_width = total
-        self.step_chain = self.build_cond(B)                # the per-step chain (inline, or one step ahead on the side stream)
+        self.scale_width = total                            # of a scale table row (laid out by ``table_offsets``)
+        self.tables = ScaleTables(B, total, device, self.build_cond)      # which table a call reads, and what fills it on which stream
 
         # ---- hourglass ------------------------------------------------------------------------
         L = self.launches
@@ -696,11 +667,6 @@ class _Plan:
             self._gemm(L, prefix + "down_proj", None, w_down, x, T, d, d_ff, epi=nat.EPI_RESIDUAL, residual=x, a_planes=hid8, mx8=True)
         else:
             self._gemm(L, prefix + "down_proj", self.hid, w_down, x, T, d, d_ff, epi=nat.EPI_RESIDUAL, residual=x)
-
-    def run_cond(self, buf, stream):
-        """Per-step conditioning chain into scale table ``buf`` on ``stream``; its inputs were filled by the caller on the
-        same stream (``step_chain.fill``)."""
-        self.step_chain.run(self.scales[buf].data_ptr(), stream)
 
     def run(self, x, out, sigma_data, base):
         """Main chain on the current stream.  x: input image (read by patch_in and, when preconditioning, by patch_out);
@@ -1081,42 +1047,14 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         x, _ = self._check_input(x, class_cond, mapping_cond, "ImageTransformerDenoiserModelV2")
         B, _, H, W = x.shape
         plan = self._plan_for(x, aug_cond, class_cond, create=True)
-        cur = torch.cuda.current_stream()
-        ident = self._cond_identity(sigma, aug_cond, class_cond, mapping_cond)
-        table, from_schedule = None, False
-        for sch in plan.schedules:                # this call's scales were computed with its whole sigma schedule
-            i = sch.row_of(sigma) if sch.ident_others == ident[1:] else None
-            if i is not None:
-                # the table was computed once, ahead of the loop, on the stream that was current in prefetch_schedule: ONE wait per
-                # (schedule, stream) orders every later forward on that stream behind it (a wait packet per forward cost ~3 us of idle
-                # queue each: profiles/r06_launch_gaps_*.txt)
-                if cur.cuda_stream not in sch.waited:
-                    cur.wait_event(sch.done)
-                    sch.waited.add(cur.cuda_stream)
-                table = sch.tables[i].data_ptr()
-                from_schedule = True
-                break
-        if table is None:
-            pre, plan.prefetched = plan.prefetched, None
-            if pre is not None and pre[0] == ident:
-                buf = pre[1]                      # this step's scale table was computed ahead of time on the side stream
-                cur.wait_event(pre[2])
-            else:
-                buf = 1 - plan.last_buf
-                if pre is not None:
-                    cur.wait_event(pre[2])        # an unused prefetch still owns the conditioning workspace: order behind it
-                plan.step_chain.fill(sigma, aug_cond, class_cond, mapping_cond)
-                plan.run_cond(buf, C.c_void_p(cur.cuda_stream))
-            plan.last_buf = buf
-            table = plan.scales[buf].data_ptr()
+        table = plan.tables.table_for(sigma, aug_cond, class_cond, mapping_cond)
         if sigma_data is not None:                # per-sample sigma of the preconditioning folded into patch-in / patch-out
             if sigma.numel() != B or sigma.dtype != torch.float32 or not sigma.is_contiguous() or sigma.device != x.device:
                 plan.sigma.copy_(sigma.reshape(-1).expand(B) if sigma.numel() == 1 else sigma.reshape(B), non_blocking=True)
                 plan.sigma_ptr = plan.sigma.data_ptr()
             else:
                 plan.sigma_ptr = sigma.data_ptr()  # read in place: freed storage is not reused before this stream's work is done
-        if not from_schedule:                     # (only the per-step side-stream chain of prefetch_conditioning waits on this event)
-            plan.main_entry.record(cur)           # everything before this step's main chain (incl. an inline conditioning chain)
+        plan.tables.mark_entry()                  # everything before this step's main chain (incl. an inline conditioning chain)
         out = torch.empty(B, self.out_channels, H, W, device=x.device, dtype=torch.float32)
         plan.run(x, out, sigma_data, table)
         return out
@@ -1174,9 +1112,6 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         return plan
 
     # ---- conditioning ahead of time ---------------------------------------------------------------
-    def _cond_identity(self, sigma, aug_cond, class_cond, mapping_cond):
-        return tuple(map(weights.ident, (sigma, aug_cond, class_cond, mapping_cond)))
-
     def _hint_usable(self, x_like, class_cond, mapping_cond):
         if not x_like.is_cuda or x_like.dim() != 4:
             return False
@@ -1195,37 +1130,14 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         if B != x_like.shape[0] or n == 0 or sigma_table.dtype != torch.float32 or not sigma_table.is_contiguous():
             return False
         plan = self._plan_for(x_like, aug_cond, class_cond, create=True)
-        if n * B * plan.scale_width * 4 > SCHEDULE_TABLE_MAX_BYTES:
-            return False
-        chain = plan.schedule_chains.pop(n, None)
-        if chain is None:
-            with torch.inference_mode(False):
-                chain = plan.build_cond(n * B)
-        plan.schedule_chains[n] = chain                   # most recently used last; older lengths (and their workspaces) are dropped
-        for old_n in list(plan.schedule_chains)[:-SCHEDULE_CHAINS_KEPT]:
-            del plan.schedule_chains[old_n]
-        cur = torch.cuda.current_stream()
-        for sch in plan.schedules:                # an earlier schedule's chain of the same length shares the work buffers
-            cur.wait_event(sch.done)
-        tables = torch.empty(n, B, plan.scale_width, device=sigma_table.device, dtype=torch.float32)
-        chain.fill(sigma_table, aug_cond, class_cond, mapping_cond, repeat=n)
-        chain.run(tables.data_ptr(), C.c_void_p(cur.cuda_stream))
-        done = torch.cuda.Event()
-        done.record(cur)
-        others = (aug_cond, class_cond, mapping_cond)
-        plan.schedules.append(_Schedule(sigma_table, others, self._cond_identity(None, *others)[1:], tables, done))
-        del plan.schedules[:-SCHEDULES_KEPT]
-        while len(plan.schedules) > 1 and sum(sc.tables.numel() * 4 for sc in plan.schedules) > SCHEDULE_TABLE_MAX_BYTES:
-            del plan.schedules[0]                          # all tables of a plan together stay below the bound of a single one
-        return True
+        return plan.tables.hint_schedule(sigma_table, aug_cond, class_cond, mapping_cond)
 
     def release_schedules(self):
         """Drop the scale tables (and the hinted tensors they keep alive) of finished runs: up to SCHEDULE_TABLE_MAX_BYTES of HBM
         per plan otherwise stay allocated until the next run replaces them.  Safe at any time: calls no table covers use the
         per-step chain, with the same bits."""
         for plan in self._plans.values():
-            plan.schedules.clear()
-            plan.schedule_chains.clear()
+            plan.tables.release()
 
     @torch.no_grad()
     def prefetch_conditioning(self, x_like, sigma, aug_cond=None, class_cond=None, mapping_cond=None):
@@ -1236,20 +1148,5 @@ class ImageTransformerDenoiserModelV2(nn.Module):
         if not self._hint_usable(x_like, class_cond, mapping_cond):
             return
         plan = self._plan_for(x_like, aug_cond, class_cond, create=False)
-        if plan is None or plan.prefetched is not None:
-            return
-        others = self._cond_identity(None, aug_cond, class_cond, mapping_cond)[1:]
-        if any(sch.ident_others == others and sch.row_of(sigma) is not None for sch in plan.schedules):
-            return
-        buf = 1 - plan.last_buf
-        side = plan.side_stream
-        side.wait_event(plan.main_entry)          # table `buf` and the conditioning workspace are free once the main chain of
-        with torch.cuda.stream(side):             # the step in flight has started (its predecessors are complete in stream order)
-            plan.step_chain.fill(sigma, aug_cond, class_cond, mapping_cond)
-            plan.run_cond(buf, C.c_void_p(side.cuda_stream))
-            done = torch.cuda.Event()
-            done.record(side)
-        # the record keeps the hinted tensors alive: while it is pending their storage cannot be freed and handed to another
-        # tensor, so a later call whose (address, version, shape) key matches really is the same data (a sampler aborted
-        # mid-loop leaves a record behind; the next run's schedule then necessarily lives at other addresses)
-        plan.prefetched = (self._cond_identity(sigma, aug_cond, class_cond, mapping_cond), buf, done, (sigma, aug_cond, class_cond, mapping_cond))
+        if plan is not None:
+            plan.tables.hint_next(sigma, aug_cond, class_cond, mapping_cond)

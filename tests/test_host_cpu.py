@@ -135,9 +135,9 @@ def test_schedule_rows_are_recognised_by_storage_and_version(KD):
     """prefetch_schedule bookkeeping (host logic, no GPU): a model call is served from a schedule's scale table only when its sigma
     argument IS a row of the hinted table -- same storage, same version counter, whole contiguous fp32 row."""
     from importlib import import_module
-    mod = import_module(KD.__name__ + ".models.image_transformer_v2")
+    mod = import_module(KD.__name__ + ".models.cond_tables")
     table = torch.linspace(80.0, 0.1, 6)[:, None].expand(6, 4).contiguous()
-    sch = mod._Schedule(table, (None, None, None), (None, None, None), torch.zeros(6, 4, 8), None)
+    sch = mod._Schedule(table, mod._Held(None, None, None), torch.zeros(6, 4, 8), None)
     assert [sch.row_of(table[i]) for i in range(6)] == list(range(6))
     assert sch.row_of(table[2].clone()) is None                       # same values, other storage
     assert sch.row_of(table[1, 1:]) is None and sch.row_of(table[:, 0]) is None and sch.row_of(table.view(-1)[2:6]) is None
@@ -152,7 +152,7 @@ def test_schedule_rows_are_recognised_by_storage_and_version(KD):
     # so such a table is simply not used and its calls take the per-step chain
     with torch.inference_mode():
         itab = torch.linspace(80.0, 0.1, 6)[:, None].expand(6, 4).contiguous()
-    isch = mod._Schedule(itab, (None, None, None), (None, None, None), torch.zeros(6, 4, 8), None)
+    isch = mod._Schedule(itab, mod._Held(None, None, None), torch.zeros(6, 4, 8), None)
     assert all(isch.row_of(itab[i]) is None for i in range(6))
     assert mod.weights.version(itab) != mod.weights.version(itab) and mod.weights.version(table) == mod.weights.version(table)
 
