@@ -37,7 +37,13 @@ __device__ __forceinline__ void mfma_acc_aa(const bf16x8 w) {
   asm volatile("v_mfma_f32_32x32x16_bf16 a[%c1:%c2], %0, a[%c3:%c4], a[%c1:%c2]" :: "v"(w), "i"(IDX), "i"(IDX + 15), "i"(BIDX), "i"(BIDX + 3) : KD_AGPR_ALL);
 }
 
-template <int NC /* K / 16: 8 or 16 */, bool OUTP = false /* K = 256: the attention block's out projection first (FArgs3.Att / Wo) */>
+// one LDS-DMA request of 16 bytes per lane (the instruction's own offset field stays 0, as everywhere in this library)
+__device__ __forceinline__ void glds16(const char* src, char* dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+}
+
+template <int NC /* K / 16: 8 or 16 */, bool OUTP = false /* K = 256: the attention block's out projection first (FArgs3.Att / Wo) */,
+          bool PROBE = false /* the time stamps of kd_prof_clock_buffer: their own instantiation, the tile loop of the other one is one basic block */>
 __global__ __launch_bounds__(256, 1) void ffn_x3_kernel(const FArgs3 p) {
   static_assert(!OUTP || NC == 16, "fused out projection: width 256 here, width 128 in ffn_x3h_kernel");
   constexpr int K = NC * 16, NKU = NC / 2;                      // ring stages of a tile's up projection
@@ -57,25 +63,41 @@ __global__ __launch_bounds__(256, 1) void ffn_x3_kernel(const FArgs3 p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const auto warm = code_warm_begin<(NC <= 8 ? 16 : 28) * 1024>((int)blockIdx.x < p.warm && tid < 64);
+  // (code sizes: 14 KiB at width 128, 23 KiB at width 256, 35 KiB with the out projection -- of which the warm-up's maximum covers 32)
+  const auto warm = code_warm_begin<(NC <= 8 ? 16 : OUTP ? 32 : 28) * 1024>((int)blockIdx.x < p.warm && tid < 64);
   const int m0 = blockIdx.x * 128;
   const int T = p.n_tiles, total = T * UNIT;
-  const bool probe = p.clk && blockIdx.x == (gridDim.x * 5) / 8 && tid == 0;      // a workgroup of a later round: the chip under load
+  const bool probe = PROBE && p.clk && blockIdx.x == (gridDim.x * 5) / 8 && tid == 0;      // a workgroup of a later round: the chip under load
   if (probe) { p.clk[0] = __builtin_amdgcn_s_memtime(); p.clk[1] = __builtin_amdgcn_s_memrealtime(); }
   const WgStamp wgs = wg_stamp_begin(p.clk);
 
   // The weight stream: tile t contributes UNIT stages -- u < NKU: up block (t, u); else down block (n-tile (u - NKU) / 2, k-step
-  // 2 t + (u - NKU) % 2).  Stage (t, u) sits in ring slot (t UNIT + u) % NSTG.  Requests past the end re-request the last stage (uniform
-  // 4 pieces per wave per stage: gemm_x3.hip).  `off` (compile-time where it matters) is relative to tile t's first stage, so that no
-  // run-time division is needed.
-  auto issue_rel = [&](int t, int off, int j) {
-    int tt = t + off / UNIT, u = off % UNIT;
-    if (tt >= T) { tt = T - 1; u = UNIT - 1; }
-    const char* src = (u < NKU ? p.Wu + ((size_t)tt * NKU + u) * STG
-                               : p.Wd + ((size_t)((u - NKU) >> 1) * (2 * T) + 2 * tt + ((u - NKU) & 1)) * STG) + wid * (PB * 1024) + lane * 16;
-    char* dst = smem + ((t * UNIT + off) % NSTG) * STG + wid * (PB * 1024);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + j * 1024),
-                                     (__attribute__((address_space(3))) void*)(dst + j * 1024), 16, 0, 0);
+  // 2 t + (u - NKU) % 2).  Stage (t, u) sits in ring slot (t UNIT + u) % NSTG.  Every wave issues exactly PB pieces per stage (the counted
+  // waits rest on it: gemm_x3.hip), past the end of the stream too: those re-request stages of the LAST tile, which nobody reads.
+  // A request is the scalar-base form of the load: the stage's address is wave-uniform (scalar arithmetic, a constant step from stage to
+  // stage), the lane's part -- the wave's 4 KiB of the stage, the piece's KiB, the lane's 16 bytes -- one 32-bit register per piece for
+  // the whole kernel, zero-extended by the instruction; the LDS destination (M0) is the slot's scalar + a constant.
+  unsigned voff[PB];
+#pragma unroll
+  for (int j = 0; j < PB; ++j) voff[j] = wid * (PB * 1024) + j * 1024 + lane * 16;
+  asm volatile("" : "+v"(voff[0]), "+v"(voff[1]), "+v"(voff[2]), "+v"(voff[3]));      // (opaque: four registers, not re-derived per request)
+  const int wring = wid * (PB * 1024);
+  auto glds4 = [&](const char* src /* wave-uniform */, int ring /* byte offset of the slot, wave-uniform */, auto j_) {
+    constexpr int j = decltype(j_)::value;
+    asm volatile("" : "+v"(voff[j]));                 // (the zero-extension stays in the request's own block, where instruction selection sees it)
+    glds16(src + voff[j], smem + ring + wring + j * 1024);
+  };
+  const size_t dstride = (size_t)(2 * T) * STG;       // from one n-tile of the down projection's image to the next
+  auto stage_src = [&](int tt, auto u_) -> const char* {
+    constexpr int u = decltype(u_)::value;
+    if constexpr (u < NKU) return p.Wu + ((size_t)tt * NKU + u) * STG;
+    else return p.Wd + (size_t)(2 * tt + ((u - NKU) & 1)) * STG + ((u - NKU) >> 1) * dstride;
+  };
+  // stage s (< NSTG) of the stream into slot s: the requests ahead of the tile loop (width 128: UNIT = 6, so stage 6 is tile 1's first)
+  auto issue_head = [&](auto s_, auto j_) {
+    constexpr int s = decltype(s_)::value;
+    const int tt = s < UNIT ? 0 : min(s / UNIT, T - 1);
+    glds4(stage_src(tt, std::integral_constant<int, s % UNIT>{}), s * STG, j_);
   };
 
   // ---- this wave's 32 rows -> a_hi / a_lo (the prologue of gemm_x3.hip) ---------------------------------------------------------------
@@ -116,10 +138,7 @@ __global__ __launch_bounds__(256, 1) void ffn_x3_kernel(const FArgs3 p) {
                                        (__attribute__((address_space(3))) void*)(stage + i * 1024), 16, 0, 0);
     }
     if constexpr (EARLY > 0) {                       // the first weight stages go to the slots no row borrows, behind the rows in the queue
-#pragma unroll
-      for (int s = 0; s < EARLY; ++s)
-#pragma unroll
-        for (int j = 0; j < PB; ++j) issue_rel(0, s, j);
+      static_for<EARLY>([&](auto s_) { static_for<PB>([&](auto j_) { issue_head(s_, j_); }); });
       wait_vm(PB * EARLY);
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -186,29 +205,20 @@ __global__ __launch_bounds__(256, 1) void ffn_x3_kernel(const FArgs3 p) {
   // OUTP: the stream starts with Wo's 2 NKU stages ([n-tile of 128 out rows][32-k stage], plain layout): twice round the ring, so the
   // block's own stages keep their ring positions
   constexpr int NWO = OUTP ? 2 * NKU : 0;
-  auto issue_wo = [&](int q, int j) {
-    const char* src = p.Wo + (size_t)q * STG + wid * (PB * 1024) + j * 1024 + lane * 16;
-    char* dst = smem + (q % NSTG) * STG + wid * (PB * 1024) + j * 1024;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-  };
-  if constexpr (OUTP) {
-#pragma unroll
-    for (int q = 0; q < PDIST; ++q)
-#pragma unroll
-      for (int j = 0; j < PB; ++j) issue_wo(q, j);
-  } else {
-#pragma unroll
-    for (int s = EARLY; s < PDIST; ++s)
-#pragma unroll
-      for (int j = 0; j < PB; ++j) issue_rel(0, s, j);
-  }
+  auto issue_wo = [&](auto q_, auto j_) { glds4(p.Wo + (size_t)decltype(q_)::value * STG, (decltype(q_)::value % NSTG) * STG, j_); };
+  static_for<PDIST - EARLY>([&](auto s_) {
+    constexpr std::integral_constant<int, decltype(s_)::value + EARLY> q{};
+    static_for<PB>([&](auto j_) {
+      if constexpr (OUTP) issue_wo(q, j_);
+      else issue_head(q, j_);
+    });
+  });
   if (probe) p.clk[4] = __builtin_amdgcn_s_memtime();
 
   const int o0 = swz64(l31, lh), o1 = swz64(l31, 2 + lh);
   f32x16 acc[4];
   bf16x8 wh[2][4], wl[2][4];
-  auto read_frags = [&](int slot, int h, bf16x8 (&fh)[4], bf16x8 (&fl)[4]) {
-    const char* st = smem + slot * STG + (h ? o1 : o0);
+  auto read_frags = [&](const char* st, bf16x8 (&fh)[4], bf16x8 (&fl)[4]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       fh[j] = *reinterpret_cast<const bf16x8*>(st + j * 32 * 64);
@@ -222,26 +232,26 @@ __global__ __launch_bounds__(256, 1) void ffn_x3_kernel(const FArgs3 p) {
   };
   wait_vm(PB * (PDIST - 1));
   KD_BARRIER();
-  read_frags(0, 0, wh[0], wl[0]);
+  read_frags(smem + o0, wh[0], wl[0]);
+  constexpr std::integral_constant<int, 0> I0{};
+  constexpr std::integral_constant<int, 1> I1{};
+  constexpr std::integral_constant<int, 2> I2{};
+  constexpr std::integral_constant<int, 3> I3{};
   if constexpr (OUTP) {
     // ================= out projection: x (in the output accumulators) += att Wo^T, 2 n-tiles x NKU stages of 24 MFMAs ======================
-    constexpr std::integral_constant<int, 0> I0{};
-    constexpr std::integral_constant<int, 1> I1{};
-    constexpr std::integral_constant<int, 2> I2{};
-    constexpr std::integral_constant<int, 3> I3{};
     static_for<NWO>([&](auto q_) {
       constexpr int q = decltype(q_)::value, ntile = q / NKU, ks = q % NKU;
       auto oo = [&](auto b_, auto j_, bool w_lo, auto al_) {
         constexpr int b = decltype(b_)::value, j = decltype(j_)::value, al = decltype(al_)::value, c = 2 * ks + b;
         mfma_acc_aa<AO + 16 * (4 * ntile + j), 8 * c + 4 * al>(w_lo ? wl[b][j] : wh[b][j]);
       };
-      auto request = [&](int j) {                      // stream position q + PDIST: Wo's later stages, then the block's first ones
-        if constexpr (q + PDIST < NWO) issue_wo(q + PDIST, j);
-        else issue_rel(0, q + PDIST - NWO, j);
+      auto request = [&](auto j_) {                    // stream position q + PDIST: Wo's later stages, then the block's first ones
+        if constexpr (q + PDIST < NWO) issue_wo(std::integral_constant<int, q + PDIST>{}, j_);
+        else issue_head(std::integral_constant<int, (q + PDIST >= NWO ? q + PDIST - NWO : 0)>{}, j_);
       };
       oo(I0, I0, true, I0);
       __builtin_amdgcn_sched_barrier(0);
-      read_frags(q % NSTG, 1, wh[1], wl[1]);
+      read_frags(smem + (q % NSTG) * STG + o1, wh[1], wl[1]);
       __builtin_amdgcn_sched_barrier(0);
       oo(I0, I1, true, I0); oo(I0, I2, true, I0); oo(I0, I3, true, I0);
       oo(I0, I0, false, I1); oo(I0, I1, false, I1); oo(I0, I2, false, I1); oo(I0, I3, false, I1);
@@ -250,19 +260,19 @@ __global__ __launch_bounds__(256, 1) void ffn_x3_kernel(const FArgs3 p) {
       next_stage_in();
       oo(I1, I0, true, I0);
       __builtin_amdgcn_sched_barrier(0);
-      read_frags((q + 1) % NSTG, 0, wh[0], wl[0]);
+      read_frags(smem + ((q + 1) % NSTG) * STG + o0, wh[0], wl[0]);
       __builtin_amdgcn_sched_barrier(0);
       oo(I1, I1, true, I0); oo(I1, I2, true, I0);
-      request(0);
+      request(I0);
       __builtin_amdgcn_sched_barrier(0);
       oo(I1, I3, true, I0); oo(I1, I0, false, I1); oo(I1, I1, false, I1);
-      request(1);
+      request(I1);
       __builtin_amdgcn_sched_barrier(0);
       oo(I1, I2, false, I1); oo(I1, I3, false, I1); oo(I1, I0, false, I0);
-      request(2);
+      request(I2);
       __builtin_amdgcn_sched_barrier(0);
       oo(I1, I1, false, I0); oo(I1, I2, false, I0);
-      request(3);
+      request(I3);
       oo(I1, I3, false, I0);
       __builtin_amdgcn_sched_barrier(0);
     });
@@ -299,16 +309,42 @@ __global__ __launch_bounds__(256, 1) void ffn_x3_kernel(const FArgs3 p) {
   }
   const float rsh = 0.5f * rs;
 
+  // The tile body is straight-line code: every ring position in it is a constant relative to `ring0`, the byte offset of the slot of the
+  // tile's first stage.  Width 256: UNIT = 12 stages on a ring of 8, so a tile starts at slot 0 or 4 in turn -- the ring is two halves,
+  // A (the tile's stages 0..3 and 8..11) and B (4..7, and the next tile's first), swapped from tile to tile by one XOR: the LDS reads
+  // take 4 address registers (half x chunk pair) and immediate offsets, the requests' destinations one scalar + a constant.
+  // Width 128: UNIT = 6, four starting slots in turn; `ring0` steps through them and the slot is one scalar AND away.
+  constexpr int RING = NSTG * STG, HALFR = RING / 2;
+  constexpr bool TOG = UNIT % (NSTG / 2) == 0 && (UNIT / (NSTG / 2)) % 2 == 1;
+  int ring0 = 0;
+  int ra[2] = {o0, o1}, rb[2] = {o0 + HALFR, o1 + HALFR};     // TOG: read addresses of the halves' first slots
+  auto ring_of = [&](auto i_) -> int {                // slot (byte offset) of stage i of the stream, counted from the tile's first
+    constexpr int i = decltype(i_)::value;
+    if constexpr (TOG) return (((i >> 2) & 1) ? ring0 ^ HALFR : ring0) + (i & 3) * STG;
+    else return (ring0 + i * STG) & (RING - 1);
+  };
+  auto frag_ptr = [&](auto i_, int h) -> const char* {
+    constexpr int i = decltype(i_)::value;
+    if constexpr (TOG) return smem + (((i >> 2) & 1) ? rb[h] : ra[h]) + (i & 3) * STG;
+    else return smem + ring_of(i_) + (h ? o1 : o0);
+  };
   for (int t = 0; t < T; ++t) {
-    const int sbase = t * UNIT;
-    const int slot0 = sbase % NSTG;                   // ring slot of the tile's first stage (UNIT is not a multiple of NSTG at K = 128)
-    if (probe && t == 2) p.clk[8] = __builtin_amdgcn_s_memtime();
+    // stage `off` (>= PDIST) behind the tile's first: a later stage of this tile or a stage of one of the next two; past the last tile
+    // the same stage of the last tile again (a real stage of the images, requested into a slot nobody reads any more)
+    auto request = [&](auto off_, auto j_) {
+      constexpr int off = decltype(off_)::value, d = off / UNIT;
+      const int tt = d == 0 ? t : min(t + d, T - 1);
+      glds4(stage_src(tt, std::integral_constant<int, off % UNIT>{}), ring_of(off_), j_);
+    };
+    if constexpr (PROBE) { if (probe && t == 2) p.clk[8] = __builtin_amdgcn_s_memtime(); }
     // (no zeroing of the accumulators: the first MFMA of each chain takes the constant 0 as its C operand -- 64 v_mov per tile less, and
     // no v_mov -> SrcC hazard, which the compiler pads for its own MFMAs only)
     // ================= up projection of tile t: value / gate accumulators of its 2 x 32 hidden features (K / 32 stages) =================
     static_for<NKU>([&](auto ks_) {
       constexpr int ks = decltype(ks_)::value;
-      const int slot = (slot0 + ks) % NSTG, nslot = (slot0 + ks + 1) % NSTG;
+      constexpr std::integral_constant<int, ks> SI{};
+      constexpr std::integral_constant<int, ks + 1> SN{};
+      constexpr std::integral_constant<int, ks + PDIST> SR{};
       auto mm = [&](auto b_, int j, bool w_lo, auto a_lo_) {
         constexpr int b = decltype(b_)::value, al = decltype(a_lo_)::value, c = 2 * ks + b;
         const bf16x8& w = w_lo ? wl[b][j] : wh[b][j];
@@ -321,11 +357,9 @@ __global__ __launch_bounds__(256, 1) void ffn_x3_kernel(const FArgs3 p) {
           else mfma_vv(acc[j], w, al ? a_lo[c] : a_hi[c]);
         }
       };
-      constexpr std::integral_constant<int, 0> I0{};
-      constexpr std::integral_constant<int, 1> I1{};
       mm(I0, 0, true, I0);
       __builtin_amdgcn_sched_barrier(0);
-      read_frags(slot, 1, wh[1], wl[1]);
+      read_frags(frag_ptr(SI, 1), wh[1], wl[1]);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 1; j < 4; ++j) mm(I0, j, true, I0);
@@ -337,31 +371,33 @@ __global__ __launch_bounds__(256, 1) void ffn_x3_kernel(const FArgs3 p) {
       next_stage_in();
       mm(I1, 0, true, I0);
       __builtin_amdgcn_sched_barrier(0);
-      read_frags(nslot, 0, wh[0], wl[0]);
+      read_frags(frag_ptr(SN, 0), wh[0], wl[0]);
       __builtin_amdgcn_sched_barrier(0);
       mm(I1, 1, true, I0);
       mm(I1, 2, true, I0);
-      issue_rel(t, ks + PDIST, 0);
+      request(SR, I0);
       __builtin_amdgcn_sched_barrier(0);
       mm(I1, 3, true, I0);
       mm(I1, 0, false, I1);
       mm(I1, 1, false, I1);
-      issue_rel(t, ks + PDIST, 1);
+      request(SR, I1);
       __builtin_amdgcn_sched_barrier(0);
       mm(I1, 2, false, I1);
       mm(I1, 3, false, I1);
       mm(I1, 0, false, I0);
-      issue_rel(t, ks + PDIST, 2);
+      request(SR, I2);
       __builtin_amdgcn_sched_barrier(0);
       mm(I1, 1, false, I0);
       mm(I1, 2, false, I0);
-      issue_rel(t, ks + PDIST, 3);
+      request(SR, I3);
       mm(I1, 3, false, I0);
       __builtin_amdgcn_sched_barrier(0);
     });
     asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));      // asm MFMA results -> vector reads
-    if (probe && t == 0) p.clk[5] = __builtin_amdgcn_s_memtime();
-    if (probe && t == 2) p.clk[9] = __builtin_amdgcn_s_memtime();
+    if constexpr (PROBE) {
+      if (probe && t == 0) p.clk[5] = __builtin_amdgcn_s_memtime();
+      if (probe && t == 2) p.clk[9] = __builtin_amdgcn_s_memtime();
+    }
 
     // ================= GEGLU in the lane that owns the row -> hi / lo B-operand fragments of the 4 hidden 16-chunks ======================
     // chunk c' = 2 jj + (g >> 1) of the tile; the lane's 8 values of it are accumulator registers 8 (c' & 1) .. + 7 of blocks (2 jj, 2 jj + 1),
@@ -393,26 +429,24 @@ __global__ __launch_bounds__(256, 1) void ffn_x3_kernel(const FArgs3 p) {
     // 0, 1, 4, 5 of every tile's first chunk on the first try)
     asm volatile("s_nop 7" : "+v"(hf_hi[0]), "+v"(hf_hi[1]), "+v"(hf_hi[2]), "+v"(hf_hi[3]), "+v"(hf_lo[0]), "+v"(hf_lo[1]), "+v"(hf_lo[2]), "+v"(hf_lo[3]));
     __builtin_amdgcn_sched_barrier(0);
-    if (probe && t == 2) p.clk[10] = __builtin_amdgcn_s_memtime();
+    if constexpr (PROBE) { if (probe && t == 2) p.clk[10] = __builtin_amdgcn_s_memtime(); }
 
     // ================= down projection: k-steps 2 t, 2 t + 1 (64 hidden features) into the row's K output features ========================
     // stage v = 2 nt + kk: output n-tile nt (4 blocks of 32), hidden chunks 2 kk, 2 kk + 1
     static_for<NKD>([&](auto v_) {
       constexpr int v = decltype(v_)::value, ntile = v >> 1, kk = v & 1;
-      const int slot = (slot0 + NKU + v) % NSTG, nslot = (slot0 + NKU + v + 1) % NSTG;
+      constexpr std::integral_constant<int, NKU + v> SI{};
+      constexpr std::integral_constant<int, NKU + v + 1> SN{};
+      constexpr std::integral_constant<int, NKU + v + PDIST> SR{};
       auto dd = [&](auto b_, auto j_, bool w_lo, bool h_lo) {
         constexpr int b = decltype(b_)::value, j = decltype(j_)::value;
         const bf16x8& w = w_lo ? wl[b][j] : wh[b][j];
         const bf16x8& h = h_lo ? hf_lo[2 * kk + b] : hf_hi[2 * kk + b];
         mfma_acc_ag<AO + 16 * (4 * ntile + j)>(w, h);
       };
-      constexpr std::integral_constant<int, 0> I0{};
-      constexpr std::integral_constant<int, 1> I1{};
-      constexpr std::integral_constant<int, 2> I2{};
-      constexpr std::integral_constant<int, 3> I3{};
       dd(I0, I0, true, false);
       __builtin_amdgcn_sched_barrier(0);
-      read_frags(slot, 1, wh[1], wl[1]);
+      read_frags(frag_ptr(SI, 1), wh[1], wl[1]);
       __builtin_amdgcn_sched_barrier(0);
       dd(I0, I1, true, false); dd(I0, I2, true, false); dd(I0, I3, true, false);
       dd(I0, I0, false, true); dd(I0, I1, false, true); dd(I0, I2, false, true); dd(I0, I3, false, true);
@@ -421,24 +455,34 @@ __global__ __launch_bounds__(256, 1) void ffn_x3_kernel(const FArgs3 p) {
       next_stage_in();
       dd(I1, I0, true, false);
       __builtin_amdgcn_sched_barrier(0);
-      read_frags(nslot, 0, wh[0], wl[0]);
+      read_frags(frag_ptr(SN, 0), wh[0], wl[0]);
       __builtin_amdgcn_sched_barrier(0);
       dd(I1, I1, true, false); dd(I1, I2, true, false);
-      issue_rel(t, NKU + v + PDIST, 0);
+      request(SR, I0);
       __builtin_amdgcn_sched_barrier(0);
       dd(I1, I3, true, false); dd(I1, I0, false, true); dd(I1, I1, false, true);
-      issue_rel(t, NKU + v + PDIST, 1);
+      request(SR, I1);
       __builtin_amdgcn_sched_barrier(0);
       dd(I1, I2, false, true); dd(I1, I3, false, true); dd(I1, I0, false, false);
-      issue_rel(t, NKU + v + PDIST, 2);
+      request(SR, I2);
       __builtin_amdgcn_sched_barrier(0);
       dd(I1, I1, false, false); dd(I1, I2, false, false);
-      issue_rel(t, NKU + v + PDIST, 3);
+      request(SR, I3);
       dd(I1, I3, false, false);
       __builtin_amdgcn_sched_barrier(0);
     });
-    if (probe && t == 0) p.clk[6] = __builtin_amdgcn_s_memtime();
-    if (probe && t == 2) p.clk[11] = __builtin_amdgcn_s_memtime();
+    if constexpr (PROBE) {
+      if (probe && t == 0) p.clk[6] = __builtin_amdgcn_s_memtime();
+      if (probe && t == 2) p.clk[11] = __builtin_amdgcn_s_memtime();
+    }
+    // the next tile's first slot
+    if constexpr (TOG) {
+      ring0 ^= HALFR;
+      ra[0] ^= HALFR; ra[1] ^= HALFR; rb[0] ^= HALFR; rb[1] ^= HALFR;
+      asm volatile("" : "+v"(ra[0]), "+v"(ra[1]), "+v"(rb[0]), "+v"(rb[1]));      // (four registers, not re-derived per read)
+    } else {
+      ring0 = (ring0 + UNIT * STG) & (RING - 1);
+    }
   }
   if (probe) p.clk[12] = __builtin_amdgcn_s_memtime();
   // ---- + x, store: out accumulators from the AccVGPRs, the row's x read again (fp32), through the wave's store strip -------------------
@@ -526,13 +570,16 @@ static int launch_ffn_half(const FArgs3& a, const char* nm, double flops, double
   return check_launch("kd_ffn_f32");
 }
 
-template <int NC, bool OUTP = false>
+template <int NC, bool OUTP = false, bool PROBE = false>
 static int launch_ffn(const FArgs3& a, const char* nm, double flops, double bytes, hipStream_t s) {
+  // (the in-kernel time stamps of kd_prof_clock_buffer are their own instantiation: run-time `if (probe)` blocks split the tile loop into
+  // several basic blocks -- gemm_x3r.hip)
+  if constexpr (!PROBE) { if (a.clk) return launch_ffn<NC, OUTP, true>(a, nm, flops, bytes, s); }
   constexpr int K = NC * 16;
   constexpr int LDS = 8 * STG + 4 * (K * 4 < 1024 ? 1024 : K * 4) + 4 * 2048;
   const CfgName cfg(nm, "half0");
   LaunchScope prof(cfg, flops, bytes, s);
-  launch<ffn_x3_kernel<NC, OUTP>>(dim3((unsigned)((a.M + 127) / 128)), dim3(256), LDS, s, a);
+  launch<ffn_x3_kernel<NC, OUTP, PROBE>>(dim3((unsigned)((a.M + 127) / 128)), dim3(256), LDS, s, a);
   return check_launch("kd_ffn_f32");
 }
 
