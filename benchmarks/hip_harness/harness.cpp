@@ -969,12 +969,6 @@ int main(int argc, char** argv) {
         {"astat ragged geglu", 1000, 192, 256, KD_EPI_GEGLU, 1, 50, 0},
     };
     for (const auto& c : ca) run_gemm_case(c);
-    for (int rows : {128, 256, 128, 256}) {
-      kd_set_option("astat_rows", rows);
-      printf("-- astat_rows = %d\n", rows);
-      for (int i = 0; i < 5; ++i) run_gemm_case(ca[i]);
-    }
-    kd_set_option("astat_rows", 0);
     for (int sp : {1, 2, 3, 6}) {
       kd_set_option("astat_splits", sp);
       printf("-- astat_splits = %d\n", sp);
@@ -1004,67 +998,25 @@ int main(int argc, char** argv) {
       for (const auto& c : ct) run_gemm_case(c);
     }
     kd_set_option("tiled_bm", 0);
-    for (int deep : {0, 1, 0, 1}) {
-      kd_set_option("tiled_deep", deep);
-      printf("-- tiled_deep = %d (4-slot ring for grids of at most one tile per CU)\n", deep);
-      const GemmCase cd[] = {
-          {"tiled L2 out+res", 8192, 512, 512, KD_EPI_RESIDUAL, 0, 256, 0},
-          {"tiled L2 down+res", 8192, 512, 1536, KD_EPI_RESIDUAL, 0, 256, 0},
-          {"tiled merge1", 8192, 512, 1024, KD_EPI_STORE, 0, 256, 0, KD_A_MERGE2x2, 16, 16},
-          {"tiled ragged res", 300, 160, 64, KD_EPI_RESIDUAL, 0, 300, 0},
-          {"tiled small K", 2000, 128, 64, KD_EPI_STORE, 0, 2000, 0},
-      };
-      for (const auto& c : cd) run_gemm_case(c);
-    }
-    kd_set_option("tiled_deep", 0);
+    printf("-- tiled_bm = 0 (per shape), wstat off\n");
+    const GemmCase cd[] = {
+        {"tiled L2 out+res", 8192, 512, 512, KD_EPI_RESIDUAL, 0, 256, 0},
+        {"tiled L2 down+res", 8192, 512, 1536, KD_EPI_RESIDUAL, 0, 256, 0},
+        {"tiled merge1", 8192, 512, 1024, KD_EPI_STORE, 0, 256, 0, KD_A_MERGE2x2, 16, 16},
+        {"tiled ragged res", 300, 160, 64, KD_EPI_RESIDUAL, 0, 300, 0},
+        {"tiled small K", 2000, 128, 64, KD_EPI_STORE, 0, 2000, 0},
+    };
+    for (const auto& c : cd) run_gemm_case(c);
     kd_set_option("wstat", 1);
   }
-  if (want("prefetch")) {
-    for (int pf : {0, 1, 2, 6}) {
-      kd_set_option("wstat_prefetch", pf & 3);
-      kd_set_option("wstat_waves", pf == 6 ? 4 : 0);
-      printf("-- wstat_prefetch = %d\n", pf);
-      const GemmCase cw[] = {
-          {"prefetch L0 qkv", 131072, 384, 128, KD_EPI_QKV, 1, 4096, 2},
-          {"prefetch L0 geglu", 131072, 384, 128, KD_EPI_GEGLU, 1, 4096, 0},
-          {"prefetch L0 out+res", 131072, 128, 128, KD_EPI_RESIDUAL, 0, 4096, 0},
-          {"prefetch L0 down+res", 131072, 128, 384, KD_EPI_RESIDUAL, 0, 4096, 0},
-          {"prefetch ragged qkv", 4128, 384, 128, KD_EPI_QKV, 1, 96, 2},
-      };
-      for (const auto& c : cw) run_gemm_case(c);
-    }
-    kd_set_option("wstat_prefetch", 0);
-    kd_set_option("wstat_waves", 0);
-  }
-  if (want("waves")) {
-    for (int w : {4, 12}) {
-      kd_set_option("wstat_waves", w);
-      printf("-- wstat_waves = %d\n", w);
-      const GemmCase cw[] = {
-          {"waves L0 qkv", 131072, 384, 128, KD_EPI_QKV, 1, 4096, 2},
-          {"waves L0 geglu", 131072, 384, 128, KD_EPI_GEGLU, 1, 4096, 0},
-          {"waves L1 qkv", 32768, 768, 256, KD_EPI_QKV, 1, 1024, 4},
-          {"waves L1 geglu", 32768, 768, 256, KD_EPI_GEGLU, 1, 1024, 0},
-          {"waves L2 qkv", 8192, 1536, 512, KD_EPI_QKV, 1, 256, 8},
-          {"waves L2 geglu", 8192, 1536, 512, KD_EPI_GEGLU, 1, 256, 0},
-      };
-      for (const auto& c : cw) run_gemm_case(c);
-    }
-    kd_set_option("wstat_waves", 0);
-  }
-  for (int v : {1, 3}) {
-    kd_set_option("ffn_variant", v);
-    if (want("ffn")) printf("-- ffn_variant = %d\n", v);
-    run_ffn_case("ffn L0", 131072, 128, 384, 4096);
-    run_ffn_case("ffn ragged", 4128 + 77, 128, 448, 96);
-    run_ffn_case("ffn tiny", 37, 128, 64, 37);
-    run_ffn_case("ffn L1 (K=256)", 32768, 256, 768, 1024);
-    run_ffn_case("ffn K=256 ragged", 1000 + 77, 256, 192, 96);
-    run_ffn_case("ffn K=256 one tile", 130, 256, 64, 130);
-    run_ffn_case("ffn one tile", 300, 128, 64, 100);
-    run_ffn_case("ffn two tiles", 300, 128, 128, 100);
-  }
-  kd_set_option("ffn_variant", 1);
+  run_ffn_case("ffn L0", 131072, 128, 384, 4096);
+  run_ffn_case("ffn ragged", 4128 + 77, 128, 448, 96);
+  run_ffn_case("ffn tiny", 37, 128, 64, 37);
+  run_ffn_case("ffn L1 (K=256)", 32768, 256, 768, 1024);
+  run_ffn_case("ffn K=256 ragged", 1000 + 77, 256, 192, 96);
+  run_ffn_case("ffn K=256 one tile", 130, 256, 64, 130);
+  run_ffn_case("ffn one tile", 300, 128, 64, 100);
+  run_ffn_case("ffn two tiles", 300, 128, 128, 100);
   run_patch_case("patch flowers", 32, 3, 64, 64, 4, 128);
   run_patch_case("patch mnist", 4, 1, 7, 7, 4, 256);
   run_patch_case("patch cifar (generic)", 8, 3, 16, 16, 2, 256);

@@ -38,29 +38,23 @@ __device__ __forceinline__ void wait_vm_count(int n) {      // s_waitcnt vmcnt(n
 }
 constexpr int FF_NW = 8;
 
-// SKEW: waves 4..7 (the second wave of every SIMD) run half a tile behind waves 0..3 -- in interval t they finish tile t - 1
-// (GEGLU, down projection) and then start tile t (up projection), while their SIMD partner does up(t), GEGLU(t), down(t).  The
-// barrier per tile otherwise keeps both waves of a SIMD in the SAME phase (both want the matrix pipe, then both want the VALU,
-// and the per-tile costs add up); skewed, one wave's MFMAs run beside the other's GEGLU.  The down-projection k-step of tile t - 1
-// has to stay one interval longer: its ring gets a fourth slot (3 x 32 KiB + 4 x 16 KiB = all 160 KiB of LDS).
 // OUTP (round 3, as in ffn_x3.hip): the attention block's out projection runs first in the same workgroup (x <- x + att Wo^T,
 // image_transformer_v2.py:473-476).  The lane's ATTENTION row is the B operand as it is stored (bf16), the fp32 output accumulators start
 // from x (read into the C layout) and take the 32 MFMAs of Wo (32 KiB, parked in the ring slot the third weight unit will use); what they
 // then hold is the new residual stream in the layout of an MFMA result, which under pack layout 3 of the up projection's weight IS its B
 // operand: norm statistics, scale and rounding in registers, and the down projection keeps accumulating on top of the new x -- the out
 // projection's result and the skip operand never cross HBM (and the new x reaches the norm in fp32, not rounded to bf16).
-template <int NC /* K / 16 */, bool SKEW, bool OUTP = false>
+template <int NC /* K / 16 */, bool OUTP = false>
 __global__ __launch_bounds__(FF_NW * 64) void ffn_kernel(const FArgs p) {
-  static_assert(!OUTP || (NC == 8 && !SKEW), "fused out projection: width 128, plain variant");
+  static_assert(!OUTP || NC == 8, "fused out projection: width 128");
   constexpr int K = NC * 16, NKU = NC / 4, KB = K / 32, NTD = K / 128;
   constexpr int UP_BYTES = NKU * WBLK, DN_BYTES = NTD * WBLK, UNIT = UP_BYTES + DN_BYTES;
-  constexpr int NDS = SKEW ? 4 : 3;                   // slots of the down-projection ring
   constexpr int PCS = UNIT / 1024 / FF_NW;            // 1 KiB pieces per wave per tile
   static_assert(K % 128 == 0 && (UNIT / 1024) % FF_NW == 0, "unit = whole pieces per wave");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
-  const int wid = SKEW ? tid >> 6 : __builtin_amdgcn_readfirstlane(tid >> 6);     // (scalar branches on `late` cost the skewed variant 130 spilled registers)
-  const auto warm = code_warm_begin<(SKEW ? 12 : 9) * 1024>((int)blockIdx.x < p.warm && tid < 64);     // kd_common.h
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const auto warm = code_warm_begin<9 * 1024>((int)blockIdx.x < p.warm && tid < 64);     // kd_common.h
   const int row = blockIdx.x * (FF_NW * 32) + wid * 32 + l31;
   const bool ok = row < p.M;
   const int rowc = ok ? row : p.M - 1;
@@ -68,9 +62,8 @@ __global__ __launch_bounds__(FF_NW * 64) void ffn_kernel(const FArgs p) {
   const bool probe = p.clk && blockIdx.x == 0 && tid == 0;
   if (probe) { p.clk[0] = __builtin_amdgcn_s_memtime(); p.clk[1] = __builtin_amdgcn_s_memrealtime(); }
 
-  const bool late = SKEW && wid >= FF_NW / 2;
   auto up_slot = [&](int t) -> char* { return smem + (t % 3) * UP_BYTES; };
-  auto dn_slot = [&](int t) -> char* { return smem + 3 * UP_BYTES + (t % NDS) * DN_BYTES; };
+  auto dn_slot = [&](int t) -> char* { return smem + 3 * UP_BYTES + (t % 3) * DN_BYTES; };
   auto issue = [&](int t) {
 #pragma unroll
     for (int i = 0; i < PCS; ++i) {
@@ -231,17 +224,13 @@ __global__ __launch_bounds__(FF_NW * 64) void ffn_kernel(const FArgs p) {
       }
   };
   static_assert(PCS == 6, "the counted waits below are written for 6 pieces per wave per tile");
-  const int n_int = SKEW ? T + 1 : T;                 // the late waves finish the last tile in one more interval
-  for (int t = 0; t < n_int; ++t) {
+  for (int t = 0; t < T; ++t) {
     if (t + 1 < T) { KD_WAIT_VM(6); } else { KD_WAIT_VM(0); }
     KD_BARRIER();                                      // unit t is in for every wave; every wave is done with interval t - 1
     if (t + 2 < T) issue(t + 2);
-    if (!late) {
-      if (t < T) { up(t); glu(); down(t); }
-    } else {
-      if (t > 0) { glu(); down(t - 1); }
-      if (t < T) up(t);
-    }
+    up(t);
+    glu();
+    down(t);
   }
   if (probe) { p.clk[5] = __builtin_amdgcn_s_memtime(); p.clk[6] = p.clk[5]; }       // tiles done
   // ---- + skip, store -------------------------------------------------------------------------------------------------------------
@@ -257,16 +246,6 @@ __global__ __launch_bounds__(FF_NW * 64) void ffn_kernel(const FArgs p) {
       float v[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) v[r] = acc_o[ob][r];
-      store_block_bf16(yrow + 32 * ob, v, lh, ok);
-    }
-  } else if (SKEW) {        // the skewed variant (on request only) has no registers to spare for the raw row: it reads it again
-    const u16* xrow = p.X + (size_t)rowc * K;
-#pragma unroll
-    for (int ob = 0; ob < KB; ++ob) {
-      float sk[16], v[16];
-      load_block_bf16(xrow + 32 * ob, sk, lh);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) v[r] = acc_o[ob][r] + sk[r];
       store_block_bf16(yrow + 32 * ob, v, lh, ok);
     }
   } else
@@ -492,10 +471,9 @@ extern "C" int kd_ffn_bf16(const KdFfn* dp, void* stream) {
     launch<ffn256_kernel>(dim3((unsigned)((d.M + F2_NW * 32 - 1) / (F2_NW * 32))), dim3(F2_NW * 64), LDS256, s, a);
     return check_launch("kd_ffn_bf16");
   }
-  // 1 (default) plain, 3 skewed wave pairs.  Measured equal within noise (64.5 / 68.6 us at the level-0 shape; a third form with
-  // one wave per SIMD and the two row blocks' MFMA / GEGLU streams interleaved instruction by instruction took 71 us):
+  // Two re-arrangements of the same work were measured equal within noise and retired (skewed wave pairs 68.6 against 64.5 us at the
+  // level-0 shape; one wave per SIMD with the two row blocks' MFMA / GEGLU streams interleaved instruction by instruction 71 us):
   // profiles/r02_ffn_fused.md -- under this kernel the chip runs against its power limit and re-arranging the same work buys nothing.
-  const int variant = opt(KD_OPT_ffn_variant);
   const bool outp = d.attn != nullptr;
   if (outp) {
     if (!d.Wp_out) return fail(KD_EINVAL, "kd_ffn_bf16: attn without Wp_out");
@@ -506,11 +484,10 @@ extern "C" int kd_ffn_bf16(const KdFfn* dp, void* stream) {
   const ProfName nm("ffn_bf16", "%s M=%d K=%d dff=%d", outp ? "ffn_bf16+out" : "ffn_bf16", d.M, d.K, d.d_ff);
   const double flops = 2.0 * d.M * (double)d.K * (3.0 * d.d_ff + (outp ? d.K : 0));
   const double bytes = (outp ? 6.0 : 4.0) * d.M * (double)d.K + 6.0 * d.d_ff * (double)d.K + (outp ? 2.0 * d.K * d.K : 0.0);
-  const CfgName cfg(nm, "variant%d", variant == 3 && !outp ? 3 : 1);
+  const CfgName cfg(nm, "variant1");
   LaunchScope prof(cfg, flops, bytes, s);
-  if (outp) launch<ffn_kernel<8, false, true>>(grid, block, 9 * WBLK, s, a);
-  else if (variant == 3) launch<ffn_kernel<8, true>>(grid, block, 10 * WBLK, s, a);
-  else launch<ffn_kernel<8, false>>(grid, block, 9 * WBLK, s, a);
+  if (outp) launch<ffn_kernel<8, true>>(grid, block, 9 * WBLK, s, a);
+  else launch<ffn_kernel<8>>(grid, block, 9 * WBLK, s, a);
   return check_launch("kd_ffn_bf16");
 }
 

@@ -29,13 +29,14 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
-constexpr int BM = 128;                 // rows per workgroup of the 4-wave form (4 waves x 32); the 8-wave form owns 2 * BM
+constexpr int NWV = 4;                  // waves per workgroup
+constexpr int BM = 128;                 // rows per workgroup (4 waves x 32)
 constexpr int BK = 32;                  // K per W stage
 constexpr int IMG = 128 * BK * 2;       // one bf16 image of a stage: [128 W rows][32 k] = 8 KiB
 constexpr int STAGE = 2 * IMG;          // hi + lo = 16 KiB  (== WP_BLOCK of gemm.hip)
 constexpr int NSTG = 4;                 // ring depth
 constexpr int LDS_RING = NSTG * STAGE;  // 64 KiB
-constexpr int lds_bytes(int nwv) { return LDS_RING + nwv * 8 * 64 * 4 + nwv * 32 * 4 + 64; }   // + epilogue strips + row rsqrt table + sqrt(qk scale) per head (<= 16)
+constexpr int LDS_BYTES = LDS_RING + NWV * 8 * 64 * 4 + NWV * 32 * 4 + 64;   // + epilogue strips + row rsqrt table + sqrt(qk scale) per head (<= 16)
 
 __device__ __forceinline__ int swz(int row, int c) { return row * 64 + ((c ^ ((row >> 2) & 3)) << 4); }
 __device__ __forceinline__ unsigned pack_bf16(float a, float b) {
@@ -56,13 +57,13 @@ __device__ __forceinline__ void split4(const f32x4 v, u32x2& hi, u32x2& lo) {
 // NC = K / 16 (8, 16 or 32); EPI: KD_EPI_STORE / KD_EPI_QKV / KD_EPI_GEGLU.  gridDim.y splits the n-tiles of a panel over
 // several workgroups when M alone gives too few panels to fill the chip (each re-normalises the A panel: cheap next to
 // its share of W).  K = 512 keeps 256 VGPRs of A fragments per lane: one workgroup per CU, unified VGPR/AGPR file.
-// NWV = waves per workgroup (4 or 8): an 8-wave workgroup owns a 256-row panel fed by ONE W ring -- half the L2 -> CU
-// bytes per flop of two co-resident 4-wave workgroups.  The vector-memory path delivers ~10-13 B/clk/CU even on L2 hits
-// (every tiled / streamed kernel here tops out there), so bytes per flop into the CU is what the main loop pays for.
-template <int NC, int EPI, int NWV>
-__global__ __launch_bounds__(64 * NWV, (NC <= 8 && NWV == 4) ? 2 : 1) void gemm_astat_kernel(const GemmP p) {
+// (An 8-wave workgroup on a 256-row panel fed by ONE W ring -- half the L2 -> CU bytes per flop of two co-resident 4-wave
+// workgroups -- measured neutral at K = 128, level-0 qkv 59 -> 65 us, GEGLU 117 -> 114 us, end to end -0.4 %:
+// profiles/r01_astat_ablation.md; halving the W bytes into the CU is not what the main loop waits for.  Retired.)
+template <int NC, int EPI>
+__global__ __launch_bounds__(64 * NWV, NC <= 8 ? 2 : 1) void gemm_astat_kernel(const GemmP p) {
   constexpr int BMW = NWV * 32;                           // rows of this workgroup's panel
-  constexpr int PCS = 4 * 4 / NWV;                        // 1 KiB pieces of a W stage moved by each wave (4 or 2)
+  constexpr int PCS = 4 * 4 / NWV;                        // 1 KiB pieces of a W stage moved by each wave
   constexpr int K = NC * 16, NK = NC / 2;                 // NK: W stages per n-tile (multiple of NSTG)
   constexpr bool GEGLU = EPI == KD_EPI_GEGLU;
   constexpr int NCOL = GEGLU ? 64 : 128;                  // output columns per n-tile
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(64 * NWV, (NC <= 8 && NWV == 4) ? 2 : 1) void gemm_
     for (int ks = 0; ks < NK; ++ks) {
       const int s = nt * NK + ks;
       // Stage s has landed?  Stages ks = 0, 1 of every tile but the first were confirmed before the previous epilogue.
-      if (nt > 0 && ks == 2 && full_panel && NWV == 4) {
+      if (nt > 0 && ks == 2 && full_panel) {
         // First counted wait after an epilogue.  vmcnt retires in issue order on gfx9-class hardware, loads and stores
         // alike, and this wave's queue now reads [stage s][NST epilogue stores][stage s+1][stage s+2]: allowing the
         // stores to stay outstanding (+NST) waits for stage s only.  Counting loads alone here made every n-tile wait for
@@ -233,8 +234,7 @@ __global__ __launch_bounds__(64 * NWV, (NC <= 8 && NWV == 4) ? 2 : 1) void gemm_
         else if (s + 1 < total) { if (NST == 8) KD_WAIT_VM(12); else KD_WAIT_VM(20); }
         else { if (NST == 8) KD_WAIT_VM(8); else KD_WAIT_VM(16); }
       } else if (nt == 0 || ks >= 2) {
-        if (NWV == 4) { if (s + 2 < total) KD_WAIT_VM(8); else if (s + 1 < total) KD_WAIT_VM(4); else KD_WAIT_VM(0); }
-        else { if (s + 2 < total) KD_WAIT_VM(4); else if (s + 1 < total) KD_WAIT_VM(2); else KD_WAIT_VM(0); }
+        if (s + 2 < total) KD_WAIT_VM(8); else if (s + 1 < total) KD_WAIT_VM(4); else KD_WAIT_VM(0);
       }
       KD_BARRIER();                      // every wave's quarter of stage s is in; everyone is done reading slot (s-1) % NSTG
       if (s + 3 < total) issue(s + 3);   // refill the slot freed by stage s-1
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(64 * NWV, (NC <= 8 && NWV == 4) ? 2 : 1) void gemm_
     }
     // stages (nt+1, ks = 0, 1) were requested >= 2 stages ago: confirm them now, before the stores of this epilogue
     // enter the vector-memory queue (outstanding after the last issue: stages s+1, s+2, s+3 -> leave only s+3)
-    if (nt + 1 < n_tiles) { if (NWV == 4) KD_WAIT_VM(4); else KD_WAIT_VM(2); }
+    if (nt + 1 < n_tiles) KD_WAIT_VM(4);
     epilogue(nt);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -268,20 +268,19 @@ __global__ __launch_bounds__(64 * NWV, (NC <= 8 && NWV == 4) ? 2 : 1) void gemm_
   }
 }
 
-template <int NC, int EPI, int NWV>
+template <int NC, int EPI>
 static int launch(const GemmP& d, hipStream_t s) {
-  constexpr int LDS_BYTES = lds_bytes(NWV), BMW = NWV * 32;
   const double n_eff = (EPI == KD_EPI_GEGLU) ? 2.0 * d.N : (double)d.N;
   const ProfName nm("gemm_astat", "gemm_astat<e%d> M=%d N=%d K=%d", EPI, d.M, d.N, d.K);
   // panels x n-splits: aim at >= 256 workgroups (one per CU) while every split keeps >= 2 n-tiles
-  const int panels = (d.M + BMW - 1) / BMW, n_tiles = d.N / (EPI == KD_EPI_GEGLU ? 64 : 128);
+  const int panels = (d.M + BM - 1) / BM, n_tiles = d.N / (EPI == KD_EPI_GEGLU ? 64 : 128);
   int splits = 1;
   while (panels * splits < 256 && n_tiles / (splits * 2) >= 2) splits *= 2;
   const CfgName cfg(nm, "splits%d,waves%d", splits, NWV);
   LaunchScope prof(cfg, 2.0 * d.M * n_eff * d.K, 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N), s);
   GemmP e = d;
   if (opt(KD_OPT_astat_storewait)) e.debug |= 32;
-  kd::launch<gemm_astat_kernel<NC, EPI, NWV>>(dim3((unsigned)panels, (unsigned)splits), dim3(64 * NWV), LDS_BYTES, s, e);
+  kd::launch<gemm_astat_kernel<NC, EPI>>(dim3((unsigned)panels, (unsigned)splits), dim3(64 * NWV), LDS_BYTES, s, e);
   return check_launch("kd_gemm_f32(astat)");
 }
 
@@ -299,19 +298,7 @@ int gemm_astat_try(const GemmP& d, hipStream_t s, int* rc) {
   if (!(d.scale_stride == 0 || d.rows_per_sample % BM == 0)) return 1;          // one scale vector per panel
   if (d.epi == KD_EPI_QKV && (d.rows_per_sample % BM || d.n_heads > 16)) return 1;
   if (d.M < 4 * BM) return 1;
-  // 256-row panels (8 waves, one W ring; KDIFF_ASTAT_WAVES=8) where the A fragments leave room for two waves per SIMD
-  // (K = 128) and the panel grid still fills the chip.  Measured neutral against two co-resident 4-wave workgroups
-  // (level-0 qkv 59 -> 65 us, GEGLU 117 -> 114 us, end to end -0.4 %: profiles/r01_astat_ablation.md), so the 4-wave
-  // form stays the default: halving the W bytes into the CU is not what the main loop waits for.
-  const int max_waves = opt(KD_OPT_astat_waves);
-  const bool wide = max_waves >= 8 && d.K == 128 && d.M >= 256 * 2 * BM && (d.scale_stride == 0 || d.rows_per_sample % (2 * BM) == 0) &&
-                    (d.epi != KD_EPI_QKV || d.rows_per_sample % (2 * BM) == 0);
-#define KD_AS(NCV, EP) if (d.K == NCV * 16 && d.epi == EP) { *rc = launch<NCV, EP, 4>(d, s); return 0; }
-  if (wide) {
-    if (d.epi == KD_EPI_STORE) { *rc = launch<8, KD_EPI_STORE, 8>(d, s); return 0; }
-    if (d.epi == KD_EPI_QKV) { *rc = launch<8, KD_EPI_QKV, 8>(d, s); return 0; }
-    if (d.epi == KD_EPI_GEGLU) { *rc = launch<8, KD_EPI_GEGLU, 8>(d, s); return 0; }
-  }
+#define KD_AS(NCV, EP) if (d.K == NCV * 16 && d.epi == EP) { *rc = launch<NCV, EP>(d, s); return 0; }
   KD_AS(8, KD_EPI_STORE) KD_AS(8, KD_EPI_QKV) KD_AS(8, KD_EPI_GEGLU)
   KD_AS(16, KD_EPI_STORE) KD_AS(16, KD_EPI_QKV) KD_AS(16, KD_EPI_GEGLU)
   KD_AS(32, KD_EPI_STORE) KD_AS(32, KD_EPI_QKV) KD_AS(32, KD_EPI_GEGLU)

@@ -30,10 +30,11 @@ struct GArgs {
 
 // ------------------------------------------------------------------------------------------------------------------
 // wstat
-// PF: the NEXT chunk's rows are requested before the current chunk is processed (one extra set of raw fragments in registers):
-// with 2 waves per SIMD the other wave alone does not cover a chunk's HBM latency.  Every wave walks a CONTIGUOUS range of
-// chunks (same sample for most consecutive chunks: the scale vector stays in L1).
-template <int NC /* K / 16 */, int EPI, bool NORM, int NW, bool PF, bool PIPE>
+// Every wave walks a CONTIGUOUS range of chunks (same sample for most consecutive chunks: the scale vector stays in L1).
+// Next-chunk prefetch, software-pipelined tiles and 4 / 12 waves were measured and retired (profiles/r02_wstat_ablation.md: the
+// first two level within noise, the last two slower).
+constexpr int NW = 8;       // waves per workgroup: 2 per SIMD, up to 256 registers each
+template <int NC /* K / 16 */, int EPI, bool NORM>
 __global__ __launch_bounds__(NW * 64) void gemm_wstat_kernel(const GArgs p) {
   constexpr int K = NC * 16, NK = NC / 4;
   constexpr bool GEGLU = EPI == KD_EPI_GEGLU;
@@ -72,8 +73,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_wstat_kernel(const GArgs p) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) raw[c] = ap[2 * c];
   };
-  u32x4 nxt[PF ? NC : 1];
-  if (PF && ch0 < ch1) load_raw(ch0, reinterpret_cast<u32x4(&)[NC]>(nxt));
   for (int ch = ch0; ch < ch1; ++ch) {
     const int row = ch * 32 + l31;
     const bool ok = row < p.M;
@@ -84,13 +83,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_wstat_kernel(const GArgs p) {
     float rs = 1.0f;
     {
       u32x4 raw[NC];
-      if (PF) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) raw[c] = nxt[PF ? c : 0];
-        if (ch + 1 < ch1) load_raw(ch + 1, reinterpret_cast<u32x4(&)[NC]>(nxt));
-      } else {
-        load_raw(ch, raw);
-      }
+      load_raw(ch, raw);
       if (NORM) {
         const int b = rowc / p.rows_per_sample;
         const float* sp = p.scale + (size_t)b * p.scale_stride + 8 * lh;
@@ -134,12 +127,10 @@ __global__ __launch_bounds__(NW * 64) void gemm_wstat_kernel(const GArgs p) {
       px = p.pos[2 * tok + 1];
     }
 
-    // ---- the tiles of this slice.  mma(t): products of tile t into an accumulator set; epi(t): its epilogue, in the lane
-    // that owns the row.  PIPE: two accumulator sets -- the epilogue of tile t is issued BETWEEN the MFMAs of tile t + 1 (one
-    // MFMA, then ~10 VALU instructions of the epilogue, one fragment read, ...): the matrix pipe works through a 32-clock MFMA
-    // while the same wave's VALU instructions issue, instead of the two phases taking turns (they add up otherwise: measured).
+    // ---- the tiles of this slice.  mma(t): products of tile t into the accumulators; epi(t): its epilogue, in the lane
+    // that owns the row.
     u16* crow = p.C + (size_t)rowc * p.N;
-    auto mma = [&](int t, f32x16 (&acc)[4], bool pin) {
+    auto mma = [&](int t, f32x16 (&acc)[4]) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -159,15 +150,13 @@ __global__ __launch_bounds__(NW * 64) void gemm_wstat_kernel(const GArgs p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[c & 1][j], a[c], acc[j], 0, 0, 0);
       }
-      if (pin) {
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
-        for (int c = 0; c + 1 < NC; ++c) {
-          __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-        }
+      for (int c = 0; c + 1 < NC; ++c) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
       }
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
     };
     auto epi = [&](int t, f32x16 (&acc)[4], u32x4 (&rraw)[4][2]) {
       const int n0 = (nt0 + t) * NCOL;
@@ -219,45 +208,15 @@ __global__ __launch_bounds__(NW * 64) void gemm_wstat_kernel(const GArgs p) {
       }
     };
     u32x4 rraw[4][2];
-    if (PIPE) {
-      // issue pattern of one "MFMAs of the next tile + epilogue of this tile" region
-      auto interleave = [&]() {
-        constexpr int VPM = 10;                                // VALU instructions between two MFMAs (epilogue ~ 10 per MFMA)
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+    for (int t = 0; t < ntn; ++t) {
+      if (EPI == KD_EPI_RESIDUAL) {      // residual operand of this tile, requested before the products
+        const int n0 = (nt0 + t) * NCOL;
 #pragma unroll
-        for (int i = 0; i < 4 * NC; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);
-          if (i < 4 * NC - 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-      };
-      f32x16 accA[4], accB[4];
-      mma(0, accA, true);
-      int t = 0;
-      for (; t + 1 < ntn; t += 2) {
-        mma(t + 1, accB, false);
-        epi(t, accA, rraw);
-        interleave();
-        if (t + 2 < ntn) {
-          mma(t + 2, accA, false);
-          epi(t + 1, accB, rraw);
-          interleave();
-        } else {
-          epi(t + 1, accB, rraw);
-        }
+        for (int j = 0; j < 4; ++j) load_block_raw(p.R + (size_t)rowc * p.N + min(n0 + 32 * j, p.N - 32), rraw[j], lh);
       }
-      if (t < ntn) epi(t, accA, rraw);
-    } else {
-      for (int t = 0; t < ntn; ++t) {
-        if (EPI == KD_EPI_RESIDUAL) {      // residual operand of this tile, requested before the products
-          const int n0 = (nt0 + t) * NCOL;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) load_block_raw(p.R + (size_t)rowc * p.N + min(n0 + 32 * j, p.N - 32), rraw[j], lh);
-        }
-        f32x16 acc[4];
-        mma(t, acc, true);
-        epi(t, acc, rraw);
-      }
+      f32x16 acc[4];
+      mma(t, acc);
+      epi(t, acc, rraw);
     }
   }
   if (p.clk && blockIdx.x == 0 && tid == 0) { p.clk[2] = __builtin_amdgcn_s_memtime(); p.clk[3] = __builtin_amdgcn_s_memrealtime(); }
@@ -268,16 +227,16 @@ unsigned long long* g_clk = nullptr;
 
 constexpr int WSTAT_LDS_MAX = 144 * 1024;
 
-template <int NC, int EPI, bool NORM, int NW, bool PF, bool PIPE>
+template <int NC, int EPI, bool NORM>
 static int launch_wstat(const GArgs& a, int lds, const char* nm, double flops, double bytes, hipStream_t s) {
   const int chunks = (a.M + 31) / 32;
   int groups = cu_count() / a.n_slices;
   if (groups < 1) groups = 1;
   const int need = (chunks + NW - 1) / NW;
   if (groups > need) groups = need;
-  const CfgName cfg(nm, "waves%d,pf%d,slices%d", NW, PIPE ? 2 : (PF ? 1 : 0), a.n_slices);
+  const CfgName cfg(nm, "waves%d,pf0,slices%d", NW, a.n_slices);
   LaunchScope prof(cfg, flops, bytes, s);
-  launch_max_lds<gemm_wstat_kernel<NC, EPI, NORM, NW, PF, PIPE>>(WSTAT_LDS_MAX, dim3((unsigned)(groups * a.n_slices)), dim3(NW * 64), lds, s, a);
+  launch_max_lds<gemm_wstat_kernel<NC, EPI, NORM>>(WSTAT_LDS_MAX, dim3((unsigned)(groups * a.n_slices)), dim3(NW * 64), lds, s, a);
   return check_launch("kd_gemm_bf16(wstat)");
 }
 
@@ -315,38 +274,22 @@ int gemm_wstat_try(const KdGemm& d, hipStream_t s, int* rc) {
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 2.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N) + (d.epi == KD_EPI_RESIDUAL ? 2.0 * d.M * d.N : 0.0);
   const ProfName nm("gemm_wstat", "gemm_bf16_wstat<e%d,n%d> M=%d N=%d K=%d", d.epi, d.norm, d.M, d.N, d.K);
-  // 0 plain (default), 1 next-chunk prefetch, 2 software-pipelined tiles (qkv / GEGLU at K = 128).  All three measure the same
-  // within noise (profiles/r02_wstat_ablation.md): under these kernels the chip runs at 1.6-2.2 GHz (s_memtime / s_memrealtime),
-  // i.e. against its power limit, where re-arranging the same work buys nothing
-  const int pf = opt(KD_OPT_wstat_prefetch);
-#define KD_WS(NCV, EP, NO, NWV)                                                                                        \
-  {                                                                                                                    \
-    constexpr bool can_pipe = NCV == 8 && (EP == KD_EPI_QKV || EP == KD_EPI_GEGLU);                                    \
-    if (pf == 2 && can_pipe) *rc = launch_wstat<NCV, EP, NO, NWV, false, can_pipe>(a, lds, nm, flops, bytes, s);       \
-    else if (pf >= 1 && NCV <= 16) *rc = launch_wstat<NCV, EP, NO, NWV, (NCV <= 16), false>(a, lds, nm, flops, bytes, s); \
-    else *rc = launch_wstat<NCV, EP, NO, NWV, false, false>(a, lds, nm, flops, bytes, s);                              \
-    return 0;                                                                                                          \
+#define KD_WS(NCV, EP, NO) { *rc = launch_wstat<NCV, EP, NO>(a, lds, nm, flops, bytes, s); return 0; }
+#define KD_WS_ALL(NCV)                                                       \
+  {                                                                          \
+    if (d.epi == KD_EPI_QKV) KD_WS(NCV, KD_EPI_QKV, true)                    \
+    if (d.epi == KD_EPI_GEGLU) KD_WS(NCV, KD_EPI_GEGLU, true)                \
+    if (d.epi == KD_EPI_STORE && d.norm) KD_WS(NCV, KD_EPI_STORE, true)      \
+    if (d.epi == KD_EPI_STORE) KD_WS(NCV, KD_EPI_STORE, false)               \
+    if (d.epi == KD_EPI_RESIDUAL) KD_WS(NCV, KD_EPI_RESIDUAL, false)         \
   }
-#define KD_WS_ALL(NCV, NWV)                                                       \
-  {                                                                               \
-    if (d.epi == KD_EPI_QKV) KD_WS(NCV, KD_EPI_QKV, true, NWV)                    \
-    if (d.epi == KD_EPI_GEGLU) KD_WS(NCV, KD_EPI_GEGLU, true, NWV)                \
-    if (d.epi == KD_EPI_STORE && d.norm) KD_WS(NCV, KD_EPI_STORE, true, NWV)      \
-    if (d.epi == KD_EPI_STORE) KD_WS(NCV, KD_EPI_STORE, false, NWV)               \
-    if (d.epi == KD_EPI_RESIDUAL) KD_WS(NCV, KD_EPI_RESIDUAL, false, NWV)         \
-  }
-  const int ww = opt(KD_OPT_wstat_waves);        // 0: per-shape default (8 waves: 2 per SIMD, up to 256 registers each)
-  if (d.K == 128 && ww == 12) KD_WS_ALL(8, 12)
-  if (d.K == 128 && ww == 4) KD_WS_ALL(8, 4)
-  if (d.K == 128) KD_WS_ALL(8, 8)
-  if (d.K == 256 && ww == 4) KD_WS_ALL(16, 4)
-  if (d.K == 256) KD_WS_ALL(16, 8)
+  if (d.K == 128) KD_WS_ALL(8)
+  if (d.K == 256) KD_WS_ALL(16)
   if (d.K == 384) {
-    if (d.epi == KD_EPI_RESIDUAL) KD_WS(24, KD_EPI_RESIDUAL, false, 8)
-    if (d.epi == KD_EPI_STORE && !d.norm) KD_WS(24, KD_EPI_STORE, false, 8)
+    if (d.epi == KD_EPI_RESIDUAL) KD_WS(24, KD_EPI_RESIDUAL, false)
+    if (d.epi == KD_EPI_STORE && !d.norm) KD_WS(24, KD_EPI_STORE, false)
   }
-  if (d.K == 512 && ww == 4) KD_WS_ALL(32, 4)
-  if (d.K == 512) KD_WS_ALL(32, 8)
+  if (d.K == 512) KD_WS_ALL(32)
 #undef KD_WS_ALL
 #undef KD_WS
   return 1;
@@ -367,16 +310,17 @@ struct TArgs {
   int warm;                 // code warm-up workgroups (kd_common.h)
 };
 
-// DEEP (BMT = 1 only): 4-slot ring, one workgroup per CU -- for grids of at most one tile per CU (the level-2 shapes: 8192 rows),
-// where the second workgroup of the 2-slot form does not exist and every K step would wait a full L2 round trip for its blocks.
+// DEEP (= LW): 4-slot ring -- for grids of at most one tile per CU (the level-2 shapes: 8192 rows), where the second workgroup of the
+// 2-slot form does not exist.  (Without loader waves it measured no better than 2 slots: 10.2 vs 9.5 us, 21.5 vs 21.5; retired.)
 // LW (round 4; BMT = 1, DEEP ring, one workgroup per CU): LOADER WAVES as in csrc/gemm_x3r.hip.  The level-2 shapes (8192 rows: one tile per
 // CU) ran ~1 800 clocks per 64-wide K step against 512 of MFMA: every wave issued its 8 LDS-DMA requests of the next step in one burst behind
 // the barrier, and a wave that is issuing requests issues nothing else.  The kernel needs 114 - 178 of a SIMD's 512 registers per lane, so the
 // workgroup carries four more waves that do only the staging (requests, counted vmcnt, the step's barrier); the compute waves' K loop is
 // ds_read + MFMA + the one barrier per step.
-template <int AMODE, int EPI, int BMT, bool DEEP = false, bool LW = false>
-__global__ __launch_bounds__(LW ? 512 : 256 * BMT, (BMT == 1 && (!DEEP || LW)) ? 2 : 1) void gemm_tiled_kernel(const TArgs p) {
-  static_assert(!LW || (BMT == 1 && DEEP), "loader waves: 128-row tiles, 4-slot ring");
+template <int AMODE, int EPI, int BMT, bool LW = false>
+__global__ __launch_bounds__(LW ? 512 : 256 * BMT, BMT == 1 ? 2 : 1) void gemm_tiled_kernel(const TArgs p) {
+  static_assert(!LW || BMT == 1, "loader waves: 128-row tiles");
+  constexpr bool DEEP = LW;                          // loader waves: 4-slot ring
   constexpr int NWV = 4 * BMT, BMR = 128 * BMT;
   constexpr int A_IMG = BMR * 128, STG = A_IMG + WBLK, NSTG = BMT == 1 ? (DEEP ? 4 : 2) : 3;
   constexpr int WPC = 16 / NWV;                      // weight pieces (1 KiB) per staging wave per step
@@ -606,13 +550,13 @@ __global__ __launch_bounds__(LW ? 512 : 256 * BMT, (BMT == 1 && (!DEEP || LW)) ?
   }
 }
 
-template <int AMODE, int EPI, int BMT, bool DEEP = false, bool LW = false>
+template <int AMODE, int EPI, int BMT, bool LW = false>
 static int launch_tiled(const TArgs& a, const char* nm, double flops, double bytes, hipStream_t s) {
-  constexpr int LDS = (BMT == 1 ? (DEEP ? 4 : 2) : 3) * (128 * BMT * 128 + WBLK);
+  constexpr int LDS = (BMT == 1 ? (LW ? 4 : 2) : 3) * (128 * BMT * 128 + WBLK);
   const long tiles = (long)((a.M + 128 * BMT - 1) / (128 * BMT)) * a.n_tiles_n;
-  const CfgName cfg(nm, "bm%d,lw%d,deep%d", 128 * BMT, (int)LW, (int)DEEP);       // (the loader-wave form runs on the deep ring: lw1,deep1)
+  const CfgName cfg(nm, "bm%d,lw%d,deep%d", 128 * BMT, (int)LW, (int)LW);         // (the loader-wave form runs on the deep ring: lw1,deep1)
   LaunchScope prof(cfg, flops, bytes, s);
-  launch<gemm_tiled_kernel<AMODE, EPI, BMT, DEEP, LW>>(dim3((unsigned)tiles), dim3(LW ? 512 : 256 * BMT), LDS, s, a);
+  launch<gemm_tiled_kernel<AMODE, EPI, BMT, LW>>(dim3((unsigned)tiles), dim3(LW ? 512 : 256 * BMT), LDS, s, a);
   return check_launch("kd_gemm_bf16(tiled)");
 }
 
@@ -636,9 +580,6 @@ int gemm_tiled_try(const KdGemm& d, hipStream_t s, int* rc) {
   const long tiles256 = (long)((d.M + 255) / 256) * a.n_tiles_n, tiles128 = (long)((d.M + 127) / 128) * a.n_tiles_n;
   const int bmt = opt(KD_OPT_tiled_bm);
   const bool big = bmt ? bmt == 256 : tiles256 >= cu_count();
-  // 4-slot ring for grids of at most one tile per CU: measured no better than the 2-slot form (level-2 shapes 10.2 vs 9.5 us,
-  // 21.5 vs 21.5: the block latency is not what those steps wait for) -- on request only
-  const bool deep = !big && tiles128 <= cu_count() && opt(KD_OPT_tiled_deep);
   // round 4: grids of at most ONE tile per CU (the level-2 shapes) on the loader-wave form (4-slot ring, 4 compute + 4 staging waves)
   // (from 12 K steps on: with fewer the launch's fixed cost decides and the smaller 2-slot form is ahead -- level-2 out projection 13.8 vs 14.2 us,
   // the 256-wide MNIST / CIFAR levels +4 us per launch: profiles/r04_tiled_bf16_bench.log, r04_small_batch.log)
@@ -646,8 +587,8 @@ int gemm_tiled_try(const KdGemm& d, hipStream_t s, int* rc) {
 #define KD_TL(AM, EP)                                                                       \
   if (d.a_mode == AM && d.epi == EP) {                                                      \
     *rc = big ? launch_tiled<AM, EP, 2>(a, nm, flops, bytes, s)                             \
-              : (lw ? launch_tiled<AM, EP, 1, true, true>(a, nm, flops, bytes, s)           \
-                    : (deep ? launch_tiled<AM, EP, 1, true>(a, nm, flops, bytes, s) : launch_tiled<AM, EP, 1>(a, nm, flops, bytes, s))); \
+              : (lw ? launch_tiled<AM, EP, 1, true>(a, nm, flops, bytes, s)                 \
+                    : launch_tiled<AM, EP, 1>(a, nm, flops, bytes, s));                     \
     return 0;                                                                               \
   }
   KD_TL(KD_A_PLAIN, KD_EPI_STORE)
@@ -660,19 +601,18 @@ int gemm_tiled_try(const KdGemm& d, hipStream_t s, int* rc) {
 
 // ------------------------------------------------------------------------------------------------------------------
 // astat: AdaRMSNorm -> wide projection (qkv, up-projection + GEGLU) at K = 256 / 512, where the weight is too large to park.
-// A workgroup of NWV waves owns a panel of 32 NWV rows for a range of n-tiles: each wave keeps its 32 rows of the normalised,
+// A workgroup of NWV = 4 waves owns a panel of 128 rows for a range of n-tiles: each wave keeps its 32 rows of the normalised,
 // scaled panel in registers as B-operand fragments (read and converted once), the packed weight streams through an LDS ring
 // (one 16 KiB block = [128 features][64 k] per slot, global_load_lds NSTG - 1 blocks ahead, counted vmcnt, one barrier per
 // block), the epilogue of an n-tile runs in the lanes that own the rows while the next blocks are in flight.
-//   NWV = 4: 128-row panels, 4-slot ring, two workgroups per CU (small M: more, smaller units);
-//   NWV = 8: 256-row panels, 8-slot ring, one workgroup per CU -- every block that crosses the L2 -> LDS path (39-52 bytes / clock /
-//            CU measured, profiles/r02_harness_*.log) now feeds 256 rows instead of 128: at two 128-row workgroups per CU the
-//            weight stream alone asked for ~50 bytes / clock / CU, i.e. that path, not the matrix pipe, set the pace.
+// 4-slot ring, two workgroups per CU.  (256-row panels of 8 waves on an 8-slot ring, one workgroup per CU, halve the weight stream through
+// the L2 -> LDS path but were never faster -- L1 qkv 30.4 vs 28.2 us, L2 qkv 47.0 vs 38.6, the GEGLU shapes equal,
+// profiles/r02_harness_astat_rows.log: that stream is not what limits these kernels -- and were retired.)
 // vmcnt bookkeeping (loads and stores retire in issue order): the wait before block s allows the blocks requested after it AND the
 // epilogue stores issued after it to stay outstanding (full panels only; ragged panels wait for their stores).
-template <int NC, int EPI, int NWV>
-__global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_astat_kernel(const GArgs p) {
-  constexpr int K = NC * 16, NK = NC / 4, NSTG = NWV == 4 ? 4 : 8, PDIST = NSTG - 1;
+template <int NC, int EPI>
+__global__ __launch_bounds__(256, 2) void gemm_astat_kernel(const GArgs p) {
+  constexpr int NWV = 4, K = NC * 16, NK = NC / 4, NSTG = 4, PDIST = NSTG - 1;
   constexpr int PB = 16 / NWV;                       // 1 KiB pieces of a block per wave
   constexpr bool GEGLU = EPI == KD_EPI_GEGLU;
   constexpr int NCOL = GEGLU ? 64 : 128;
@@ -896,31 +836,21 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_astat_kernel(
   if (probe) { p.clk[2] = __builtin_amdgcn_s_memtime(); p.clk[3] = __builtin_amdgcn_s_memrealtime(); p.clk[7] = (unsigned long long)total; }
 }
 
-template <int NC, int EPI, int NWV>
-static int launch_astat_w(const GArgs& a, int splits, const char* nm, double flops, double bytes, hipStream_t s) {
-  constexpr int LDS = (NWV == 4 ? 4 : 8) * WBLK + NWV * NC * 64;      // ring + one scale vector (K floats) per wave
-  const int panels = (a.M + 32 * NWV - 1) / (32 * NWV);
-  GArgs b = a;
-  b.n_slices = splits;                                // (the astat kernel's use of this field: n-splits per panel)
-  const CfgName cfg(nm, "rows%d,splits%d", 32 * NWV, splits);
-  LaunchScope prof(cfg, flops, bytes, s);
-  launch<gemm_astat_kernel<NC, EPI, NWV>>(dim3((unsigned)(panels * splits)), dim3(NWV * 64), LDS, s, b);
-  return check_launch("kd_gemm_bf16(astat)");
-}
-
 template <int NC, int EPI>
 static int launch_astat(const GArgs& a, const char* nm, double flops, double bytes, hipStream_t s) {
-  // panels x n-splits: 128-row panels, two workgroups per CU, n-tiles split until the grid fills them ("astat_rows" = 256: the
-  // 256-row / one-workgroup-per-CU form).
+  // panels x n-splits: 128-row panels, two workgroups per CU, n-tiles split until the grid fills them.
   // n-splits of a panel: best_n_splits with the row prologue at about one n-tile's worth of time (profiles/r02_astat_timeline.md)
-  const int forced = opt(KD_OPT_astat_splits), rows = opt(KD_OPT_astat_rows);
-  const int p256 = (a.M + 255) / 256, s256 = best_n_splits(p256, a.n_tiles, cu_count(), 1);
-  // measured (harness "astat", profiles/r02_harness_astat_rows.log): the 256-row form is never faster (L1 qkv 30.4 vs 28.2 us, L2 qkv
-  // 47.0 vs 38.6, the GEGLU shapes equal) -- the L2 -> LDS stream it halves is not what limits these kernels -- so it runs on request only
-  const bool wide = rows == 256;
-  if (wide) return launch_astat_w<NC, EPI, 8>(a, forced > 0 && forced <= a.n_tiles ? forced : s256, nm, flops, bytes, s);
+  const int forced = opt(KD_OPT_astat_splits);
   const int s128 = best_n_splits((a.M + 127) / 128, a.n_tiles, 2 * cu_count(), 1);
-  return launch_astat_w<NC, EPI, 4>(a, forced > 0 && forced <= a.n_tiles ? forced : s128, nm, flops, bytes, s);
+  const int splits = forced > 0 && forced <= a.n_tiles ? forced : s128;
+  constexpr int LDS = 4 * WBLK + 4 * NC * 64;         // ring + one scale vector (K floats) per wave
+  const int panels = (a.M + 127) / 128;
+  GArgs b = a;
+  b.n_slices = splits;                                // (the astat kernel's use of this field: n-splits per panel)
+  const CfgName cfg(nm, "rows128,splits%d", splits);
+  LaunchScope prof(cfg, flops, bytes, s);
+  launch<gemm_astat_kernel<NC, EPI>>(dim3((unsigned)(panels * splits)), dim3(256), LDS, s, b);
+  return check_launch("kd_gemm_bf16(astat)");
 }
 
 int gemm_astat_try(const KdGemm& d, hipStream_t s, int* rc) {

@@ -16,7 +16,6 @@
 //     store, GEGLU, residual, plain store).  The residual enters as wave 7's initial accumulators.
 // Same arithmetic as the throughput kernels (3 bf16 MFMA terms per product, fp32 accumulate) in another summation order.
 #include "x3_common.h"
-#include <cstdio>
 
 namespace kd {
 namespace x3s {
@@ -25,9 +24,12 @@ using namespace x3;
 using b16::u16;
 
 constexpr int HALF = 4096, NW = 8;
+// RB: 32-row blocks per workgroup.  (Two -- 64 rows per workgroup with every W fragment feeding both, a third less through the L1 per row, half
+// the workgroups -- need 64 accumulators next to 2 x 64 registers of stages in flight: at the 256 registers of two waves per SIMD hipcc spills
+// 50 - 280 of them to scratch.)
+constexpr int RB = 1;
 constexpr int RED_BYTES = NW * 8 * 64 * 16;             // [wave][register group][lane] x 16 bytes: one row block's partial sums
-constexpr int SCL_MAX_K = 2048, SCL_BYTES = SCL_MAX_K * 4;
-template <int RB> constexpr int lds_bytes() { return RED_BYTES + RB * (NW * 32 * 4 + 8 * 64 * 16 + 2048) + SCL_BYTES; }
+constexpr int LDS_BYTES = RED_BYTES + RB * (NW * 32 * 4 + 8 * 64 * 16 + 2048);
 
 struct SArgs {
   const float* A; const char* Wp; float* C; const float* R;
@@ -38,26 +40,25 @@ struct SArgs {
   float out_add;
 };
 
-// SC: 0 no norm in front; 1 AdaRMSNorm, every lane loads its row's scale entries (rows of several samples in a workgroup); 2 AdaRMSNorm, all
-// rows of the workgroup share one scale vector: parked in LDS once, read as broadcasts (a quarter less through the L1 than SC = 1)
-template <int RB, int SC>
+// SC: 0 no norm in front; 1 AdaRMSNorm, every lane loads its row's scale entries (rows of several samples in a workgroup).  (The scale vector
+// parked in LDS once where the workgroup's rows share it -- a quarter less through the L1 -- measured level, 17.7 / 12.7 / 10.6 against
+// 17.1 / 12.8 / 10.3 us: the kernel waits on latency, not on the L1.  Retired.)
+template <int SC>
 struct Stage {
   f32x4 x[RB][2][2];           // the lane's rows: k = 16 c + 8 lh .. + 7 of the stage
   f32x4 s[SC == 1 ? 2 : 1][2]; // SC = 1: the scale vector's entries there
   bf16x8 wh[2][2], wl[2][2];   // W fragments [16-k chunk c][32-row block j], hi / lo images
 };
 
-template <int EPI, int SC, int RB>
+template <int EPI, int SC>
 __global__ __launch_bounds__(512) void gemm_x3s_kernel(const SArgs p) {
   constexpr bool GEGLU = EPI == KD_EPI_GEGLU, NORM = SC != 0;
   constexpr int HCOL = GEGLU ? 32 : 64;                          // output columns of a half tile
-  static_assert(RB == 1 || SC != 1, "two row blocks per wave: no registers left for per-lane scale entries");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   f32x4* red = reinterpret_cast<f32x4*>(smem);                                     // [wave][register group q = 4 j + g][lane]
   float* ssqp = reinterpret_cast<float*>(smem + RED_BYTES);                        // [row block][wave][row]
   f32x4* red2 = reinterpret_cast<f32x4*>(smem + RED_BYTES + RB * NW * 32 * 4);     // [row block][q][lane]
   char* strips = smem + RED_BYTES + RB * (NW * 32 * 4 + 8 * 64 * 16);              // [row block] 2 KiB store strip of its epilogue wave
-  const float* scl = reinterpret_cast<const float*>(strips + RB * 2048);           // SC = 2: the sample's scale vector
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ht = blockIdx.x, m0 = blockIdx.y * (32 * RB), n0 = ht * HCOL;
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(512) void gemm_x3s_kernel(const SArgs p) {
   // (the 16-byte loads of a stage are issued in THIS order everywhere -- a sched_barrier behind each: the compiler's counted waits are per
   // register and merged over the paths into a block, so one order keeps them as tight as the program is)
 #define KD_PIN() __builtin_amdgcn_sched_barrier(0)
-  using Stg = Stage<RB, SC>;
+  using Stg = Stage<SC>;
   auto load = [&](Stg& b, int ks) {
     const char* w = wp + (size_t)ks * STG;
     KD_PIN();
@@ -104,14 +105,6 @@ __global__ __launch_bounds__(512) void gemm_x3s_kernel(const SArgs p) {
       }
     }
   };
-
-  // SC = 2: the scale vector of the workgroup's sample, requested AHEAD of the stage loads (its wait then leaves them in flight)
-  f32x4 sv4 = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (SC == 2) {
-    const float* sbase = p.scale + (size_t)(min(m0, p.M - 1) / p.rows_per_sample) * p.scale_stride;
-    if (4 * tid < p.K) sv4 = *reinterpret_cast<const f32x4*>(sbase + 4 * tid);
-    KD_PIN();
-  }
 
   f32x16 acc[RB][2];
 #pragma unroll
@@ -162,11 +155,6 @@ __global__ __launch_bounds__(512) void gemm_x3s_kernel(const SArgs p) {
     for (int c = 0; c < 2; ++c) {
       f32x4 s0, s1;
       if constexpr (SC == 1) { s0 = b.s[c][0]; s1 = b.s[c][1]; }
-      if constexpr (SC == 2) {
-        const float* sc = scl + ks * 32 + 16 * c + 8 * lh;
-        s0 = *reinterpret_cast<const f32x4*>(sc);
-        s1 = *reinterpret_cast<const f32x4*>(sc + 4);
-      }
 #pragma unroll
       for (int r = 0; r < RB; ++r) {
         f32x4 v0 = b.x[r][c][0], v1 = b.x[r][c][1];
@@ -194,18 +182,10 @@ __global__ __launch_bounds__(512) void gemm_x3s_kernel(const SArgs p) {
   // wait counting merge "issued" with "not issued" and wait for everything outstanding at the next use (seen: vmcnt(0) in the loop's first
   // compute()).  sched_barrier: left alone, the instruction scheduler moves both refills behind the second compute() and the next
   // iteration waits for all of them at its top -- a round trip to L2 per pair of stages with nothing in flight ---------------------------------
-  auto park_scale = [&]() {       // (every wave, also one without stages: the barrier is the workgroup's)
-    if constexpr (SC == 2) {
-      if (4 * tid < p.K) *reinterpret_cast<f32x4*>(const_cast<float*>(scl) + 4 * tid) = sv4;
-      __syncthreads();
-    }
-  };
   if (n_my >= 2) {
     Stg b0, b1;
     load(b0, wid);
     load(b1, wid + NW);
-    __builtin_amdgcn_sched_barrier(0);
-    park_scale();
     __builtin_amdgcn_sched_barrier(0);
     int i = 0;
     for (; i + 3 < n_my; i += 2) {
@@ -236,11 +216,7 @@ __global__ __launch_bounds__(512) void gemm_x3s_kernel(const SArgs p) {
     Stg b0;
     load(b0, wid);
     __builtin_amdgcn_sched_barrier(0);
-    park_scale();
-    __builtin_amdgcn_sched_barrier(0);
     compute(b0, wid);
-  } else {
-    park_scale();
   }
 
   // ---- the 8 partial sums of a row block -> its epilogue wave (row block r: wave r), one row block after the other through `red` ------------
@@ -370,19 +346,12 @@ __global__ __launch_bounds__(512) void gemm_x3s_kernel(const SArgs p) {
 }
 
 
-template <int EPI, int SC, int RB>
+template <int EPI, int SC>
 static int launch(const SArgs& a, const char* nm, double flops, double bytes, hipStream_t s) {
   const int hcol = EPI == KD_EPI_GEGLU ? 32 : 64;
   LaunchScope prof(nm, flops, bytes, s);
-  kd::launch<gemm_x3s_kernel<EPI, SC, RB>>(dim3((unsigned)(a.N / hcol), (unsigned)((a.M + 32 * RB - 1) / (32 * RB))), dim3(64 * NW), lds_bytes<RB>(), s, a);
+  kd::launch<gemm_x3s_kernel<EPI, SC>>(dim3((unsigned)(a.N / hcol), (unsigned)((a.M + 32 * RB - 1) / (32 * RB))), dim3(64 * NW), LDS_BYTES, s, a);
   return check_launch("kd_gemm_f32(x3s)");
-}
-// (RB = 2, 64 rows per workgroup with every W fragment feeding two row blocks -- a third less through the L1 per row, half the workgroups --
-// needs 64 accumulators next to 2 x 64 registers of stages in flight: at the 256 registers of two waves per SIMD hipcc spills 50 - 280 of
-// them to scratch.  Not instantiated.)
-template <int EPI>
-static int launch_norm(const SArgs& a, int sc, const char* nm, double flops, double bytes, hipStream_t s) {
-  return sc == 2 ? launch<EPI, 2, 1>(a, nm, flops, bytes, s) : launch<EPI, 1, 1>(a, nm, flops, bytes, s);
 }
 
 }  // namespace x3s
@@ -409,10 +378,8 @@ int gemm_x3s_try(const GemmP& d, hipStream_t s, int* rc) {
   if (d.N % (geglu ? 32 : 64)) return 1;
   if (d.c_split && (!geglu || !d.C_lo)) return 1;
   if (d.out_add != 0.f && d.epi != KD_EPI_STORE) return 1;
-  // variant (option x3s_scale_lds, off): the scale vector through LDS where a workgroup's 32 rows share it.  A quarter less through the L1,
-  // but measured level with the per-lane loads (17.7 / 12.7 / 10.6 against 17.1 / 12.8 / 10.3 us): the kernel waits on latency, not on the L1
   const int rps = d.rows_per_sample > 0 ? d.rows_per_sample : d.M;
-  const int sc = !d.norm ? 0 : (((d.scale_stride == 0 || rps % 32 == 0) && d.K <= SCL_MAX_K && opt(KD_OPT_x3s_scale_lds)) ? 2 : 1);
+  const int sc = d.norm ? 1 : 0;
   const int cus = cu_count();
   const long wgs = (long)((d.M + 31) / 32) * (d.N / (geglu ? 32 : 64));
   const int cap = opt(KD_OPT_x3s_max_wgs);
@@ -436,16 +403,11 @@ int gemm_x3s_try(const GemmP& d, hipStream_t s, int* rc) {
   const double flops = 2.0 * d.M * n_eff * d.K;
   const double bytes = 4.0 * ((double)d.M * d.K + n_eff * d.K + (double)d.M * d.N * (d.epi == KD_EPI_RESIDUAL ? 2 : 1));
   const ProfName nm("gemm_x3s", "gemm_x3s<n%d,e%d> M=%d N=%d K=%d", sc, d.epi, d.M, d.N, d.K);
-  if (opt(KD_OPT_x3s_trace)) {                 // debugging aid (kd_set_option): one line per launch on stderr, the stream drained in front of it
-    fprintf(stderr, "x3s: epi=%d norm=%d M=%d N=%d K=%d rps=%d stride=%d heads=%d packed=%d c_split=%d A=%p Wp=%p C=%p R=%p scale=%p pos=%p freq=%p\n", d.epi, d.norm, d.M, d.N, d.K,
-            a.rows_per_sample, a.scale_stride, a.n_heads, a.qkv_packed, a.c_split, (const void*)a.A, (const void*)a.Wp, (void*)a.C, (const void*)a.R, (const void*)a.scale, (const void*)a.pos, (const void*)a.freq);
-    (void)hipStreamSynchronize(s);
-  }
-  if (d.epi == KD_EPI_STORE && d.norm) *rc = launch_norm<KD_EPI_STORE>(a, sc, nm, flops, bytes, s);
-  else if (d.epi == KD_EPI_STORE) *rc = launch<KD_EPI_STORE, 0, 1>(a, nm, flops, bytes, s);
-  else if (d.epi == KD_EPI_RESIDUAL && !d.norm && d.R) *rc = launch<KD_EPI_RESIDUAL, 0, 1>(a, nm, flops, bytes, s);
-  else if (d.epi == KD_EPI_QKV && d.norm && d.rope_pos && d.rope_freq) *rc = launch_norm<KD_EPI_QKV>(a, sc, nm, flops, bytes, s);
-  else if (geglu && d.norm) *rc = launch_norm<KD_EPI_GEGLU>(a, sc, nm, flops, bytes, s);
+  if (d.epi == KD_EPI_STORE && d.norm) *rc = launch<KD_EPI_STORE, 1>(a, nm, flops, bytes, s);
+  else if (d.epi == KD_EPI_STORE) *rc = launch<KD_EPI_STORE, 0>(a, nm, flops, bytes, s);
+  else if (d.epi == KD_EPI_RESIDUAL && !d.norm && d.R) *rc = launch<KD_EPI_RESIDUAL, 0>(a, nm, flops, bytes, s);
+  else if (d.epi == KD_EPI_QKV && d.norm && d.rope_pos && d.rope_freq) *rc = launch<KD_EPI_QKV, 1>(a, nm, flops, bytes, s);
+  else if (geglu && d.norm) *rc = launch<KD_EPI_GEGLU, 1>(a, nm, flops, bytes, s);
   else return 1;
   return 0;
 }

@@ -22,12 +22,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXISTING = {
     "x3s_max_rows": ("tests/test_ops_gpu.py", "test_split3_few_rows_latency_kernel"),
     "x3s_max_wgs": ("tests/test_ops_gpu.py", "test_split3_few_rows_latency_kernel"),
-    "x3s_scale_lds": ("tests/test_ops_gpu.py", "test_split3_few_rows_latency_kernel"),
     "b16s_max_rows": ("tests/test_ops_gpu.py", "test_bf16_few_rows_latency_kernel"),
     "b16s_max_wgs": ("tests/test_ops_gpu.py", "test_bf16_few_rows_latency_kernel"),
     "ffn_fused_256": ("tests/test_ops_gpu.py", "test_bf16_fused_ffn_width_256"),
     "attn_x3": ("tests/test_ops_gpu.py", "test_split_stored_qkv_feeds_the_attention_cores"),
-    "astat_waves": ("tests/test_ops_gpu.py", "test_wide_projections_a_stationary"),
     "x3r_split": ("tests/test_ops_gpu.py", "test_token_split_multi_tile"),
     "x3_unpatch": ("tests/test_ops_gpu.py", "test_split3_patch_out_round3"),
     "x3_res": ("tests/test_ops_gpu.py", "test_split3_residual_projection_round3"),
@@ -39,7 +37,6 @@ EXISTING = {
 EXEMPT = {
     "code_warm": "how many workgroups pre-read the kernel's code into the L2; tests/test_model_gpu.py shows it changes no result",
     "gemm_debug": "benchmarks/ only: removes stores / MFMAs / erf for timing ablations, the results are not the op's",
-    "x3s_trace": "prints one line per launch on stderr",
 }
 
 
@@ -53,14 +50,14 @@ def _test_source(path, test):
 
 def test_every_option_is_forced_by_a_row_or_accounted_for():
     names = source_options()
-    assert {"x3_splits", "astat_splits", "mx8_splits", "tiled_bm", "wstat_waves", "ffn_variant", "attn_global_qw"} <= names
+    assert {"x3_splits", "astat_splits", "mx8_splits", "tiled_bm", "attn_global_qw"} <= names
     forced = lc.forced_options()
     unaccounted = sorted(n for n in names if n not in forced and n not in EXISTING and n not in EXEMPT)
     assert not unaccounted, f"options no test forces around a launch (add a row to tests/test_launch_config_gpu.py): {unaccounted}"
     stale = sorted((set(EXISTING) | set(EXEMPT)) - names)
     assert not stale, f"entries for options the sources no longer read: {stale}"
     assert not set(EXEMPT) & (forced | set(EXISTING))
-    assert set(EXEMPT) == {"code_warm", "gemm_debug", "x3s_trace"}          # the list does not grow quietly
+    assert set(EXEMPT) == {"code_warm", "gemm_debug"}          # the list does not grow quietly
     for name, (path, test) in EXISTING.items():
         src = _test_source(path, test)
         assert src is not None, f"{path}::{test} does not exist"
@@ -141,7 +138,7 @@ def test_restated_split_rule():
     assert lc.best_n_splits(8, 12, 512, 2) == 12 and lc.best_n_splits(512, 12, 512, 2) == 1 and lc.best_n_splits(9, 6, 256, 1) == 6
     assert lc.best_n_splits(300, 4, 256, 1) == 2          # rounds x (1 + tiles): 2 x 5, 3 x 3, 5 x 2
     assert lc.tiled_cfg(300, 256, 1536, 128, 1)(256) == "bm128,lw1,deep1" and lc.tiled_cfg(300, 256, 1536, 256, 1)(256) == "bm256,lw0,deep0"
-    assert lc.tiled_cfg(300, 256, 256, 128, 1)(256) == "bm128,lw0,deep0" and lc.tiled_cfg(300, 256, 256, deep=1)(256) == "bm128,lw0,deep1"
+    assert lc.tiled_cfg(300, 256, 256, 128, 1)(256) == "bm128,lw0,deep0"
     assert lc.tiled_cfg(65536, 256, 256)(256) == "bm256,lw0,deep0"
 
 

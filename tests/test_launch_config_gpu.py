@@ -66,14 +66,14 @@ def best_n_splits(panels, n_tiles, slots, prologue_weight):
     return best
 
 
-def tiled_cfg(M, N, K, bm=0, lw=1, deep=0):
+def tiled_cfg(M, N, K, bm=0, lw=1):
     """gemm_bf16.hip: gemm_tiled_try.  The loader-wave form needs 128-row tiles, at most one tile per CU and K >= 768, and runs on the deep ring."""
     def f(cus):
         t128, t256 = -(-M // 128) * -(-N // 128), -(-M // 256) * -(-N // 128)
         big = bm == 256 if bm else t256 >= cus
         one_round = not big and t128 <= cus
         use_lw = bool(one_round and K >= 768 and lw)
-        return f"bm{256 if big else 128},lw{int(use_lw)},deep{int(use_lw or bool(one_round and deep))}"
+        return f"bm{256 if big else 128},lw{int(use_lw)},deep{int(use_lw)}"
     return f
 
 
@@ -202,35 +202,14 @@ for _M, _B in ((2048, 4), (2080, 5)):           # behind a norm a 32-row chunk i
     AUTO.append(Row(lin("norm_ps", _M, 288, 512, None, "gemm_bf16_wstat", B16, bf=True, B=_B), {}, f"gemm_bf16_wstat<e{E_STORE},n1>", "waves8,pf0,slices3"))
 
 # ---- request-only variants ------------------------------------------------------------------------------------------------------------------------
-_W = f"gemm_bf16_wstat<e{E_STORE},n0>"
 _plain_ws = lin("plain", 2075, 640, 128, None, None, None, bf=True)
-_geglu_ws = lin("norm_geglu_ps", 2080, 320, 128, None, "gemm_bf16_wstat", B16, bf=True, B=5)
-_qkv_ws = qkv(2048, 2, 128, None, "gemm_bf16_wstat<e5,n1>", B16, bf=True)
 _astat_b = lin("norm_ps", 1000, 512, 256, None, "gemm_bf16_astat", B16, bf=True)
 _x3_store = lin("norm", 1000, 512, 128, "split3", "gemm_x3_astat", X3)
 _qkv_256 = qkv(1000, 4, 256, "split3", "gemm_x3_astat<e5,h>", X3)
 _geglu_256 = lin("norm_geglu_ps", 1100, 384, 256, "split3", "gemm_x3_astat", X3)
-for _M in (300, 520):
-    REQUEST.append(Row(lin("plain", _M, 256, 256, None, None, None, bf=True), {"tiled_deep": 1}, f"gemm_bf16_tiled<a0,e{E_STORE}>", tiled_cfg(_M, 256, 256, deep=1)))
 REQUEST += [
-    # the 256-row / 8-wave panels of the bf16 a-stationary kernel, with the cost model's split count and with a forced one
-    Row(_astat_b, {"astat_rows": 256}, f"gemm_bf16_astat<e{E_STORE}>", lambda cus: f"rows256,splits{best_n_splits(4, 4, cus, 1)}"),
-    Row(_astat_b, {"astat_rows": 256, "astat_splits": 2}, f"gemm_bf16_astat<e{E_STORE}>", "rows256,splits2"),
-    Row(lin("norm_geglu_ps", 1024, 384, 512, None, "gemm_bf16_astat", B16, bf=True), {"astat_rows": 256, "astat_splits": 3}, f"gemm_bf16_astat<e{E_GEGLU}>", "rows256,splits3"),
-    # wave counts and the prefetch forms of the W-stationary kernel (2 = software-pipelined tiles: qkv / GEGLU at K = 128 only, elsewhere it means 1)
-    Row(_plain_ws, {"wstat_waves": 4}, _W, "waves4,pf0,slices2"),
-    Row(_plain_ws, {"wstat_waves": 12}, _W, "waves12,pf0,slices2"),
-    Row(lin("norm_ps", 2080, 288, 256, None, "gemm_bf16_wstat", B16, bf=True, B=5), {"wstat_waves": 4}, f"gemm_bf16_wstat<e{E_STORE},n1>", "waves4,pf0,slices2"),
-    Row(_plain_ws, {"wstat_prefetch": 1}, _W, "waves8,pf1,slices2"),
-    Row(_plain_ws, {"wstat_prefetch": 2}, _W, "waves8,pf1,slices2"),
-    Row(_geglu_ws, {"wstat_prefetch": 1}, f"gemm_bf16_wstat<e{E_GEGLU},n1>", "waves8,pf1,slices2"),
-    Row(_geglu_ws, {"wstat_prefetch": 2}, f"gemm_bf16_wstat<e{E_GEGLU},n1>", "waves8,pf2,slices2"),
-    Row(_qkv_ws, {"wstat_prefetch": 2}, f"gemm_bf16_wstat<e{E_QKV},n1>", "waves8,pf2,slices1"),
-    Row(_qkv_ws, {"wstat_prefetch": 2, "wstat_waves": 12}, f"gemm_bf16_wstat<e{E_QKV},n1>", "waves12,pf2,slices1"),
     Row(_plain_ws, {"wstat_max_slices": 1}, f"gemm_bf16_tiled<a0,e{E_STORE}>"),                # two slices refused: the tiled kernel serves the shape
     # the fused feed-forward forms
-    Row(built(tb._ffn, "ffn[bf16,B2,T300,K128,dff128]", (2, 300), 128, 128, True, kernel="ffn_bf16"), {"ffn_variant": 3}, "ffn_bf16 ", "variant3"),
-    Row(built(tb._ffn, "ffn[bf16,B1,T130,K128,dff64]", (1, 130), 128, 64, True, kernel="ffn_bf16"), {"ffn_variant": 3}, "ffn_bf16 ", "variant3"),
     Row(built(tb._ffn, "ffn[split3,30x30,B3,K128,dff192]", (3, 30, 30), 128, 192, False, kernel="ffn_x3"), {"ffn_x3_half": 0}, "ffn_x3 ", "half0"),
     Row(built(tb._ffn, "ffn[split3,25x44,B1,K128,dff384]", (1, 25, 44), 128, 384, False, kernel="ffn_x3"), {"ffn_x3_half": 0}, "ffn_x3 ", "half0"),
     # patch-in / patch-out without the 4 x 4 patch kernels
@@ -276,8 +255,6 @@ REQUEST += [
     Row(_res_x3r, {"x3r": 0}, f"gemm_bf16x3<a0,n0,e{E_RES}"),
     Row(_att_pk, {}, "attn_global_x3"),
     Row(_att_pk, {"attn_x3": 0}, "attn_global_bf16x3"),
-    # 256-row panels of the round-1 a-stationary kernel: only from 256 such panels on
-    Row(lin("norm", 65536, 256, 128, "split3", None, None), {"x3": 0, "astat_waves": 8}, f"gemm_astat<e{E_STORE}>", "splits1,waves8"),
 ]
 
 # ---- switches that act through a predicate of the C ABI: (options, predicate, arguments, answer by default, answer with the options) -------------------
@@ -407,7 +384,7 @@ PLAN_ROWS = [
     PlanRow("na128_g256", "split3", 2, {"attn_ffn_x3": 0}, [_L0 + "attn_na2d+ff", "up_levels.0.0.attn_na2d+ff"], [_L0 + "attn_na2d", _L0 + "ff", "up_levels.0.0.ff"],
             ["+ff", _L0 + "out_proj"], ["attn_na2d_x3", "ffn_x3+out"], ["attn_ffn_x3"]),
     PlanRow("na128_g256", "split3", 2, {"ffn_x3": 0}, [_L0 + "attn_na2d+ff"], [_L0 + "attn_na2d", _L0 + "out_proj", _L0 + "up_proj", _L0 + "down_proj", "up_levels.0.0.up_proj"],
-            ["+ff", ".ff"], [(f"gemm_x3_astat<e{E_GEGLU}>", f"gemm_x3s<n1,e{E_GEGLU}>", f"gemm_x3s<n2,e{E_GEGLU}>")], ["attn_ffn_x3", "ffn_x3"]),
+            ["+ff", ".ff"], [(f"gemm_x3_astat<e{E_GEGLU}>", f"gemm_x3s<n1,e{E_GEGLU}>")], ["attn_ffn_x3", "ffn_x3"]),
     # split3, width 256: the fused FF block from ffn_x3_min_panels_256 row panels on (default: 7/8 of the CUs); the mid level has 4 at batch 2
     PlanRow("na128_g256", "split3", 2, {"ffn_x3_min_panels_256": 4}, [_MID + "up_proj", _MID + "down_proj"], [_MID + "ff"], [_MID + "up_proj", _MID + "out_proj"], ["ffn_x3+out M=512 K=256"], []),
     PlanRow("na128_g256", "split3", 2, {"ffn_x3_min_panels_256": 5}, [_MID + "up_proj"], [_MID + "up_proj", _MID + "down_proj", _MID + "out_proj"], [_MID + "ff"], [], ["ffn_x3+out M=512 K=256", "ffn_x3 M=512 K=256"]),
