@@ -10,6 +10,9 @@ forward on the device (torch's conv / group-norm / SDPA kernels, depthwise resam
     rocprofv3 --kernel-trace --stats -d <dir> -- python benchmarks/unet_bench.py --profile cifar
 ``--dual`` instead times the dual (primal + tangent) pass ``forward_jvp`` of ``log_likelihood`` at batch B against the forward at batch B and
 the forward at batch 2 B (the dual pass stacks the tangent behind the primal: 2 B samples in every buffer), same warm-up and sampling.
+``--vjp`` instead times the reverse pass at batch B -- ``forward_vjp`` plus one ``pullback`` -- against the plain forward at batch B and against
+``forward_vjp`` alone (the primal on tensors of its own), same warm-up and sampling; after the timed samples one more reverse pass runs under the
+library's per-launch events, and the line carries the time per kernel name (where the reverse pass's time goes).
 Prints one JSON line per model.
 """
 import argparse
@@ -53,12 +56,28 @@ def timed(fn):
     return e0.elapsed_time(e1)
 
 
+def kernel_ms():
+    """The library's per-launch event times since the last reset, summed per kernel name: {name: [launches, ms]}."""
+    import ctypes as C
+    import k_diffusion_amd as K
+    lib = K._native.lib()
+    out, name, ms, fl, by = {}, C.create_string_buffer(128), C.c_float(), C.c_double(), C.c_double()
+    for i in range(lib.kd_prof_count()):
+        K._native.check(lib.kd_prof_get(i, name, 128, C.byref(ms), C.byref(fl), C.byref(by)), "kd_prof_get")
+        ent = out.setdefault(name.value.decode().split(" ")[0], [0, 0.0])
+        ent[0] += 1
+        ent[1] += ms.value
+    lib.kd_prof_reset()
+    return {k: [n, round(t, 4)] for k, (n, t) in sorted(out.items(), key=lambda kv: -kv[1][1])}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", choices=sorted(MODELS))
     ap.add_argument("--models", nargs="*", default=["cifar", "mnist"])
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--dual", action="store_true")
+    ap.add_argument("--vjp", action="store_true")
     args = ap.parse_args()
     import k_diffusion_amd as K
     from tests import unet_ref as ur
@@ -98,6 +117,28 @@ def main():
                         times[k].append(timed(fn))
                 line = {"model": name, "batch": B, **{k: [statistics.median(t), min(t), max(t)] for k, t in times.items()},
                         "dual_launches": len(model.inner_model._plan(B, H, W, x.device, dual=True).calls) + 8}
+                print(json.dumps(line), flush=True)
+                continue
+            if args.vjp:
+                u = (torch.randint(0, 2, x.shape, generator=g).float() * 2 - 1).to(dev)
+                sides = {"forward_ms": hip, "primal_ms": lambda: model.forward_vjp(x, sigma, aug_cond=aug),
+                         "vjp_ms": lambda: model.forward_vjp(x, sigma, aug_cond=aug)[1](u)}
+                for _ in range(10):
+                    for fn in sides.values():
+                        fn()
+                torch.cuda.synchronize()
+                times = {k: [] for k in sides}
+                for _ in range(7):
+                    for k, fn in sides.items():
+                        times[k].append(timed(fn))
+                line = {"model": name, "batch": B, **{k: [statistics.median(t), min(t), max(t)] for k, t in times.items()}}
+                line["vjp_over_forward"] = line["vjp_ms"][0] / line["forward_ms"][0]
+                K._native.prof_enable(True)
+                K._native.lib().kd_prof_reset()
+                sides["vjp_ms"]()
+                torch.cuda.synchronize()
+                line["vjp_kernel_ms"] = kernel_ms()
+                K._native.prof_enable(False)
                 print(json.dumps(line), flush=True)
                 continue
             sd_dev = ur.prepare(sd, torch.float32, dev)

@@ -11,6 +11,7 @@ from ._abi import HeaderError, parse
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KDIFF_HIP_LIB") or os.path.join(_HERE, "csrc", "libkdiff_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_hip.h")
+GRAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_grad.h")
 
 
 class NativeLibraryError(RuntimeError):
@@ -32,6 +33,16 @@ globals().update({name[3:]: value for name, value in _parsed.constants.items()})
 RUN_LIST_OPS = {"kd_" + name[6:].lower(): value for name, value in _parsed.constants.items() if name.startswith("KD_OP_")}
 if not set(RUN_LIST_OPS) <= set(SIGNATURES):
     raise HeaderError(f"KD_OP_* without an entry point: {sorted(set(RUN_LIST_OPS) - set(SIGNATURES))}")
+# The U-Net's reverse kernels (csrc/unet_vjp_f32.hip) are declared in a header of their own, read by the same parser into a table of their
+# own: prototypes only, and no kd_run_list entry can name them
+try:
+    with open(GRAD_HEADER_PATH) as _header:
+        _grad = parse(_header.read())
+except OSError as e:
+    raise NativeLibraryError(f"{GRAD_HEADER_PATH}: the C ABI header the package binds from cannot be read ({e})") from e
+if _grad.structs or _grad.constants or set(_grad.signatures) & set(SIGNATURES):
+    raise HeaderError(f"{GRAD_HEADER_PATH}: prototypes of entry points kdiff_hip.h does not declare, and nothing else")
+GRAD_SIGNATURES, GRAD_RESTYPES = _grad.signatures, _grad.restypes
 _i, _f = C.c_int, C.c_float                  # the kinds encode_call tells apart (the parser hands out these very objects)
 
 # PREC_FP8 is a mode of the NETWORK, not a KdGemm.precision value: the bf16 mode with the AdaRMSNorm -> wide projections of the K = 256 / 512
@@ -111,13 +122,14 @@ def lib():
                 "(python -c 'import __graft_entry__ as g; g.build()' or make -C k-diffusion_amd/csrc). "
                 "There is no CPU / PyTorch fallback for the sampling hot path.")
         handle = C.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as e:
-                raise NativeLibraryError(f"{LIB_PATH} does not export {name}") from e
-            fn.argtypes = argtypes
-            fn.restype = RESTYPES[name]
+        for signatures, restypes in ((SIGNATURES, RESTYPES), (GRAD_SIGNATURES, GRAD_RESTYPES)):
+            for name, argtypes in signatures.items():
+                try:
+                    fn = getattr(handle, name)
+                except AttributeError as e:
+                    raise NativeLibraryError(f"{LIB_PATH} does not export {name}") from e
+                fn.argtypes = argtypes
+                fn.restype = restypes[name]
         _lib = handle
     _sync_options(_lib)
     return _lib

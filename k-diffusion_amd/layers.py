@@ -162,6 +162,30 @@ class Denoiser(nn.Module):
         return ops.precond_out(f.contiguous(), x, sigma, self.sigma_data), ops.precond_out(fd.contiguous(), xd, sigma, self.sigma_data)
 
 
+    def forward_vjp(self, input, sigma, **kwargs):
+        """(D(input, sigma), pullback) in the shape of ``torch.func.vjp``: ``pullback(grad_out)`` = J_D^T grad_out w.r.t. ``input``, sigma and
+        the conditioning held fixed (gradient guidance: the gradient of a loss on the denoised image).  A native inner model runs its own
+        ``forward_vjp`` with the preconditioning folded in; a foreign inner model needs a ``forward_vjp(x, sigma, **kwargs) -> (F, pullback)``
+        of its own, and the preconditioning -- linear in x -- goes through ``ops.precond_in`` / ``precond_out`` forward and
+        ``ops.precond_vjp`` backward."""
+        inner = self.inner_model
+        rule = getattr(inner, 'forward_vjp', None)
+        if rule is None:
+            raise NotImplementedError(f'Denoiser.forward_vjp: the inner model {type(inner).__name__} has no forward_vjp rule (a reverse-mode '
+                                      f'VJP rule is needed for input gradients on the HIP path)')
+        if getattr(inner, 'forward_preconditioned', None) is not None:
+            return rule(input, sigma, sigma_data=self.sigma_data, **kwargs)
+        sigma = sigma.to(device=input.device, dtype=torch.float32).reshape(-1).expand(input.shape[0]).contiguous()
+        x = input.contiguous()
+        f, inner_pullback = rule(ops.precond_in(x, sigma, self.sigma_data), sigma, **kwargs)
+
+        def pullback(grad_out):
+            go = grad_out.contiguous()
+            g = inner_pullback(ops.precond_vjp(go, ops.nat.PC_OUT, sigma, self.sigma_data))
+            return ops.precond_vjp(g.contiguous(), ops.nat.PC_IN, sigma, self.sigma_data, h=go, h_coef=ops.nat.PC_SKIP)
+        return ops.precond_out(f.contiguous(), x, sigma, self.sigma_data), pullback
+
+
 class DenoiserWithVariance(Denoiser):
     """What ``make_denoiser_wrapper`` returns for ``has_variance`` configs (config.py:223-224; layers.py:93-101).  The reference's class
     overrides ``loss`` only (the model's log-variance output is a training quantity): ``forward`` / ``get_scalings`` -- the sampling path --

@@ -16,8 +16,11 @@ kernel launches over fp32 NHWC token buffers ``[B H W, C]``, built once per (bat
   primal: the linear kernels run once over both, a stacked convolution gives its bias to the primal samples only
   (``kd_conv2d_x3_stacked``), AdaGN has dual kernels (``kd_groupnorm_stats_jvp_f32``, ``kd_adagn_apply_jvp_f32``) and attention is
   ``ops.attn_global_jvp``.  Its primal output has the forward's bits.
+* ``forward_vjp`` (gradient guidance: the gradient of a loss on the output w.r.t. the input) returns the output with the forward's bits and a
+  pullback; the reverse walk and its recomputation are ``models/unet_vjp.py``, its AdaGN and resampling rules ``csrc/unet_vjp_f32.hip``.
 
-Scope: the forward pass and its forward-mode derivative in fp32-grade (split-bf16x3) arithmetic whatever ``KDIFF_GEMM`` says, ``patch_size == 1``, ``skip_stages == 0``, no
+Scope: the forward pass, its forward-mode derivative and its reverse-mode derivative w.r.t. the input (explicit methods: ``forward_jvp``,
+``forward_vjp``; nothing runs behind autograd, and sigma, the conditioning and the weights get no gradient) in fp32-grade (split-bf16x3) arithmetic whatever ``KDIFF_GEMM`` says, ``patch_size == 1``, ``skip_stages == 0``, no
 variance output, no cross attention, no ``unet_cond``, channels that are multiples of 64, even H and W at every downsample.  Anything else is
 refused in the constructor; training (grad mode with something that requires grad) raises NotImplementedError.
 """
@@ -122,6 +125,16 @@ class _MappingNet(nn.Sequential):
         super().__init__(*mods)
 
 
+def level_sizes(model, H, W):
+    """(H, W) of every level of an H x W input; refuses a size that some downsample cannot halve."""
+    n = len(model.depths)
+    sizes = [(H >> i, W >> i) for i in range(n)]
+    for i in range(n - 1):
+        if sizes[i][0] % 2 or sizes[i][1] % 2 or min(sizes[i]) < 2:
+            raise ValueError(f"image_v1: input size {H}x{W}: level {i} is {sizes[i][0]}x{sizes[i][1]}, which the downsample cannot halve")
+    return sizes
+
+
 class _Plan:
     """Buffers and the fixed launch list of one (batch, H, W): ``head`` / ``tail`` take the call's own tensors, ``calls`` is everything between.
 
@@ -132,10 +145,7 @@ class _Plan:
 
     def __init__(self, model, B, H, W, device, dual=False):
         n, ch = len(model.depths), model.channels
-        sizes = [(H >> i, W >> i) for i in range(n)]
-        for i in range(n - 1):
-            if sizes[i][0] % 2 or sizes[i][1] % 2 or min(sizes[i]) < 2:
-                raise ValueError(f"image_v1: input size {H}x{W}: level {i} is {sizes[i][0]}x{sizes[i][1]}, which the downsample cannot halve")
+        sizes = level_sizes(model, H, W)
         f32 = dict(device=device, dtype=torch.float32)
         feats = model.feats_in
         self.B, self.calls, pool = B, [], {}
@@ -264,8 +274,8 @@ class _Plan:
 
 class AugmentWrapperV1(KarrasAugmentWrapper):
     """``KarrasAugmentWrapper`` around the U-Net (config.py:169-170) that also hands ``Denoiser.forward`` the inner model's fused
-    ``forward_preconditioned`` -- and ``Denoiser.forward_jvp`` its ``forward_jvp`` -- with the same conditioning rule: ``aug_cond`` (zeros
-    [B, 9] when none is given) in front of ``mapping_cond``."""
+    ``forward_preconditioned`` -- and ``Denoiser.forward_jvp`` / ``forward_vjp`` its ``forward_jvp`` / ``forward_vjp`` -- with the same
+    conditioning rule: ``aug_cond`` (zeros [B, 9] when none is given) in front of ``mapping_cond``."""
 
     def forward_preconditioned(self, input, sigma, sigma_data, aug_cond=None, mapping_cond=None, **kwargs):
         cond = input.new_zeros([input.shape[0], 9]) if aug_cond is None else aug_cond
@@ -281,9 +291,17 @@ class AugmentWrapperV1(KarrasAugmentWrapper):
         return self.inner_model.forward_jvp(input, sigma, tangent, mapping_cond=cond, sigma_data=sigma_data, **kwargs)
 
 
+    def forward_vjp(self, input, sigma, sigma_data=None, aug_cond=None, mapping_cond=None, **kwargs):
+        """The inner model's ``forward_vjp`` under the conditioning rule of ``forward_preconditioned``."""
+        cond = input.new_zeros([input.shape[0], 9]) if aug_cond is None else aug_cond
+        if mapping_cond is not None:
+            cond = torch.cat([cond, mapping_cond], dim=1)
+        return self.inner_model.forward_vjp(input, sigma, mapping_cond=cond, sigma_data=sigma_data, **kwargs)
+
+
 class ImageDenoiserModelV1(nn.Module):
-    """image_v1.py:89-176 with the reference's constructor signature, attributes, state_dict and ``param_groups``; the forward and its
-    forward-mode derivative, no backward pass (see the module docstring for the scope)."""
+    """image_v1.py:89-176 with the reference's constructor signature, attributes, state_dict and ``param_groups``; the forward, its
+    forward-mode derivative and its input gradient as explicit methods, no autograd backward pass (see the module docstring for the scope)."""
 
     def __init__(self, c_in, feats_in, depths, channels, self_attn_depths, cross_attn_depths=None, mapping_cond_dim=0, unet_cond_dim=0,
                  cross_cond_dim=0, dropout_rate=0., patch_size=1, skip_stages=0, has_variance=False):
@@ -330,6 +348,7 @@ class ImageDenoiserModelV1(nn.Module):
         self._watch, self._plan_cache, self._fingerprint = weights.WeightWatch(self), weights.PlanCache(), None
         self._plans = self._plan_cache.plans
         self._dual_cache = weights.PlanCache()         # the dual pass's plans: forward_jvp leaves ``_plans`` and its eviction order alone
+        self._vjp_cache, self._vjp_fingerprint = weights.PlanCache(), None       # forward_vjp's weight-derived tensors (models/unet_vjp.py)
 
     def param_groups(self, base_lr=2e-4):
         """image_v1.py:117-133: the weights of ``mapping`` and ``u_net`` decay, everything else does not."""
@@ -370,8 +389,9 @@ class ImageDenoiserModelV1(nn.Module):
         cache = self._dual_cache if dual else self._plan_cache
         return cache.get(key) or cache.put(key, lambda: _Plan(self, B, H, W, device, dual), MAX_PLANS)
 
-    def _run(self, input, sigma, mapping_cond, sigma_data, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False,
-             tangent=None, dual=False):
+    def _refuse(self, input, sigma, mapping_cond, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False, tangent=None,
+                dual=False):
+        """The refusals of every pass (forward, dual, reverse): what the HIP path does not take, by name."""
         if unet_cond is not None or cross_cond is not None or cross_cond_padding is not None or return_variance:
             raise ValueError("image_v1: unet_cond, cross_cond and return_variance are not supported on the HIP path")
         tensors = [t for t in (input, sigma, mapping_cond, tangent) if isinstance(t, torch.Tensor)]
@@ -399,19 +419,28 @@ class ImageDenoiserModelV1(nn.Module):
                 raise RuntimeError(f"image_v1: tangent is on {tangent.device}, input on {input.device}")
             if tangent.dtype != torch.float32:
                 raise TypeError(f"image_v1: tangent is fp32 like the input (got {tangent.dtype})")
+
+    def _cond_table(self, sigma, mapping_cond, B, device, ws):
+        """The conditioning of one call: Fourier features of sigma (+ mapping_cond), the mapping network, and every AdaGN mapper's (weight,
+        bias) pair into ``ws.table``.  ``ws`` holds the buffers ff, e, h1, h2, table and the concatenated mapper weight map_w / map_b."""
+        e = ops.fourier_sigma(sigma, self.timestep_embed.weight, out=ws.ff)
+        if mapping_cond is not None:
+            mc = mapping_cond.to(device=device, dtype=torch.float32).contiguous()
+            if tuple(mc.shape) != (B, self.mapping_cond.weight.shape[1]):
+                raise ValueError(f"image_v1: mapping_cond is [{B}, {self.mapping_cond.weight.shape[1]}] (got {tuple(mc.shape)})")
+            e = uo.cond_mlp(mc, self.mapping_cond.weight, add=ws.ff, out=ws.e)
+        h = uo.cond_mlp(e, self.mapping[0].weight, self.mapping[0].bias, gelu=True, out=ws.h1)
+        h = uo.cond_mlp(h, self.mapping[2].weight, self.mapping[2].bias, gelu=True, out=ws.h2)
+        return uo.cond_mlp(h, ws.map_w, ws.map_b, out=ws.table)
+
+    def _run(self, input, sigma, mapping_cond, sigma_data, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False,
+             tangent=None, dual=False):
+        self._refuse(input, sigma, mapping_cond, unet_cond, cross_cond, cross_cond_padding, return_variance, tangent, dual)
         x = input.contiguous()
         B, _, H, W = x.shape
         sigma = sigma.to(device=x.device, dtype=torch.float32).reshape(-1).expand(B).contiguous()
         plan = self._plan(B, H, W, x.device, dual)
-        e = ops.fourier_sigma(sigma, self.timestep_embed.weight, out=plan.ff)
-        if mapping_cond is not None:
-            mc = mapping_cond.to(device=x.device, dtype=torch.float32).contiguous()
-            if tuple(mc.shape) != (B, self.mapping_cond.weight.shape[1]):
-                raise ValueError(f"image_v1: mapping_cond is [{B}, {self.mapping_cond.weight.shape[1]}] (got {tuple(mc.shape)})")
-            e = uo.cond_mlp(mc, self.mapping_cond.weight, add=plan.ff, out=plan.e)
-        h = uo.cond_mlp(e, self.mapping[0].weight, self.mapping[0].bias, gelu=True, out=plan.h1)
-        h = uo.cond_mlp(h, self.mapping[2].weight, self.mapping[2].bias, gelu=True, out=plan.h2)
-        uo.cond_mlp(h, plan.map_w, plan.map_b, out=plan.table)
+        self._cond_table(sigma, mapping_cond, B, x.device, plan)
         pre = sigma_data is not None
         scale = dict(sigma=sigma if pre else None, sigma_data=sigma_data if pre else 1.0)
         rows = B * H * W
@@ -442,3 +471,12 @@ class ImageDenoiserModelV1(nn.Module):
         ``likelihood.log_likelihood`` call.  One dual pass over [primal | tangent] buffers (``_Plan``); it builds no autograd graph, and the
         refusals are the forward's."""
         return self._run(input, sigma, mapping_cond, None if sigma_data is None else float(sigma_data), tangent=tangent, dual=True, **kwargs)
+
+    def forward_vjp(self, input, sigma, mapping_cond=None, sigma_data=None, **kwargs):
+        """(out, pullback) in the shape of ``torch.func.vjp``: out = F(input, sigma) -- or D(input, sigma) with ``sigma_data``, folded in as in
+        ``forward_preconditioned`` -- with the forward's bits, and ``pullback(grad_out)`` = J^T grad_out w.r.t. ``input``, sigma, the
+        conditioning and the weights held fixed: what ``Denoiser.forward_vjp`` and gradient guidance call.  The pullback may be called more
+        than once; it raises if the weights changed since the primal.  The reverse walk is ``models/unet_vjp.py``; it builds no autograd
+        graph and touches no launch plan, and the refusals are the forward's."""
+        from . import unet_vjp
+        return unet_vjp.forward_vjp(self, input, sigma, mapping_cond, sigma_data, **kwargs)

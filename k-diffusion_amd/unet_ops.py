@@ -1,5 +1,6 @@
 """Tensor-level wrappers over the C ABI of the image_v1 U-Net kernels (csrc/conv_x3.hip, csrc/unet_f32.hip; contracts: include/kdiff_hip.h)
--- the module's counterpart of ``ops``, as ``augmentation`` and ``data`` have theirs.
+and of their reverse rules (csrc/unet_vjp_f32.hip; contracts: include/kdiff_unet_grad.h) -- the module's counterpart of ``ops``, as
+``augmentation`` and ``data`` have theirs.
 
 Activations are fp32 NHWC, token-major: a 2-D tensor ``[B * H * W, C]`` whose row stride may exceed C (a column range of a wider buffer:
 ``buf[:, :C]`` and ``buf[:, C:]`` are the two halves of a skip concatenation, written in place by their producers).  Column 0 of such a view
@@ -201,3 +202,107 @@ def cond_mlp(x, weight, bias=None, add=None, gelu=False, out=None):
     nat.check(nat.lib().kd_cond_mlp_f32(_p(x), _p(weight), _p(None if bias is None else _chk(bias, "bias")), _p(add), _p(out), R, N, K,
                                         int(bool(gelu)), _stream()), "kd_cond_mlp_f32")
     return out
+
+
+# ---- reverse rules w.r.t. the activations (csrc/unet_vjp_f32.hip): what ``ImageDenoiserModelV1.forward_vjp`` walks back through ----------------------
+
+def pack_conv_dgrad(weight, q_rows=0):
+    """Packed image (``pack_conv``'s) of the weight of a convolution's DATA gradient: w'[ci, co, ky, kx] = w[co, ci, ks-1-ky, ks-1-kx], so that
+    g_x = conv2d(g_y, w', padding=ks // 2) for a stride-1 convolution with zero padding ks // 2.  ``q_rows``: the first q_rows output channels
+    of w carry a folded 1 / 8 (the q rows of a qkv projection, as the forward packs them).  Cached per tensor object and ``q_rows``."""
+    def build():
+        if _chk(weight, "weight").dim() != 4 or weight.shape[2] != weight.shape[3]:
+            raise ValueError(f"pack_conv_dgrad: weight is [C_out, C_in, ks, ks] (got {tuple(weight.shape)})")
+        w = weight.detach()
+        if q_rows:
+            w = w.clone()
+            w[:q_rows] *= 0.125
+        return pack_conv(w.flip(2, 3).transpose(0, 1).contiguous(), cache=False)
+    return _packed.get(weight, ("dgrad", int(q_rows)), None, build)
+
+
+def conv2d_dgrad(g_y, weight, B, H, W, residual=None, out=None, q_rows=0):
+    """g_x [B*H*W, C_in] = the data gradient of ``conv2d(x, weight)`` from g_y [B*H*W, C_out], + residual (``kd_conv2d_x3`` on
+    ``pack_conv_dgrad(weight)``; the bias gets no gradient).  ``out`` must not overlap g_y; it may be ``residual`` (g += ...)."""
+    c_out, c_in, ks, _ = weight.shape
+    ldg = _rows(g_y, "g_y", c_out)
+    _tokens(g_y, B, H, W, "conv2d_dgrad")
+    out = torch.empty(g_y.shape[0], c_in, device=g_y.device, dtype=torch.float32) if out is None else out
+    ldo = _rows(out, "out", c_in)
+    ldr = _rows(residual, "residual", c_in) if residual is not None else 0
+    if out.shape[0] != g_y.shape[0] or (residual is not None and residual.shape[0] != g_y.shape[0]):
+        raise ValueError("conv2d_dgrad: out and residual have the rows of g_y")
+    nat.check(nat.lib().kd_conv2d_x3(_p(g_y), ldg, _p(pack_conv_dgrad(weight, q_rows)), None, _p(residual), ldr, _p(out), ldo, B, H, W, c_out, c_in,
+                                     ks, _stream()), "kd_conv2d_x3")
+    return out
+
+
+def _adagn_vjp_dims(entry, x, stats, wb, g_y):
+    ldx, ldgy = _rows(x, "x"), _rows(g_y, "g_y")
+    if g_y.shape != x.shape:
+        raise ValueError(f"{entry}: g_y shape {tuple(g_y.shape)} != x shape {tuple(x.shape)}")
+    if _chk(stats, "stats").dim() != 3 or stats.shape[2] != 4:
+        raise ValueError(f"{entry}: stats is [B, groups, 4] (got {tuple(stats.shape)})")
+    B, groups = stats.shape[:2]
+    hw, chan = x.shape[0] // B, x.shape[1]
+    wbs = _rows(wb, "wb")
+    if wb.shape[0] != B or wb.shape[1] != 2 * chan:
+        raise ValueError(f"{entry}: wb {tuple(wb.shape)} != {(B, 2 * chan)}")
+    if hw * B != x.shape[0]:
+        raise ValueError(f"{entry}: {x.shape[0]} rows for batch {B}")
+    return ldx, ldgy, wbs, B, groups, hw, chan
+
+
+def adagn_vjp_stats(x, stats, wb, g_y, gelu=False, out=None):
+    """gstats [B, groups, 4] = (mean(g_xh), mean(g_xh xh), 0, 0) per (sample, group): the two means of the reverse of ``adagn_apply(x, stats,
+    wb, gelu)`` from the gradient g_y on its output (``kd_adagn_vjp_stats_f32``)."""
+    ldx, ldgy, wbs, B, groups, hw, chan = _adagn_vjp_dims("adagn_vjp_stats", x, stats, wb, g_y)
+    out = torch.empty(B, groups, 4, device=x.device, dtype=torch.float32) if out is None else out
+    if tuple(_chk(out, "gstats").shape) != (B, groups, 4):
+        raise ValueError(f"adagn_vjp_stats: gstats {tuple(out.shape)} != {(B, groups, 4)}")
+    nat.check(nat.lib().kd_adagn_vjp_stats_f32(_p(x), ldx, _p(stats), _p(wb), wbs, _p(g_y), ldgy, _p(out), B, hw, chan, groups, int(bool(gelu)),
+                                               _stream()), "kd_adagn_vjp_stats_f32")
+    return out
+
+
+def adagn_vjp_apply(x, stats, gstats, wb, g_y, g_add=None, gelu=False, out=None):
+    """g_x = the gradient of ``adagn_apply(x, stats, wb, gelu)`` w.r.t. x from g_y, the conditioning ``wb`` held fixed, + g_add
+    (``kd_adagn_vjp_apply_f32``).  ``out`` may be g_y or g_add (in place), not x."""
+    ldx, ldgy, wbs, B, groups, hw, chan = _adagn_vjp_dims("adagn_vjp_apply", x, stats, wb, g_y)
+    if tuple(_chk(gstats, "gstats").shape) != tuple(stats.shape):
+        raise ValueError(f"adagn_vjp_apply: gstats {tuple(gstats.shape)} != stats {tuple(stats.shape)}")
+    ldga = _rows(g_add, "g_add", chan) if g_add is not None else 0
+    out = torch.empty(x.shape[0], chan, device=x.device, dtype=torch.float32) if out is None else out
+    ldgx = _rows(out, "out", chan)
+    if out.shape[0] != x.shape[0] or (g_add is not None and g_add.shape[0] != x.shape[0]):
+        raise ValueError("adagn_vjp_apply: out and g_add have the rows of x")
+    nat.check(nat.lib().kd_adagn_vjp_apply_f32(_p(x), ldx, _p(stats), _p(gstats), _p(wb), wbs, _p(g_y), ldgy, _p(g_add), ldga, _p(out), ldgx, B, hw,
+                                               chan, groups, int(bool(gelu)), _stream()), "kd_adagn_vjp_apply_f32")
+    return out
+
+
+def _resample_vjp(entry, g_y, B, H, W, Ho, Wo, out, accumulate):
+    ldgy = _rows(g_y, "g_y")
+    _tokens(g_y, B, Ho, Wo, entry)
+    chan = g_y.shape[1]
+    if out is None:
+        if accumulate:
+            raise ValueError(f"{entry}: accumulate needs the tensor to add to (out)")
+        out = torch.empty(B * H * W, chan, device=g_y.device, dtype=torch.float32)
+    ldgx = _rows(out, "out", chan)
+    if out.shape[0] != B * H * W:
+        raise ValueError(f"{entry}: out has {out.shape[0]} rows, expected {B * H * W}")
+    nat.check(getattr(nat.lib(), entry)(_p(g_y), ldgy, _p(out), ldgx, B, H, W, chan, int(bool(accumulate)), _stream()), entry)
+    return out
+
+
+def down2_vjp(g_y, B, H, W, out=None, accumulate=False):
+    """The transpose of ``down2`` at input size H x W: g_y [B*(H/2)*(W/2), C] -> g_x [B*H*W, C] (``kd_down2_vjp_f32``); with ``accumulate`` it is
+    added to ``out``."""
+    return _resample_vjp("kd_down2_vjp_f32", g_y, B, H, W, H // 2, W // 2, out, accumulate)
+
+
+def up2_vjp(g_y, B, H, W, out=None, accumulate=False):
+    """The transpose of ``up2`` at input size H x W: g_y [B*2H*2W, C] -> g_x [B*H*W, C] (``kd_up2_vjp_f32``); with ``accumulate`` it is added
+    to ``out``."""
+    return _resample_vjp("kd_up2_vjp_f32", g_y, B, H, W, 2 * H, 2 * W, out, accumulate)
