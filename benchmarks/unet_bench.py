@@ -13,6 +13,11 @@ the forward at batch 2 B (the dual pass stacks the tangent behind the primal: 2 
 ``--vjp`` instead times the reverse pass at batch B -- ``forward_vjp`` plus one ``pullback`` -- against the plain forward at batch B and against
 ``forward_vjp`` alone (the primal on tensors of its own), same warm-up and sampling; after the timed samples one more reverse pass runs under the
 library's per-launch events, and the line carries the time per kernel name (where the reverse pass's time goes).
+``--train`` instead times one training evaluation at batch B -- ``Denoiser.loss(...).mean().backward()`` with every parameter trainable --
+against the plain forward at batch B and against torch autograd over tests/unet_ref.py's forward in fp32 on the same GPU (the yardstick), same
+warm-up and sampling, with the time per kernel name of one more evaluation; then, per 3 x 3 convolution shape of the model's levels, the weight
+gradient kernel ``kd_conv2d_wgrad_x3`` against the composition that served before it existed: nine ``ops.wgrad`` calls over nine shifted,
+zero-padded copies of A (timed without and with making the copies).
 Prints one JSON line per model.
 """
 import argparse
@@ -71,6 +76,95 @@ def kernel_ms():
     return {k: [n, round(t, 4)] for k, (n, t) in sorted(out.items(), key=lambda kv: -kv[1][1])}
 
 
+def train_bench(K, ur, name, model, sd, x, sigma, aug, B, H, W):
+    """The ``--train`` lines of one model."""
+    from torch.nn import functional as F
+    dev = x.device
+    g = torch.Generator().manual_seed(5)
+    noise = torch.randn(x.shape, generator=g).to(dev)
+    den = K.Denoiser(model, 0.5)
+    model.requires_grad_(True)
+
+    def hip():
+        model.zero_grad(set_to_none=True)
+        den.loss(x, noise, sigma, aug_cond=aug).mean().backward()
+
+    def forward():
+        with torch.no_grad():
+            den.loss(x, noise, sigma, aug_cond=aug)
+    leaves = {k: v.detach().to(dev, torch.float32).requires_grad_(v.is_floating_point() and "kernel" not in k and "timestep_embed" not in k)
+              for k, v in sd.items()}
+    prepared = {(k[len("inner_model."):] if k.startswith("inner_model.") else k): v for k, v in leaves.items()}
+    prepared["__wrapped__"] = True
+    params = [v for v in leaves.values() if v.requires_grad]
+
+    def ref():
+        var = sigma ** 2 + 0.25
+        c_skip, c_out, c_in = (t[:, None, None, None] for t in (0.25 / var, sigma * 0.5 / var.sqrt(), 1 / var.sqrt()))
+        noised = x + noise * sigma[:, None, None, None]
+        f = ur.forward(prepared, noised * c_in, sigma, aug_cond=aug, dtype=torch.float32, device=dev, grouped_resample=True, prepared=True)
+        loss = (f - (x - c_skip * noised) / c_out).pow(2).flatten(1).mean(1).mean()
+        return torch.autograd.grad(loss, params)
+    sides = {"forward_ms": forward, "train_ms": hip, "torch_fp32_autograd_ms": ref}
+    for _ in range(5):
+        for fn in sides.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in sides}
+    for _ in range(7):
+        for k, fn in sides.items():
+            times[k].append(timed(fn))
+    line = {"model": name, "batch": B, **{k: [statistics.median(t), min(t), max(t)] for k, t in times.items()}}
+    line["train_over_forward"] = line["train_ms"][0] / line["forward_ms"][0]
+    line["torch_over_train"] = line["torch_fp32_autograd_ms"][0] / line["train_ms"][0]
+    hip()
+    named = dict(model.named_parameters())
+    want = ref()
+    errs = {k: ((named[k].grad - w).abs().max() / w.abs().max()).item() for k, w in zip([k for k, v in leaves.items() if v.requires_grad], want)}
+    line["worst_grad_rel_diff_vs_torch_fp32"] = max(errs.values())
+    K._native.prof_enable(True)
+    K._native.lib().kd_prof_reset()
+    hip()
+    torch.cuda.synchronize()
+    line["train_kernel_ms"] = kernel_ms()
+    K._native.prof_enable(False)
+    print(json.dumps(line), flush=True)
+    model.requires_grad_(False)
+    # the weight-gradient kernel against nine ops.wgrad calls over shifted copies of A, per 3 x 3 shape of the levels
+    ch = model.inner_model.channels
+    shapes = []
+    for i, c in enumerate(ch):
+        for ci in sorted({c, ch[max(0, i - 1)], 2 * c if i < len(ch) - 1 else c}):
+            shapes.append((H >> i, W >> i, ci, c))
+    with torch.no_grad():
+        for h, w, ci, co in shapes:
+            a, gy = torch.randn(B * h * w, ci, device=dev), torch.randn(B * h * w, co, device=dev)
+
+            def shifted():
+                img = F.pad(a.view(B, h, w, ci), (0, 0, 1, 1, 1, 1))
+                return [img[:, ky:ky + h, kx:kx + w].reshape(-1, ci).contiguous() for ky in range(3) for kx in range(3)]
+            copies = shifted()
+            new = lambda: K.unet_ops.conv2d_wgrad(gy, a, B, h, w, 3)
+            nine = lambda: [K.ops.wgrad(gy, c) for c in copies]
+            nine_with_copies = lambda: [K.ops.wgrad(gy, c) for c in shifted()]
+            sides = {"conv2d_wgrad_x3_ms": new, "nine_wgrad_ms": nine, "nine_wgrad_with_copies_ms": nine_with_copies}
+            for _ in range(3):
+                for fn in sides.values():
+                    fn()
+            torch.cuda.synchronize()
+            times = {k: [] for k in sides}
+            for _ in range(7):
+                for k, fn in sides.items():
+                    times[k].append(timed(fn))
+            diff = (new() - torch.stack(nine(), dim=-1).view(co, ci, 3, 3)).abs().max().item() / new().abs().max().item()
+            flops = 2.0 * B * h * w * 9 * ci * co
+            row = {"model": name, "shape": f"B{B} {h}x{w} {ci}->{co}", **{k: [statistics.median(t), min(t), max(t)] for k, t in times.items()},
+                   "chunks": K.unet_ops.conv_wgrad_chunks(B, h, w, ci, co)[1], "rel_diff": diff}
+            row["nine_over_new"] = row["nine_wgrad_ms"][0] / row["conv2d_wgrad_x3_ms"][0]
+            row["tflops_fp32_equiv"] = flops / row["conv2d_wgrad_x3_ms"][0] / 1e9
+            print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", choices=sorted(MODELS))
@@ -78,6 +172,7 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--dual", action="store_true")
     ap.add_argument("--vjp", action="store_true")
+    ap.add_argument("--train", action="store_true")
     args = ap.parse_args()
     import k_diffusion_amd as K
     from tests import unet_ref as ur
@@ -96,6 +191,9 @@ def main():
         x = (torch.randn(B, C, H, W, generator=g).to(dev) * (sigma ** 2 + 0.25).sqrt()[:, None, None, None]).contiguous()
         aug = (0.5 * torch.randn(B, 9, generator=g)).to(dev)
         hip = lambda: model(x, sigma, aug_cond=aug)
+        if args.train:
+            train_bench(K, ur, name, model, sd, x, sigma, aug, B, H, W)
+            continue
         with torch.no_grad():
             if args.profile:
                 for _ in range(8):

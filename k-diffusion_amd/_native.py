@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KDIFF_HIP_LIB") or os.path.join(_HERE, "csrc", "libkdiff_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_hip.h")
 GRAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_grad.h")
+TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_train.h")
 
 
 class NativeLibraryError(RuntimeError):
@@ -43,6 +44,15 @@ except OSError as e:
 if _grad.structs or _grad.constants or set(_grad.signatures) & set(SIGNATURES):
     raise HeaderError(f"{GRAD_HEADER_PATH}: prototypes of entry points kdiff_hip.h does not declare, and nothing else")
 GRAD_SIGNATURES, GRAD_RESTYPES = _grad.signatures, _grad.restypes
+# ... and so are its parameter-gradient kernels (csrc/conv_wgrad_x3.hip, csrc/unet_train_f32.hip): a third header, a third table
+try:
+    with open(TRAIN_HEADER_PATH) as _header:
+        _train = parse(_header.read())
+except OSError as e:
+    raise NativeLibraryError(f"{TRAIN_HEADER_PATH}: the C ABI header the package binds from cannot be read ({e})") from e
+if _train.structs or _train.constants or set(_train.signatures) & (set(SIGNATURES) | set(GRAD_SIGNATURES)):
+    raise HeaderError(f"{TRAIN_HEADER_PATH}: prototypes of entry points the other two headers do not declare, and nothing else")
+TRAIN_SIGNATURES, TRAIN_RESTYPES = _train.signatures, _train.restypes
 _i, _f = C.c_int, C.c_float                  # the kinds encode_call tells apart (the parser hands out these very objects)
 
 # PREC_FP8 is a mode of the NETWORK, not a KdGemm.precision value: the bf16 mode with the AdaRMSNorm -> wide projections of the K = 256 / 512
@@ -122,7 +132,7 @@ def lib():
                 "(python -c 'import __graft_entry__ as g; g.build()' or make -C k-diffusion_amd/csrc). "
                 "There is no CPU / PyTorch fallback for the sampling hot path.")
         handle = C.CDLL(LIB_PATH)
-        for signatures, restypes in ((SIGNATURES, RESTYPES), (GRAD_SIGNATURES, GRAD_RESTYPES)):
+        for signatures, restypes in ((SIGNATURES, RESTYPES), (GRAD_SIGNATURES, GRAD_RESTYPES), (TRAIN_SIGNATURES, TRAIN_RESTYPES)):
             for name, argtypes in signatures.items():
                 try:
                     fn = getattr(handle, name)

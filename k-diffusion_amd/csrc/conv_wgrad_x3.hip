@@ -1,0 +1,212 @@
+// Weight gradient of the image_v1 U-Net's convolutions (gfx950), fp32-parity ("split3") arithmetic: for nn.Conv2d with kernel size 1 or 3, zero
+// padding ks / 2 and stride 1 on fp32 NHWC activations (token-major [B H W, C] with a row stride),
+//
+//   dW[co, ci, ky, kx] (+)= sum over (b, y, x) of G[b, y, x, co] * A[b, y + ky - h, x + kx - h, ci],   h = ks / 2.
+//
+// The counterpart of conv_x3.hip with the roles turned: M = C_out, N = C_in and the reduction runs over PIXELS, one accumulator per tap.  Every
+// fp32 operand is hi + lo bf16 (hi = bf16(x), lo = bf16(x - hi)); a product is three v_mfma_f32_32x32x16_bf16 (lo hi, hi lo, hi hi) with fp32
+// accumulation.
+//
+// One workgroup (4 waves) owns a 64 x 64 (co, ci) tile of dW for ALL ks^2 taps -- a wave a 32 x 32 block, ks^2 accumulators of 16 registers --
+// over one run of consecutive 8 x 8 pixel patches.  Per patch it stages the G patch (64 pixels x 64 co) and the haloed A patch ((8 + 2 h)^2
+// positions x 64 ci) into LDS once, split hi / lo while staging, and all taps accumulate from that one image: nine shifted GEMMs would fetch A
+// nine times.  An MFMA operand fragment is 8 consecutive values of the REDUCTION index, so both images are stored pixel-contiguous: one 16-byte
+// slot holds the 8 pixels of one patch row of one channel, and a k-step of 16 pixels is two patch rows (the half-wave picks the row).  A tap's x
+// shift would misalign that 16-byte read, so the A image is kept ks times, copy kx holding the positions kx .. kx + 7 of every haloed row; the y
+// shift is a whole slot row.  Layout [row][channel][8 pixels]: the 32 lanes of a half-wave read 32 consecutive slots (512 contiguous bytes,
+// conflict-free for ds_read_b128), and a staging thread -- one (row, channel), its lanes along the channels, so that every global load of a
+// wave is 256 contiguous bytes -- writes whole slots.  76 KB of LDS at ks = 3: two workgroups per CU, one staging while the other multiplies.
+//
+// A position outside the image -- the zero padding, and the part of a ragged patch beyond the image's edge -- is SELECTED to zero in both
+// operands: it is never loaded, so a patch never reads a neighbouring sample's rows or memory outside the tensor.
+//
+// The sum over pixels is cut into runs of `patches_per_chunk` patches: a function of the shape alone on the Python side (unet_ops.
+// conv_wgrad_chunks), checked here.  Every run writes its partial tile to the workspace [nchunk][tap][co][ci]; the second kernel adds the
+// partials in ascending order and writes nn.Conv2d's [co][ci][ky][kx] layout, so that the result is the parameter's .grad as it stands.  No
+// atomics: the order of every sum is fixed, a second run gives the same bits.
+#include "x3_common.h"
+#include "../../include/kdiff_unet_train.h"
+
+namespace kd {
+
+namespace {
+
+using b16::bf16x8;
+using b16::u32x4;
+
+constexpr int PATCH = 8;          // pixels per patch side
+constexpr int TILE = 64;          // output channels / input channels per workgroup
+constexpr int SLOT = 16;          // bytes of 8 bf16 pixels
+
+struct WgP {
+  const float* g;
+  const float* a;
+  float* ws;
+  int ldg, lda;
+  int H, W, c_in, c_out;
+  int ty_n, tx_n, n_patches;      // patches per column / row of one sample, and of the whole batch
+  int ci_tiles, n_tiles;          // 64-wide tiles along c_in, and of the whole weight
+  int ppc;                        // patches per chunk
+};
+
+constexpr int lds_bytes(int ks) { return (2 * PATCH + 2 * ks * (PATCH + 2 * (ks / 2))) * TILE * SLOT; }
+
+template <int KS>
+__global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WgP p) {
+  constexpr int HALO = KS / 2, PWH = PATCH + 2 * HALO, TAPS = KS * KS;
+  constexpr int G_IMG = PATCH * TILE * SLOT, A_IMG = PWH * TILE * SLOT;       // bytes of one hi (or lo) image
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  char* g_hi = lds;
+  char* g_lo = lds + G_IMG;
+  char* a_img = lds + 2 * G_IMG;                                               // copy kx: [hi | lo] at a_img + 2 kx A_IMG
+
+  const int item = KD_XCD_CHUNK();
+  const int tile = item % p.n_tiles, chunk = item / p.n_tiles;
+  const int co0 = (tile / p.ci_tiles) * TILE, ci0 = (tile % p.ci_tiles) * TILE;
+  const int pt0 = chunk * p.ppc, pt1 = min(p.n_patches, pt0 + p.ppc);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5, wm = wave & 1, wn = wave >> 1;
+
+  f32x16 acc[TAPS];
+#pragma unroll
+  for (int t = 0; t < TAPS; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+
+  for (int pt = pt0; pt < pt1; ++pt) {
+    const int tx = pt % p.tx_n;
+    const int rest = pt / p.tx_n;
+    const int ty = rest % p.ty_n, b = rest / p.ty_n;
+    const int y0 = ty * PATCH, x0 = tx * PATCH;
+    const size_t pix0 = (size_t)b * p.H * p.W;
+    __syncthreads();                                           // the previous patch has been consumed
+    // G: one (patch row, co) per thread and round
+    for (int it = tid; it < PATCH * TILE; it += 256) {
+      const int py = it >> 6, c = it & 63;
+      const int gy = y0 + py;
+      float v[PATCH];
+#pragma unroll
+      for (int j = 0; j < PATCH; ++j) {
+        const int gx = x0 + j;
+        v[j] = 0.f;
+        if (gy < p.H && gx < p.W) v[j] = p.g[(pix0 + (size_t)gy * p.W + gx) * p.ldg + co0 + c];
+      }
+      u32x4 hi, lo;
+      x3::split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, hi, lo);
+      *reinterpret_cast<u32x4*>(g_hi + it * SLOT) = hi;
+      *reinterpret_cast<u32x4*>(g_lo + it * SLOT) = lo;
+    }
+    // A: one (haloed row, ci) per thread and round, written once per x shift
+    for (int it = tid; it < PWH * TILE; it += 256) {
+      const int hy = it >> 6, c = it & 63;
+      const int gy = y0 + hy - HALO;
+      float v[PWH];
+#pragma unroll
+      for (int j = 0; j < PWH; ++j) {
+        const int gx = x0 + j - HALO;
+        v[j] = 0.f;
+        if (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) v[j] = p.a[(pix0 + (size_t)gy * p.W + gx) * p.lda + ci0 + c];
+      }
+#pragma unroll
+      for (int kx = 0; kx < KS; ++kx) {
+        u32x4 hi, lo;
+        x3::split8(f32x4{v[kx], v[kx + 1], v[kx + 2], v[kx + 3]}, f32x4{v[kx + 4], v[kx + 5], v[kx + 6], v[kx + 7]}, hi, lo);
+        *reinterpret_cast<u32x4*>(a_img + 2 * kx * A_IMG + it * SLOT) = hi;
+        *reinterpret_cast<u32x4*>(a_img + (2 * kx + 1) * A_IMG + it * SLOT) = lo;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < PATCH / 2; ++s) {                      // a k-step: the 16 pixels of patch rows 2 s and 2 s + 1
+      const int py = 2 * s + h;
+      const int g_at = (py * TILE + 32 * wm + r) * SLOT;
+      const bf16x8 gh = *reinterpret_cast<const bf16x8*>(g_hi + g_at);
+      const bf16x8 gl = *reinterpret_cast<const bf16x8*>(g_lo + g_at);
+#pragma unroll
+      for (int ky = 0; ky < KS; ++ky) {
+        const int a_at = ((py + ky) * TILE + 32 * wn + r) * SLOT;
+#pragma unroll
+        for (int kx = 0; kx < KS; ++kx) {
+          const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a_img + 2 * kx * A_IMG + a_at);
+          const bf16x8 al = *reinterpret_cast<const bf16x8*>(a_img + (2 * kx + 1) * A_IMG + a_at);
+          f32x16& d = acc[ky * KS + kx];
+          d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl, ah, d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, al, d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, ah, d, 0, 0, 0);
+        }
+      }
+    }
+  }
+
+  // the partial tile: rows = co (the first operand's), a lane's column = ci
+  const size_t plane = (size_t)p.c_out * p.c_in;
+  float* dst = p.ws + (size_t)chunk * TAPS * plane + ci0 + 32 * wn + r;
+#pragma unroll
+  for (int t = 0; t < TAPS; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int co = co0 + 32 * wm + mfma32_row(i, lane);
+      dst[t * plane + (size_t)co * p.c_in] = acc[t][i];
+    }
+}
+
+// dw[co][ci][tap] (+)= scale(co) * sum over the chunks, ascending, of ws[chunk][tap][co][ci]; a thread's index runs ci-fastest over the workspace
+__global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int c_out, int c_in, int taps,
+                                                                int nchunk, int q_rows, int accumulate) {
+  const long plane = (long)c_out * c_in, n_el = plane * taps;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_el; i += (long)gridDim.x * 256) {
+    const int tap = (int)(i / plane);
+    const long rem = i - tap * plane;
+    const int co = (int)(rem / c_in);
+    float sum = 0.f;
+    for (int k = 0; k < nchunk; ++k) sum += ws[(long)k * n_el + i];
+    if (co < q_rows) sum *= 0.125f;
+    float* o = dw + rem * taps + tap;
+    *o = accumulate ? *o + sum : sum;
+  }
+}
+
+template <int KS>
+int launch_wgrad(const WgP& p, long n_wg, hipStream_t s) {
+  launch<conv_wgrad_x3_kernel<KS>>(dim3((unsigned)n_wg), dim3(256), lds_bytes(KS), s, p);
+  return check_launch("kd_conv2d_wgrad_x3");
+}
+
+}  // namespace
+
+}  // namespace kd
+
+using namespace kd;
+
+extern "C" int kd_conv2d_wgrad_x3(const float* g, int ldg, const float* a, int lda, float* ws, float* dw, int batch, int H, int W, int c_in, int c_out,
+                                  int ks, int q_rows, int patches_per_chunk, int nchunk, int accumulate, void* stream) {
+  if (!g || !a || !ws || !dw || batch <= 0 || H <= 0 || W <= 0) return fail(KD_EINVAL, "kd_conv2d_wgrad_x3: bad arguments");
+  if (ks != 1 && ks != 3) return fail(KD_EINVAL, "kd_conv2d_wgrad_x3: kernel size %d (1 or 3)", ks);
+  if (c_in <= 0 || c_out <= 0 || (c_in % TILE) || (c_out % TILE))
+    return fail(KD_EINVAL, "kd_conv2d_wgrad_x3: c_in = %d and c_out = %d must be multiples of 64", c_in, c_out);
+  if (ldg < c_out || lda < c_in) return fail(KD_EINVAL, "kd_conv2d_wgrad_x3: a row stride is shorter than its row");
+  if (q_rows < 0 || q_rows > c_out) return fail(KD_EINVAL, "kd_conv2d_wgrad_x3: q_rows = %d outside 0 .. c_out = %d", q_rows, c_out);
+  const long pixels = (long)batch * H * W;
+  if (pixels > 0x7FFFFFFFl) return fail(KD_EINVAL, "kd_conv2d_wgrad_x3: %ld pixels exceed the index range", pixels);
+  const int ty_n = (H + PATCH - 1) / PATCH, tx_n = (W + PATCH - 1) / PATCH;
+  const long n_patches = (long)batch * ty_n * tx_n;
+  if (patches_per_chunk <= 0 || nchunk <= 0 || (long)nchunk != (n_patches + patches_per_chunk - 1) / patches_per_chunk)
+    return fail(KD_EINVAL, "kd_conv2d_wgrad_x3: %d chunks of %d patches do not cut %ld patches", nchunk, patches_per_chunk, n_patches);
+  WgP p{g, a, ws, ldg, lda, H, W, c_in, c_out, ty_n, tx_n, (int)n_patches, c_in / TILE, (c_in / TILE) * (c_out / TILE), patches_per_chunk};
+  const long n_wg = (long)nchunk * p.n_tiles;
+  if (n_wg > 0x7FFFFFFFl) return fail(KD_EINVAL, "kd_conv2d_wgrad_x3: %ld workgroups exceed the grid", n_wg);
+  hipStream_t s = (hipStream_t)stream;
+  const double m = (double)pixels, n_el = (double)ks * ks * c_in * c_out;
+  {
+    ProfName nm("conv2d_wgrad_x3", "conv2d_wgrad_x3<k%d> M=%ld N=%d K=%d chunks=%d", ks, (long)pixels, c_out, ks * ks * c_in, nchunk);
+    LaunchScope prof(nm, 2.0 * m * n_el, 4.0 * m * (c_in + c_out) + 4.0 * nchunk * n_el, s);
+    const int rc = ks == 3 ? launch_wgrad<3>(p, n_wg, s) : launch_wgrad<1>(p, n_wg, s);
+    if (rc != KD_OK) return rc;
+  }
+  LaunchScope prof("conv2d_wgrad_reduce", 0, 4.0 * (nchunk + 1) * n_el, s);
+  const long n_out = (long)ks * ks * c_in * c_out;
+  launch<conv_wgrad_reduce_kernel>(dim3((unsigned)std::min<long>((n_out + 255) / 256, 65536)), dim3(256), 0, s, (const float*)ws, dw, c_out, c_in,
+                                   ks * ks, nchunk, q_rows, accumulate);
+  return check_launch("kd_conv2d_wgrad_x3");
+}

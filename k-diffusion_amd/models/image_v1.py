@@ -19,10 +19,16 @@ kernel launches over fp32 NHWC token buffers ``[B H W, C]``, built once per (bat
 * ``forward_vjp`` (gradient guidance: the gradient of a loss on the output w.r.t. the input) returns the output with the forward's bits and a
   pullback; the reverse walk and its recomputation are ``models/unet_vjp.py``, its AdaGN and resampling rules ``csrc/unet_vjp_f32.hip``.
 
-Scope: the forward pass, its forward-mode derivative and its reverse-mode derivative w.r.t. the input (explicit methods: ``forward_jvp``,
-``forward_vjp``; nothing runs behind autograd, and sigma, the conditioning and the weights get no gradient) in fp32-grade (split-bf16x3) arithmetic whatever ``KDIFF_GEMM`` says, ``patch_size == 1``, ``skip_stages == 0``, no
-variance output, no cross attention, no ``unet_cond``, channels that are multiples of 64, even H and W at every downsample.  Anything else is
-refused in the constructor; training (grad mode with something that requires grad) raises NotImplementedError.
+* ``loss_forward`` (what ``Denoiser.loss`` calls: TRAINING) is the one pass behind autograd: a node whose differentiable inputs are the
+  parameters; its backward is the reverse walk with the parameter-gradient kernels of csrc/conv_wgrad_x3.hip and csrc/unet_train_f32.hip
+  (``models/unet_train.py``).
+
+Scope: the forward pass, its forward-mode derivative, its reverse-mode derivative w.r.t. the input (explicit methods: ``forward_jvp``,
+``forward_vjp``) and the parameter gradients of the training loss (``loss_forward``; sigma and the conditioning get no gradient anywhere) in
+fp32-grade (split-bf16x3) arithmetic whatever ``KDIFF_GEMM`` says, ``patch_size == 1``, ``skip_stages == 0``, no variance output, no cross
+attention, no ``unet_cond``, no dropout (training mode with ``dropout_rate > 0`` is refused), channels that are multiples of 64, even H and W at
+every downsample.  Anything else is refused in the constructor; the sampling passes (``forward``, ``forward_jvp``, ``forward_vjp``) raise
+NotImplementedError under grad mode with something that requires grad.
 """
 from functools import partial
 
@@ -298,10 +304,18 @@ class AugmentWrapperV1(KarrasAugmentWrapper):
             cond = torch.cat([cond, mapping_cond], dim=1)
         return self.inner_model.forward_vjp(input, sigma, mapping_cond=cond, sigma_data=sigma_data, **kwargs)
 
+    def loss_forward(self, input, sigma, aug_cond=None, mapping_cond=None, **kwargs):
+        """The inner model's ``loss_forward`` (``Denoiser.loss``) under the conditioning rule of ``forward_preconditioned``."""
+        cond = input.new_zeros([input.shape[0], 9]) if aug_cond is None else aug_cond
+        if mapping_cond is not None:
+            cond = torch.cat([cond, mapping_cond], dim=1)
+        return self.inner_model.loss_forward(input, sigma, mapping_cond=cond, **kwargs)
+
 
 class ImageDenoiserModelV1(nn.Module):
     """image_v1.py:89-176 with the reference's constructor signature, attributes, state_dict and ``param_groups``; the forward, its
-    forward-mode derivative and its input gradient as explicit methods, no autograd backward pass (see the module docstring for the scope)."""
+    forward-mode derivative and its input gradient as explicit methods; behind autograd only ``loss_forward``, the training loss's parameter
+    gradients (see the module docstring for the scope)."""
 
     def __init__(self, c_in, feats_in, depths, channels, self_attn_depths, cross_attn_depths=None, mapping_cond_dim=0, unet_cond_dim=0,
                  cross_cond_dim=0, dropout_rate=0., patch_size=1, skip_stages=0, has_variance=False):
@@ -391,15 +405,35 @@ class ImageDenoiserModelV1(nn.Module):
 
     def _refuse(self, input, sigma, mapping_cond, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False, tangent=None,
                 dual=False):
-        """The refusals of every pass (forward, dual, reverse): what the HIP path does not take, by name."""
-        if unet_cond is not None or cross_cond is not None or cross_cond_padding is not None or return_variance:
-            raise ValueError("image_v1: unet_cond, cross_cond and return_variance are not supported on the HIP path")
+        """The refusals of the sampling passes (forward, dual, reverse): what the HIP path does not take, by name."""
+        self._refuse_conditioning(unet_cond, cross_cond, cross_cond_padding, return_variance)
         tensors = [t for t in (input, sigma, mapping_cond, tangent) if isinstance(t, torch.Tensor)]
         if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("image_v1: sampling only -- the U-Net has no backward pass on the HIP path; call it under torch.no_grad() "
                                       "(and model.requires_grad_(False))")
         if self.training and self.dropout_rate:
             raise NotImplementedError("image_v1: sampling only -- dropout is a training quantity; call model.eval()")
+        self._check_operands(input, mapping_cond, tangent, dual)
+
+    @staticmethod
+    def _refuse_conditioning(unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False):
+        if unet_cond is not None or cross_cond is not None or cross_cond_padding is not None or return_variance:
+            raise ValueError("image_v1: unet_cond, cross_cond and return_variance are not supported on the HIP path")
+
+    def _refuse_loss(self, input, sigma, mapping_cond, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False):
+        """The refusals of ``loss_forward``: the parameters MAY require grad here; the data may not, and there is no dropout yet."""
+        self._refuse_conditioning(unet_cond, cross_cond, cross_cond_padding, return_variance)
+        for name, t in (("input", input), ("sigma", sigma), ("mapping_cond", mapping_cond)):
+            if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+                raise NotImplementedError(f"image_v1: loss_forward differentiates w.r.t. the parameters only; {name} gets no gradient (pass "
+                                          f"{name}.detach(), or use forward_vjp for the input gradient)")
+        if self.training and self.dropout_rate:
+            raise NotImplementedError(f"image_v1: dropout_rate={self.dropout_rate} in training mode: the U-Net's Dropout2d is not implemented on the "
+                                      f"HIP path; call model.eval() for the dropout-free objective")
+        self._check_operands(input, mapping_cond)
+
+    def _check_operands(self, input, mapping_cond, tangent=None, dual=False):
+        """Shapes, devices and dtypes of a call's tensors (every pass)."""
         if not isinstance(input, torch.Tensor) or input.dim() != 4 or input.shape[1] != self.c_in:
             raise ValueError(f"image_v1: input is [B, {self.c_in}, H, W] (got {tuple(getattr(input, 'shape', ()))})")
         if dual and (not isinstance(tangent, torch.Tensor) or tangent.shape != input.shape):
@@ -480,3 +514,12 @@ class ImageDenoiserModelV1(nn.Module):
         graph and touches no launch plan, and the refusals are the forward's."""
         from . import unet_vjp
         return unet_vjp.forward_vjp(self, input, sigma, mapping_cond, sigma_data, **kwargs)
+
+    def loss_forward(self, input, sigma, mapping_cond=None, **kwargs):
+        """F(input, sigma) for ``Denoiser.loss`` (which hands it the input already scaled by c_in): the forward's kernels on tensors of this
+        call.  Under grad mode the output carries a ``grad_fn`` whose backward fills the ``.grad`` of every parameter that requires grad
+        (models/unet_train.py); a parameter that does not costs no launch.  input, sigma and the conditioning get no gradient; training mode
+        with ``dropout_rate > 0`` is refused (``model.eval()`` gives the dropout-free objective).  The sampling passes above keep refusing
+        grad mode: training goes through here only."""
+        from . import unet_train
+        return unet_train.loss_forward(self, input, sigma, mapping_cond, **kwargs)

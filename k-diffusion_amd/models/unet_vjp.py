@@ -74,55 +74,75 @@ def _wb(c, norm):
 
 
 def _res_front(c, layer, x, hw):
-    """A residual block up to its second norm: (statistics of x, the pre-norm t2)."""
+    """A residual block up to its second norm: (statistics of x, the first convolution's input t1, the pre-norm t2)."""
     norm = layer.main[0]
     stats = uo.groupnorm_stats(x, c.B, norm.num_groups, norm.eps)
     t1 = uo.adagn_apply(x, stats, _wb(c, norm), gelu=True)
     t2 = uo.conv2d(t1, layer.main[2].weight, c.B, *hw, bias=layer.main[2].bias)
-    return stats, t2
+    return stats, t1, t2
 
 
 def _res_fwd(c, layer, x, y, hw):
-    _, t2 = _res_front(c, layer, x, hw)
+    _, _, t2 = _res_front(c, layer, x, hw)
     norm = layer.main[4]
     uo.adagn_apply(t2, uo.groupnorm_stats(t2, c.B, norm.num_groups, norm.eps), _wb(c, norm), gelu=True, out=t2)
     res = uo.conv2d(x, layer.skip.weight, c.B, *hw) if isinstance(layer.skip, nn.Conv2d) else x
     uo.conv2d(t2, layer.main[6].weight, c.B, *hw, bias=layer.main[6].bias, residual=res, out=y)
 
 
-def _res_vjp(c, layer, x, g, hw):
-    stats0, t2 = _res_front(c, layer, x, hw)
+def _res_vjp(c, layer, x, g, hw, sink=None):
+    """The gradient of a residual block's input from the gradient g of its output.  ``sink`` (the training backward, models/unet_train.py) is
+    shown every gradient a parameter of the block hangs on, beside the activation that met it in the forward; without one the launches are
+    ``forward_vjp``'s."""
+    stats0, t1, t2 = _res_front(c, layer, x, hw)
     n0, n4 = layer.main[0], layer.main[4]
     stats4 = uo.groupnorm_stats(t2, c.B, n4.num_groups, n4.eps)
+    if sink is not None:
+        sink.conv(layer.main[6], g, lambda: uo.adagn_apply(t2, stats4, _wb(c, n4), gelu=True), hw)
+        if isinstance(layer.skip, nn.Conv2d):
+            sink.conv(layer.skip, g, lambda: x, hw)
     g2 = uo.conv2d_dgrad(g, layer.main[6].weight, c.B, *hw)
+    if sink is not None:
+        sink.norm(n4, t2, stats4, g2, gelu=True)
     uo.adagn_vjp_apply(t2, stats4, uo.adagn_vjp_stats(t2, stats4, _wb(c, n4), g2, gelu=True), _wb(c, n4), g2, gelu=True, out=g2)
+    if sink is not None:
+        sink.conv(layer.main[2], g2, lambda: t1, hw)
     g1 = uo.conv2d_dgrad(g2, layer.main[2].weight, c.B, *hw)
+    if sink is not None:
+        sink.norm(n0, x, stats0, g1, gelu=True)
     g_skip = uo.conv2d_dgrad(g, layer.skip.weight, c.B, *hw) if isinstance(layer.skip, nn.Conv2d) else g
     return uo.adagn_vjp_apply(x, stats0, uo.adagn_vjp_stats(x, stats0, _wb(c, n0), g1, gelu=True), _wb(c, n0), g1, g_add=g_skip, gelu=True, out=g1)
 
 
 def _attn_front(c, layer, x, hw):
-    """An attention layer up to its qkv: (statistics of x, qkv [B, H W, 3 C] with the folded q)."""
+    """An attention layer up to its qkv: (statistics of x, the projection's input t1, qkv [B, H W, 3 C] with the folded q)."""
     norm = layer.norm_in
     stats = uo.groupnorm_stats(x, c.B, norm.num_groups, norm.eps)
     t1 = uo.adagn_apply(x, stats, _wb(c, norm), gelu=False)
     wq, bq, packed = c.consts.qkv[layer]
     qkv = uo.conv2d(t1, wq, c.B, *hw, bias=bq, packed=packed)
-    return stats, qkv.view(c.B, hw[0] * hw[1], 3 * layer.c_in)
+    return stats, t1, qkv.view(c.B, hw[0] * hw[1], 3 * layer.c_in)
 
 
 def _attn_fwd(c, layer, x, y, hw):
-    _, q3 = _attn_front(c, layer, x, hw)
+    _, _, q3 = _attn_front(c, layer, x, hw)
     a = ops.attn_global(q3, layer.n_head)
     uo.conv2d(a.view(-1, layer.c_in), layer.out_proj.weight, c.B, *hw, bias=layer.out_proj.bias, residual=x, out=y)
 
 
-def _attn_vjp(c, layer, x, g, hw):
-    stats, q3 = _attn_front(c, layer, x, hw)
+def _attn_vjp(c, layer, x, g, hw, sink=None):
+    """The gradient of an attention layer's input from the gradient g of its output; ``sink`` as in ``_res_vjp``."""
+    stats, t1, q3 = _attn_front(c, layer, x, hw)
     norm, C = layer.norm_in, layer.c_in
+    if sink is not None:
+        sink.conv(layer.out_proj, g, lambda: ops.attn_global(q3, layer.n_head).view(-1, C), hw)
     ga = uo.conv2d_dgrad(g, layer.out_proj.weight, c.B, *hw)
     gq = ops.attn_global_vjp(q3, ga.view(c.B, hw[0] * hw[1], C), layer.n_head)
+    if sink is not None:                                                # gq is the gradient of the FOLDED projection's output: q rows / 8
+        sink.conv(layer.qkv_proj, gq.view(-1, 3 * C), lambda: t1, hw, q_rows=C)
     g1 = uo.conv2d_dgrad(gq.view(-1, 3 * C), layer.qkv_proj.weight, c.B, *hw, q_rows=C)
+    if sink is not None:
+        sink.norm(norm, x, stats, g1, gelu=False)
     return uo.adagn_vjp_apply(x, stats, uo.adagn_vjp_stats(x, stats, _wb(c, norm), g1), _wb(c, norm), g1, g_add=g, out=g1)
 
 
@@ -162,14 +182,14 @@ def _primal(model, c, t0, sizes):
     return cur, tape
 
 
-def _reverse(model, c, tape, g, sizes):
-    """The gradient of the first activation from the gradient g of the last, along the tape in reverse."""
+def _reverse(model, c, tape, g, sizes, sink=None):
+    """The gradient of the first activation from the gradient g of the last, along the tape in reverse; ``sink`` as in ``_res_vjp``."""
     ch, B = model.channels, c.B
     g_cat = {}                                                          # level -> gradient of its concat buffer [rows, 2 C]
     for step in reversed(tape):
         if step[0] == "layer":
             _, layer, x, hw = step
-            g = (_res_vjp if isinstance(layer, v1._ResConvBlock) else _attn_vjp)(c, layer, x, g, hw)
+            g = (_res_vjp if isinstance(layer, v1._ResConvBlock) else _attn_vjp)(c, layer, x, g, hw, sink)
         elif step[0] == "up":                                           # g: the concat buffer's; its left half came from up2
             i = step[1]
             g_cat[i - 1] = g

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI of the image_v1 U-Net kernels (csrc/conv_x3.hip, csrc/unet_f32.hip; contracts: include/kdiff_hip.h)
-and of their reverse rules (csrc/unet_vjp_f32.hip; contracts: include/kdiff_unet_grad.h) -- the module's counterpart of ``ops``, as
-``augmentation`` and ``data`` have theirs.
+and of their reverse rules (csrc/unet_vjp_f32.hip; contracts: include/kdiff_unet_grad.h) and parameter-gradient rules (csrc/conv_wgrad_x3.hip,
+csrc/unet_train_f32.hip; contracts: include/kdiff_unet_train.h) -- the module's counterpart of ``ops``, as ``augmentation`` and ``data`` have
+theirs.
 
 Activations are fp32 NHWC, token-major: a 2-D tensor ``[B * H * W, C]`` whose row stride may exceed C (a column range of a wider buffer:
 ``buf[:, :C]`` and ``buf[:, C:]`` are the two halves of a skip concatenation, written in place by their producers).  Column 0 of such a view
@@ -306,3 +307,86 @@ def up2_vjp(g_y, B, H, W, out=None, accumulate=False):
     """The transpose of ``up2`` at input size H x W: g_y [B*2H*2W, C] -> g_x [B*H*W, C] (``kd_up2_vjp_f32``); with ``accumulate`` it is added
     to ``out``."""
     return _resample_vjp("kd_up2_vjp_f32", g_y, B, H, W, 2 * H, 2 * W, out, accumulate)
+
+
+# ---- parameter gradients (csrc/conv_wgrad_x3.hip, csrc/unet_train_f32.hip; contracts: include/kdiff_unet_train.h): what the backward of
+# ``ImageDenoiserModelV1.loss_forward`` launches beside the reverse rules above ------------------------------------------------------------------------
+
+CONV_WGRAD_BLOCKS = 256     # workgroups kd_conv2d_wgrad_x3 aims at: one per CU; the pixel sum is cut until (co, ci) tiles x chunks reach it
+
+
+def conv_wgrad_chunks(B, H, W, c_in, c_out):
+    """(patches_per_chunk, nchunk) of ``kd_conv2d_wgrad_x3``: how the sum over the B ceil(H / 8) ceil(W / 8) pixel patches is cut into partial
+    sums.  A fixed function of the shape, so that the order of the sum is too."""
+    patches = B * -(-H // 8) * -(-W // 8)
+    tiles = (c_in // 64) * (c_out // 64)
+    nchunk = max(1, min(-(-CONV_WGRAD_BLOCKS // max(tiles, 1)), patches))
+    per_chunk = -(-patches // nchunk)
+    return per_chunk, -(-patches // per_chunk)
+
+
+def conv2d_wgrad(g, a, B, H, W, ks, out=None, accumulate=False, q_rows=0, chunks=None):
+    """dW [C_out, C_in, ks, ks] (+)= the weight gradient of ``conv2d(a, weight)`` (ks 1 or 3, padding ks // 2) from the gradient g
+    [B*H*W, C_out] on its output and its input a [B*H*W, C_in] (``kd_conv2d_wgrad_x3``).  ``q_rows``: the first q_rows output channels ran
+    with a folded 1 / 8 (the q rows of a qkv projection), and the gradient of the stored weight takes it too.  ``chunks`` = (patches per chunk,
+    chunk count) overrides ``conv_wgrad_chunks`` (a test choosing its own cut of the sum)."""
+    ldg, lda = _rows(g, "g"), _rows(a, "a")
+    c_out, c_in = g.shape[1], a.shape[1]
+    _tokens(g, B, H, W, "conv2d_wgrad")
+    _tokens(a, B, H, W, "conv2d_wgrad")
+    if out is None:
+        if accumulate:
+            raise ValueError("conv2d_wgrad: accumulate needs the tensor to add to (out)")
+        out = torch.empty(c_out, c_in, ks, ks, device=g.device, dtype=torch.float32)
+    elif tuple(_chk(out, "out").shape) != (c_out, c_in, ks, ks):
+        raise ValueError(f"conv2d_wgrad: out {tuple(out.shape)} != {(c_out, c_in, ks, ks)}")
+    per_chunk, nchunk = conv_wgrad_chunks(B, H, W, c_in, c_out) if chunks is None else chunks
+    ws = torch.empty(max(nchunk, 1) * ks * ks * c_out * c_in, device=g.device, dtype=torch.float32)
+    nat.check(nat.lib().kd_conv2d_wgrad_x3(_p(g), ldg, _p(a), lda, _p(ws), _p(out), B, H, W, c_in, c_out, ks, int(q_rows), int(per_chunk), int(nchunk),
+                                           int(bool(accumulate)), _stream()), "kd_conv2d_wgrad_x3")
+    return out
+
+
+def adagn_wb_grad(x, stats, wb, g_y, gelu=False, out=None):
+    """g_wb [B, 2 C] = the gradient of the (w, b) pair ``adagn_apply(x, stats, wb, gelu)`` reads from ``wb``, from the gradient g_y on its
+    output (``kd_adagn_wb_grad_f32``).  ``out`` is usually the norm's column range of the call's gradient table."""
+    ldx, ldgy, wbs, B, groups, hw, chan = _adagn_vjp_dims("adagn_wb_grad", x, stats, wb, g_y)
+    out = torch.empty(B, 2 * chan, device=x.device, dtype=torch.float32) if out is None else out
+    gws = _rows(out, "g_wb", 2 * chan)
+    if out.shape[0] != B:
+        raise ValueError(f"adagn_wb_grad: g_wb {tuple(out.shape)} != {(B, 2 * chan)}")
+    nat.check(nat.lib().kd_adagn_wb_grad_f32(_p(x), ldx, _p(stats), _p(wb), wbs, _p(g_y), ldgy, _p(out), gws, B, hw, chan, groups, int(bool(gelu)),
+                                             _stream()), "kd_adagn_wb_grad_f32")
+    return out
+
+
+def gelu_vjp(pre, g_y, out=None):
+    """g_x = g_y gelu'(pre) for the exact (erf) GELU (``kd_gelu_vjp_f32``); ``out`` may be g_y."""
+    if _chk(pre, "pre").shape != _chk(g_y, "g_y").shape:
+        raise ValueError(f"gelu_vjp: g_y shape {tuple(g_y.shape)} != pre shape {tuple(pre.shape)}")
+    out = torch.empty_like(pre) if out is None else out
+    if _chk(out, "g_x").shape != pre.shape:
+        raise ValueError(f"gelu_vjp: g_x shape {tuple(out.shape)} != pre shape {tuple(pre.shape)}")
+    nat.check(nat.lib().kd_gelu_vjp_f32(_p(pre), _p(g_y), _p(out), pre.numel(), _stream()), "kd_gelu_vjp_f32")
+    return out
+
+
+def bias_grad(g, out=None, accumulate=False, q_cols=0):
+    """The gradient of a convolution's bias: out [C] (+)= the column sums of the gradient g on its output -- token rows [B*H*W, C] with a row
+    stride, or a contiguous NCHW image [B, C, H, W] (``kd_bias_grad_f32``).  ``q_cols``: the first q_cols sums take a folded 1 / 8."""
+    if g.dim() == 4:
+        rows, cols, ldg, nchw = g.shape[0] * g.shape[2] * g.shape[3], g.shape[1], 0, g.shape[2] * g.shape[3]
+        _chk(g, "g")
+    else:
+        ldg, nchw = _rows(g, "g"), 0
+        rows, cols = g.shape
+    if out is None:
+        if accumulate:
+            raise ValueError("bias_grad: accumulate needs the tensor to add to (out)")
+        out = torch.empty(cols, device=g.device, dtype=torch.float32)
+    elif tuple(_chk(out, "out").shape) != (cols,):
+        raise ValueError(f"bias_grad: out {tuple(out.shape)} != {(cols,)}")
+    ws = torch.empty(-(-rows // 256) * cols, device=g.device, dtype=torch.float64)
+    nat.check(nat.lib().kd_bias_grad_f32(_p(g), ldg, _p(ws), _p(out), rows, cols, nchw, int(q_cols), int(bool(accumulate)), _stream()),
+              "kd_bias_grad_f32")
+    return out

@@ -142,8 +142,8 @@ def main(argv=None):
         raise NotImplementedError('augment_prob > 0: KarrasAugmentationPipeline (scikit-image warps) is not implemented; set augment_prob to 0, '
                                   'or pass --device-augment to augment each batch on the device (K.augmentation)')
     if model_config['type'] == 'image_v1':
-        raise NotImplementedError('model type image_v1: the U-Net runs its forward pass only (sampling) on the HIP path; training it is not '
-                                  'implemented')
+        raise NotImplementedError('model type image_v1: this command line does not train the U-Net yet; Denoiser.loss(...).backward() with '
+                                  'model.param_groups() and K.optim.AdamW trains it in a Python loop (in model.eval(): no Dropout2d yet)')
     if opt_config['type'] != 'adamw':
         raise NotImplementedError(f'optimizer type {opt_config["type"]!r}: only adamw runs on the fused HIP step')
     check_dataset_config(config)
