@@ -18,6 +18,9 @@ against the plain forward at batch B and against torch autograd over tests/unet_
 warm-up and sampling, with the time per kernel name of one more evaluation; then, per 3 x 3 convolution shape of the model's levels, the weight
 gradient kernel ``kd_conv2d_wgrad_x3`` against the composition that served before it existed: nine ``ops.wgrad`` calls over nine shifted,
 zero-padded copies of A (timed without and with making the copies).
+``--train --dropout P`` instead times the same training evaluation of a model with ``dropout_rate`` P in training mode after
+``enable_dropout()`` against the SAME model in ``eval()`` (the dropout-free objective: the baseline, measured in the same session, alternating),
+same warm-up and sampling, with the time per kernel name of one more evaluation of each.
 Prints one JSON line per model.
 """
 import argparse
@@ -74,6 +77,41 @@ def kernel_ms():
         ent[1] += ms.value
     lib.kd_prof_reset()
     return {k: [n, round(t, 4)] for k, (n, t) in sorted(out.items(), key=lambda kv: -kv[1][1])}
+
+
+def dropout_bench(K, name, mc, sd, x, sigma, aug, B, rate):
+    """The ``--train --dropout`` line of one model."""
+    dev = x.device
+    cfg = K.config.load_config({"model": dict(mc, dropout_rate=rate), "dataset": {"type": "imagefolder", "num_classes": 0}})
+    model = K.config.make_model(cfg)
+    model.load_state_dict(sd)
+    model = model.to(dev).requires_grad_(True).enable_dropout(torch.Generator(device=dev).manual_seed(7))
+    noise = torch.randn(x.shape, generator=torch.Generator().manual_seed(5)).to(dev)
+    den = K.Denoiser(model, 0.5)
+
+    def run(training):
+        model.train(training)
+        model.zero_grad(set_to_none=True)
+        den.loss(x, noise, sigma, aug_cond=aug).mean().backward()
+    sides = {"eval_train_ms": lambda: run(False), "dropout_train_ms": lambda: run(True)}
+    for _ in range(5):
+        for fn in sides.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in sides}
+    for _ in range(7):
+        for k, fn in sides.items():
+            times[k].append(timed(fn))
+    line = {"model": name, "batch": B, "dropout_rate": rate, **{k: [statistics.median(t), min(t), max(t)] for k, t in times.items()}}
+    line["dropout_over_eval"] = line["dropout_train_ms"][0] / line["eval_train_ms"][0]
+    K._native.prof_enable(True)
+    for k, fn in sides.items():
+        K._native.lib().kd_prof_reset()
+        fn()
+        torch.cuda.synchronize()
+        line[k.replace("_ms", "_kernel_ms")] = kernel_ms()
+    K._native.prof_enable(False)
+    print(json.dumps(line), flush=True)
 
 
 def train_bench(K, ur, name, model, sd, x, sigma, aug, B, H, W):
@@ -173,7 +211,10 @@ def main():
     ap.add_argument("--dual", action="store_true")
     ap.add_argument("--vjp", action="store_true")
     ap.add_argument("--train", action="store_true")
+    ap.add_argument("--dropout", type=float, default=None, metavar="P", help="with --train: dropout at rate P against eval() of the same model")
     args = ap.parse_args()
+    if args.dropout is not None and not args.train:
+        ap.error("--dropout goes with --train")
     import k_diffusion_amd as K
     from tests import unet_ref as ur
     ur.USE_SDPA = True
@@ -191,6 +232,9 @@ def main():
         x = (torch.randn(B, C, H, W, generator=g).to(dev) * (sigma ** 2 + 0.25).sqrt()[:, None, None, None]).contiguous()
         aug = (0.5 * torch.randn(B, 9, generator=g)).to(dev)
         hip = lambda: model(x, sigma, aug_cond=aug)
+        if args.train and args.dropout is not None:
+            dropout_bench(K, name, mc, sd, x, sigma, aug, B, args.dropout)
+            continue
         if args.train:
             train_bench(K, ur, name, model, sd, x, sigma, aug, B, H, W)
             continue

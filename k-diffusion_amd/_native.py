@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("KDIFF_HIP_LIB") or os.path.join(_HERE, "csrc", "libkd
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_hip.h")
 GRAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_grad.h")
 TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_train.h")
+DROP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_drop.h")
 
 
 class NativeLibraryError(RuntimeError):
@@ -53,6 +54,15 @@ except OSError as e:
 if _train.structs or _train.constants or set(_train.signatures) & (set(SIGNATURES) | set(GRAD_SIGNATURES)):
     raise HeaderError(f"{TRAIN_HEADER_PATH}: prototypes of entry points the other two headers do not declare, and nothing else")
 TRAIN_SIGNATURES, TRAIN_RESTYPES = _train.signatures, _train.restypes
+# ... and its dropout kernels (csrc/unet_drop_f32.hip, one entry point each in csrc/conv_x3.hip and two in csrc/vjp_f32.hip): a fourth header, a fourth table
+try:
+    with open(DROP_HEADER_PATH) as _header:
+        _drop = parse(_header.read())
+except OSError as e:
+    raise NativeLibraryError(f"{DROP_HEADER_PATH}: the C ABI header the package binds from cannot be read ({e})") from e
+if _drop.structs or _drop.constants or set(_drop.signatures) & (set(SIGNATURES) | set(GRAD_SIGNATURES) | set(TRAIN_SIGNATURES)):
+    raise HeaderError(f"{DROP_HEADER_PATH}: prototypes of entry points the other three headers do not declare, and nothing else")
+DROP_SIGNATURES, DROP_RESTYPES = _drop.signatures, _drop.restypes
 _i, _f = C.c_int, C.c_float                  # the kinds encode_call tells apart (the parser hands out these very objects)
 
 # PREC_FP8 is a mode of the NETWORK, not a KdGemm.precision value: the bf16 mode with the AdaRMSNorm -> wide projections of the K = 256 / 512
@@ -132,7 +142,8 @@ def lib():
                 "(python -c 'import __graft_entry__ as g; g.build()' or make -C k-diffusion_amd/csrc). "
                 "There is no CPU / PyTorch fallback for the sampling hot path.")
         handle = C.CDLL(LIB_PATH)
-        for signatures, restypes in ((SIGNATURES, RESTYPES), (GRAD_SIGNATURES, GRAD_RESTYPES), (TRAIN_SIGNATURES, TRAIN_RESTYPES)):
+        for signatures, restypes in ((SIGNATURES, RESTYPES), (GRAD_SIGNATURES, GRAD_RESTYPES), (TRAIN_SIGNATURES, TRAIN_RESTYPES),
+                                     (DROP_SIGNATURES, DROP_RESTYPES)):
             for name, argtypes in signatures.items():
                 try:
                     fn = getattr(handle, name)

@@ -108,3 +108,8 @@ class KarrasAugmentWrapper(nn.Module):
 
     def set_patch_size(self, patch_size):
         return self.inner_model.set_patch_size(patch_size)
+
+    def enable_dropout(self, generator=None):
+        """The inner model's ``enable_dropout`` (opt-in dropout of the training loss); returns this wrapper."""
+        self.inner_model.enable_dropout(generator)
+        return self

@@ -19,7 +19,12 @@
 //
 // kd_conv2d_x3_stacked is the same kernel for the dual pass of log_likelihood, whose batch is [primal | tangent]: only the samples below
 // bias_batch get the bias.  A workgroup's sample index decides it, so an output's accumulation order -- and its bits -- are kd_conv2d_x3's.
+//
+// kd_conv2d_x3_drop (include/kdiff_unet_drop.h) is the same kernel again with the training loss's channel dropout in the epilogue:
+// y = (acc + bias) m[b, n] + res, m a column range of the loss call's factor table (kd_chan_mask_f32).  Without a table the epilogue takes
+// the branch it always took: the bits of kd_conv2d_x3.
 #include "x3_common.h"
+#include "../../include/kdiff_unet_drop.h"
 
 namespace kd {
 
@@ -43,6 +48,8 @@ struct ConvP {
   int H, W, c_in, c_out;
   int ty_n, tx_n, n_tiles;
   int bias_batch;                 // samples b < bias_batch get the bias (a stacked [primal | tangent] batch: the tangent of conv(x) + bias has none)
+  const float* chan_scale;        // kd_conv2d_x3_drop: the (sample, channel) dropout factors m[b * chan_stride + n], or NULL
+  int chan_stride;
 };
 
 __global__ __launch_bounds__(256) void pack_conv_kernel(const float* __restrict__ w, u16* __restrict__ out, int c_out, int c_in, int taps) {
@@ -137,6 +144,7 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(const ConvP p) {
   for (int nb = 0; nb < NB; ++nb) {
     const int n = n0 + (wn * NB + nb) * 32 + r;
     const float bv = (p.bias && b < p.bias_batch) ? p.bias[n] : 0.f;
+    const float ms = p.chan_scale ? p.chan_scale[(size_t)b * p.chan_stride + n] : 1.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int po = 32 * wm + mfma32_row(i, lane);
@@ -144,6 +152,7 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(const ConvP p) {
       if (gy < p.H && gx < p.W) {
         const size_t pix = pix0 + (size_t)gy * p.W + gx;
         float v = acc[nb][i] + bv;
+        if (p.chan_scale) v *= ms;
         if (p.res) v += p.res[pix * p.ldr + n];
         p.y[pix * p.ldy + n] = v;
       }
@@ -176,21 +185,22 @@ extern "C" int kd_pack_conv_x3(const float* w, void* out, int c_out, int c_in, i
 
 // bias_batch: the samples that get the bias (kd_conv2d_x3: all of them)
 static int conv2d_x3(const float* x, int ldx, const void* wp, const float* bias, const float* res, int ldr, float* y, int ldy, int batch, int H, int W,
-                     int c_in, int c_out, int ks, int bias_batch, void* stream) {
+                     int c_in, int c_out, int ks, int bias_batch, void* stream, const float* chan_scale = nullptr, int chan_stride = 0) {
   if (!x || !wp || !y || batch <= 0 || H <= 0 || W <= 0) return fail(KD_EINVAL, "kd_conv2d_x3: bad arguments");
   if (ks != 1 && ks != 3) return fail(KD_EINVAL, "kd_conv2d_x3: kernel size %d (1 or 3)", ks);
   if (c_in <= 0 || c_out <= 0 || (c_in % 64) || (c_out % 64))
     return fail(KD_EINVAL, "kd_conv2d_x3: c_in = %d and c_out = %d must be multiples of 64", c_in, c_out);
   if (ldx < c_in || (ldx & 3) || ldy < c_out || (res && ldr < c_out)) return fail(KD_EINVAL, "kd_conv2d_x3: a row stride is shorter than its row (or ldx is no multiple of 4)");
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wp)) & 15) return fail(KD_EINVAL, "kd_conv2d_x3: x and the packed weight must be 16-byte aligned");
-  ConvP p{x, (const u16*)wp, bias, res, y, ldx, ldr, ldy, H, W, c_in, c_out, (H + PATCH - 1) / PATCH, (W + PATCH - 1) / PATCH, 0, bias_batch};
+  ConvP p{x, (const u16*)wp, bias, res, y, ldx, ldr, ldy, H, W, c_in, c_out, (H + PATCH - 1) / PATCH, (W + PATCH - 1) / PATCH, 0, bias_batch, chan_scale, chan_stride};
   const int nb = (c_out % 128) ? 1 : 2;
   p.n_tiles = c_out / (64 * nb);
   const long n_wg = (long)batch * p.ty_n * p.tx_n * p.n_tiles;
   if (n_wg > 0x7FFFFFFFl || (long)batch * H * W > 0x7FFFFFFFl) return fail(KD_EINVAL, "kd_conv2d_x3: %ld workgroups exceed the grid", n_wg);
   hipStream_t s = (hipStream_t)stream;
   const double m = (double)batch * H * W;
-  ProfName nm("conv2d_x3", "conv2d_x3<k%d,n%d> M=%ld N=%d K=%d", ks, 64 * nb, (long)m, c_out, ks * ks * c_in);
+  ProfName nm(chan_scale ? "conv2d_x3_drop" : "conv2d_x3", "conv2d_x3%s<k%d,n%d> M=%ld N=%d K=%d", chan_scale ? "_drop" : "", ks, 64 * nb, (long)m, c_out,
+              ks * ks * c_in);
   LaunchScope prof(nm, 2.0 * m * c_out * ks * ks * c_in, 4.0 * m * (c_in + c_out * (res ? 2 : 1)) + 4.0 * ks * ks * c_in * c_out, s);
   if (ks == 3) return nb == 2 ? launch_conv<3, 2>(p, n_wg, s) : launch_conv<3, 1>(p, n_wg, s);
   return nb == 2 ? launch_conv<1, 2>(p, n_wg, s) : launch_conv<1, 1>(p, n_wg, s);
@@ -205,4 +215,10 @@ extern "C" int kd_conv2d_x3_stacked(const float* x, int ldx, const void* wp, con
                                     int batch, int H, int W, int c_in, int c_out, int ks, int bias_batch, void* stream) {
   if (bias_batch < 0 || bias_batch > batch) return fail(KD_EINVAL, "kd_conv2d_x3_stacked: bias_batch = %d outside 0 .. batch = %d", bias_batch, batch);
   return conv2d_x3(x, ldx, wp, bias, res, ldr, y, ldy, batch, H, W, c_in, c_out, ks, bias_batch, stream);
+}
+
+extern "C" int kd_conv2d_x3_drop(const float* x, int ldx, const void* wp, const float* bias, const float* res, int ldr, const float* chan_scale,
+                                 int chan_stride, float* y, int ldy, int batch, int H, int W, int c_in, int c_out, int ks, void* stream) {
+  if (chan_scale && chan_stride < c_out) return fail(KD_EINVAL, "kd_conv2d_x3_drop: chan_stride = %d shorter than c_out = %d", chan_stride, c_out);
+  return conv2d_x3(x, ldx, wp, bias, res, ldr, y, ldy, batch, H, W, c_in, c_out, ks, batch, stream, chan_scale, chan_scale ? chan_stride : 0);
 }

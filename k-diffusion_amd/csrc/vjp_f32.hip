@@ -7,6 +7,8 @@
 //   kd_geglu_vjp_f32         linear_geglu's gate (:89-95), erf-GELU (kd_geglu_vjp_drop_f32: with the hidden's dropout mask on g_y)
 //   kd_qk_prep_vjp_f32       scale_for_cosine_sim (:106-121) + axial RoPE (:187-231), scale held fixed
 //   kd_attn_*_vjp_f32        softmax attention: global (:383,:392), neighbourhood (:428), shifted window (:253-337)
+//   kd_attn_global_drop(_vjp)_f32  global attention with dropout on the probabilities (the image_v1 U-Net's SelfAttention2d in training mode,
+//                            k_diffusion/layers.py:181-200; include/kdiff_unet_drop.h): the same two passes under a DROP template flag
 //   kd_precond_vjp_f32       the Karras preconditioning's per-sample scalings (k_diffusion/layers.py:70-74, :88-90) on a gradient
 //
 // Products are plain fp32 FMAs on the VALU.  Every reduction has a fixed shape and order (shuffle trees, fixed key / query sweeps): no
@@ -14,6 +16,7 @@
 #include "kd_common.h"
 #include "deriv_f32.h"
 #include "philox.h"
+#include "../../include/kdiff_unet_drop.h"
 
 #include <cmath>
 
@@ -128,7 +131,26 @@ struct AttnVjpArgs {
   const float* qkv; const float* gout; float* gqkv; float* lse; float* dsum;
   int batch, nh, T, H, W, geo, shift;              // geo: window size (window) or kernel size (neighbourhood)
   int blocks_per_head;                             // query / key blocks per (sample, head)
+  // probability dropout (the DROP instantiations only; include/kdiff_unet_drop.h, attention site): element ((b nh + h) T + i) T4 + j
+  const long long* key; unsigned long long site; unsigned threshold; float scale; int T4;
+  float* out;                                      // DROP_FWD: the attention output [batch, T, nh 64]
 };
+
+enum { DROP_NONE = 0, DROP_VJP = 1, DROP_FWD = 2 };
+
+__device__ __forceinline__ unsigned row16_or(unsigned v) {
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, DPP_ROR8, 0xF, 0xF, true);
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, DPP_ROR4, 0xF, 0xF, true);
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, DPP_XOR2, 0xF, 0xF, true);
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, DPP_XOR1, 0xF, 0xF, true);
+  return v;
+}
+
+// keep bits of the four mask elements 4 quad .. 4 quad + 3 of `site` (bit k: element 4 quad + k is kept)
+__device__ __forceinline__ unsigned keep4(unsigned long long key, unsigned long long quad, unsigned long long site, unsigned threshold) {
+  const Philox4 r = philox4x32_10(key, quad, site);
+  return (r.x0 >= threshold ? 1u : 0u) | (r.x1 >= threshold ? 2u : 0u) | (r.x2 >= threshold ? 4u : 0u) | (r.x3 >= threshold ? 8u : 0u);
+}
 
 // Inverse neighbourhood along one axis: the queries i whose clamped window [start(i), start(i) + ks) holds key j.  start(i) =
 // clamp(i - ks/2, 0, len - ks) is monotone in i, so the set is the interval [inv_lo(j), inv_hi(j)]; near a border it holds more than ks
@@ -171,7 +193,7 @@ struct InvNaSet {
 template <int MODE> struct QuerySetOf { using type = KeySet<MODE>; };
 template <> struct QuerySetOf<KS_NA> { using type = InvNaSet; };
 
-template <int MODE>
+template <int MODE, int DROP = DROP_NONE>
 __global__ __launch_bounds__(256) void attn_vjp_q_kernel(AttnVjpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];       // [VKC][2: k, v][64]
   const int g = threadIdx.x >> 4, c = threadIdx.x & 15;
@@ -183,8 +205,20 @@ __global__ __launch_bounds__(256) void attn_vjp_q_kernel(AttnVjpArgs a) {
   KeySet<MODE> ks;
   ks.init(a, qb, g);
   const f32x4 q = *reinterpret_cast<const f32x4*>(base + ks.qtok * row_stride + 4 * c);
-  const f32x4 go = *reinterpret_cast<const f32x4*>(a.gout + ((long)b * a.T + ks.qtok) * o_stride + head * VDH + 4 * c);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  f32x4 go = zero;
+  if (DROP != DROP_FWD) go = *reinterpret_cast<const f32x4*>(a.gout + ((long)b * a.T + ks.qtok) * o_stride + head * VDH + 4 * c);
+  // DROP: the keep bits of this query's keys j0 .. j0 + 31 (bit kk: key j0 + kk): lane c < 8 draws the 4 keys of quad c, the row ORs them
+  unsigned long long mkey = 0, mrow = 0;
+  if (DROP) {
+    mkey = (unsigned long long)a.key[0];
+    mrow = (((unsigned long long)b * a.nh + head) * a.T + ks.qtok) * (unsigned long long)a.T4;
+  }
+  auto keep_bits = [&](int j0) -> unsigned {
+    unsigned bits = 0;
+    if (c < VKC / 4) bits = keep4(mkey, (mrow + j0 + 4 * c) >> 2, a.site, a.threshold) << (4 * c);
+    return row16_or(bits);
+  };
   auto load_chunk = [&](int j0) {
     __syncthreads();
     for (int idx = threadIdx.x; idx < VKC * 32; idx += 256) {
@@ -203,6 +237,7 @@ __global__ __launch_bounds__(256) void attn_vjp_q_kernel(AttnVjpArgs a) {
   float Z = 0.f, m = V_NEG_INF;
   for (int j0 = 0; j0 < ks.n_keys; j0 += VKC) {
     load_chunk(j0);
+    const unsigned keep = DROP ? keep_bits(j0) : 0u;
     float L[VKC];
     float mc = V_NEG_INF;
 #pragma unroll
@@ -220,10 +255,17 @@ __global__ __launch_bounds__(256) void attn_vjp_q_kernel(AttnVjpArgs a) {
       for (int kk = 0; kk < VKC; ++kk) {
         const float e = L[kk] == V_NEG_INF ? 0.f : expf(L[kk] - mn);
         Z += e;
-        A += e * *reinterpret_cast<const f32x4*>(lds + (kk * 2 + 1) * VDH + 4 * c);
+        if (DROP)
+          A += ((keep >> kk & 1u) ? e * a.scale : 0.f) * *reinterpret_cast<const f32x4*>(lds + (kk * 2 + 1) * VDH + 4 * c);
+        else
+          A += e * *reinterpret_cast<const f32x4*>(lds + (kk * 2 + 1) * VDH + 4 * c);
       }
       m = mn;
     }
+  }
+  if (DROP == DROP_FWD) {
+    if (ks.qactive) *reinterpret_cast<f32x4*>(a.out + ((long)b * a.T + ks.qtok) * o_stride + head * VDH + 4 * c) = A * (1.0f / Z);
+    return;
   }
   const float lse = m + logf(Z);
   const float D = row16_sum(dot4(go, A * (1.0f / Z)));
@@ -231,12 +273,14 @@ __global__ __launch_bounds__(256) void attn_vjp_q_kernel(AttnVjpArgs a) {
   f32x4 dq = zero;
   for (int j0 = 0; j0 < ks.n_keys; j0 += VKC) {
     load_chunk(j0);
+    const unsigned keep = DROP ? keep_bits(j0) : 0u;
 #pragma unroll 8
     for (int kk = 0; kk < VKC; ++kk) {
       const f32x4 kf = *reinterpret_cast<const f32x4*>(lds + (kk * 2 + 0) * VDH + 4 * c);
       const f32x4 vf = *reinterpret_cast<const f32x4*>(lds + (kk * 2 + 1) * VDH + 4 * c);
       const float l = row16_sum(dot4(q, kf));
-      const float dp = row16_sum(dot4(go, vf));
+      float dp = row16_sum(dot4(go, vf));
+      if (DROP) dp = (keep >> kk & 1u) ? dp * a.scale : 0.f;
       const float p = ks.allowed(a, j0 + kk) ? expf(l - lse) : 0.f;
       dq += (p * (dp - D)) * kf;
     }
@@ -251,7 +295,7 @@ __global__ __launch_bounds__(256) void attn_vjp_q_kernel(AttnVjpArgs a) {
   }
 }
 
-template <int MODE>
+template <int MODE, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_vjp_kv_kernel(AttnVjpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];       // [VKC][2: q, dO][64], then lse[VKC], D[VKC]
   float* lds_lse = lds + VKC * 2 * VDH;
@@ -270,6 +314,13 @@ __global__ __launch_bounds__(256) void attn_vjp_kv_kernel(AttnVjpArgs a) {
   const f32x4 v = *reinterpret_cast<const f32x4*>(base + qs.qtok * row_stride + 2 * o_stride + 4 * c);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   f32x4 dk = zero, dv = zero;
+  // DROP: the keep bits of this KEY under the queries i0 .. i0 + 31 (bit ii: query i0 + ii): lane c draws the key's quad at the queries
+  // i0 + c and i0 + c + 16 and takes the key's word, the row ORs them
+  unsigned long long mkey = 0, mhead = 0;
+  if (DROP) {
+    mkey = (unsigned long long)a.key[0];
+    mhead = ((unsigned long long)b * a.nh + head) * a.T;
+  }
   for (int i0 = 0; i0 < qs.n_keys; i0 += VKC) {
     __syncthreads();
     for (int idx = threadIdx.x; idx < VKC * 32; idx += 256) {
@@ -289,14 +340,30 @@ __global__ __launch_bounds__(256) void attn_vjp_kv_kernel(AttnVjpArgs a) {
       lds_d[ii] = in ? a.dsum[st_base + tok] : 0.f;
     }
     __syncthreads();
+    unsigned keep = 0;
+    if (DROP) {
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int ii = c + 16 * half;
+        const unsigned long long e = (mhead + (unsigned long long)min(i0 + ii, a.T - 1)) * (unsigned long long)a.T4 + qs.qtok;
+        keep |= (keep4(mkey, e >> 2, a.site, a.threshold) >> (qs.qtok & 3) & 1u) << ii;
+      }
+      keep = row16_or(keep);
+    }
 #pragma unroll 8
     for (int ii = 0; ii < VKC; ++ii) {
       const f32x4 qf = *reinterpret_cast<const f32x4*>(lds + (ii * 2 + 0) * VDH + 4 * c);
       const f32x4 gof = *reinterpret_cast<const f32x4*>(lds + (ii * 2 + 1) * VDH + 4 * c);
       const float l = row16_sum(dot4(qf, k));
-      const float dp = row16_sum(dot4(gof, v));
+      float dp = row16_sum(dot4(gof, v));
       const float p = qs.allowed(a, i0 + ii) ? expf(l - lds_lse[ii]) : 0.f;
-      dv += p * gof;
+      if (DROP) {
+        const float mk = (keep >> ii & 1u) ? a.scale : 0.f;
+        dp *= mk;
+        dv += (p * mk) * gof;
+      } else {
+        dv += p * gof;
+      }
       dk += (p * (dp - lds_d[ii])) * qf;
     }
   }
@@ -333,17 +400,17 @@ static unsigned vjp_grid(long n) {
   return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
-template <int MODE>
+template <int MODE, bool DROP = false>
 int launch_attn_vjp(const AttnVjpArgs& a, const char* name, hipStream_t s) {
   const long blocks = (long)a.batch * a.nh * a.blocks_per_head;
   if (blocks > 0x7FFFFFFFL) return fail(KD_EINVAL, "%s: grid too large", name);
   {
     LaunchScope prof(name, 0, 12.0 * (double)a.batch * a.T * a.nh * VDH, s);
-    hipLaunchKernelGGL(attn_vjp_q_kernel<MODE>, dim3((unsigned)blocks), dim3(256), VJP_LDS_Q, s, a);
+    hipLaunchKernelGGL((attn_vjp_q_kernel<MODE, DROP ? DROP_VJP : DROP_NONE>), dim3((unsigned)blocks), dim3(256), VJP_LDS_Q, s, a);
     if (int e = check_launch(name)) return e;
   }
   LaunchScope prof(name, 0, 16.0 * (double)a.batch * a.T * a.nh * VDH, s);
-  hipLaunchKernelGGL(attn_vjp_kv_kernel<MODE>, dim3((unsigned)blocks), dim3(256), VJP_LDS_KV, s, a);
+  hipLaunchKernelGGL((attn_vjp_kv_kernel<MODE, DROP>), dim3((unsigned)blocks), dim3(256), VJP_LDS_KV, s, a);
   return check_launch(name);
 }
 
@@ -400,6 +467,27 @@ extern "C" int kd_attn_global_vjp_f32(const float* qkv, const float* g_out, floa
   if (!qkv || !g_out || !g_qkv || !lse || !dsum || batch <= 0 || T <= 0 || nh <= 0) return fail(KD_EINVAL, "kd_attn_global_vjp_f32: bad arguments");
   AttnVjpArgs a{qkv, g_out, g_qkv, lse, dsum, batch, nh, T, 1, T, 0, 0, (T + 15) / 16};
   return launch_attn_vjp<KS_GLOBAL>(a, "attn_global_vjp_f32", (hipStream_t)stream);
+}
+
+// the U-Net's attention with dropout on the probabilities (include/kdiff_unet_drop.h): the forward is the q pass's first sweep
+extern "C" int kd_attn_global_drop_f32(const float* qkv, float* out, int batch, int T, int nh, const long long* key, unsigned long long site,
+                                       unsigned threshold, float scale, void* stream) {
+  if (!qkv || !out || !key || batch <= 0 || T <= 0 || nh <= 0) return fail(KD_EINVAL, "kd_attn_global_drop_f32: bad arguments");
+  AttnVjpArgs a{qkv, nullptr, nullptr, nullptr, nullptr, batch, nh, T, 1, T, 0, 0, (T + 15) / 16, key, site, threshold, scale, 4 * ((T + 3) / 4), out};
+  const long blocks = (long)batch * nh * a.blocks_per_head;
+  if (blocks > 0x7FFFFFFFL) return fail(KD_EINVAL, "kd_attn_global_drop_f32: grid too large");
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope prof("attn_global_drop_f32", 0, 16.0 * (double)batch * T * nh * VDH, s);
+  hipLaunchKernelGGL((attn_vjp_q_kernel<KS_GLOBAL, DROP_FWD>), dim3((unsigned)blocks), dim3(256), VJP_LDS_Q, s, a);
+  return check_launch("kd_attn_global_drop_f32");
+}
+
+extern "C" int kd_attn_global_drop_vjp_f32(const float* qkv, const float* g_out, float* g_qkv, float* lse, float* dsum, int batch, int T, int nh,
+                                           const long long* key, unsigned long long site, unsigned threshold, float scale, void* stream) {
+  if (!qkv || !g_out || !g_qkv || !lse || !dsum || !key || batch <= 0 || T <= 0 || nh <= 0)
+    return fail(KD_EINVAL, "kd_attn_global_drop_vjp_f32: bad arguments");
+  AttnVjpArgs a{qkv, g_out, g_qkv, lse, dsum, batch, nh, T, 1, T, 0, 0, (T + 15) / 16, key, site, threshold, scale, 4 * ((T + 3) / 4), nullptr};
+  return launch_attn_vjp<KS_GLOBAL, true>(a, "attn_global_drop_vjp_f32", (hipStream_t)stream);
 }
 
 extern "C" int kd_attn_window_vjp_f32(const float* qkv, const float* g_out, float* g_qkv, float* lse, float* dsum, int batch, int H, int W, int nh,

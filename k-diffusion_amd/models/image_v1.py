@@ -21,12 +21,16 @@ kernel launches over fp32 NHWC token buffers ``[B H W, C]``, built once per (bat
 
 * ``loss_forward`` (what ``Denoiser.loss`` calls: TRAINING) is the one pass behind autograd: a node whose differentiable inputs are the
   parameters; its backward is the reverse walk with the parameter-gradient kernels of csrc/conv_wgrad_x3.hip and csrc/unet_train_f32.hip
-  (``models/unet_train.py``).
+  (``models/unet_train.py``).  In training mode with ``dropout_rate > 0`` it applies the reference's dropout once ``enable_dropout()`` was
+  called: Dropout2d behind both convolutions of a residual block (whole (sample, channel) maps, in the convolutions' epilogues) and dropout on
+  the attention probabilities, on masks of the project's counter-based generator regenerated wherever they are needed, never stored
+  (``dropout_sites``; include/kdiff_unet_drop.h).
 
 Scope: the forward pass, its forward-mode derivative, its reverse-mode derivative w.r.t. the input (explicit methods: ``forward_jvp``,
 ``forward_vjp``) and the parameter gradients of the training loss (``loss_forward``; sigma and the conditioning get no gradient anywhere) in
 fp32-grade (split-bf16x3) arithmetic whatever ``KDIFF_GEMM`` says, ``patch_size == 1``, ``skip_stages == 0``, no variance output, no cross
-attention, no ``unet_cond``, no dropout (training mode with ``dropout_rate > 0`` is refused), channels that are multiples of 64, even H and W at
+attention, no ``unet_cond``, dropout in ``loss_forward`` only and only after ``enable_dropout()`` (otherwise training mode with
+``dropout_rate > 0`` is refused; ``model.eval()`` is always the dropout-free objective), channels that are multiples of 64, even H and W at
 every downsample.  Anything else is refused in the constructor; the sampling passes (``forward``, ``forward_jvp``, ``forward_vjp``) raise
 NotImplementedError under grad mode with something that requires grad.
 """
@@ -139,6 +143,34 @@ def level_sizes(model, H, W):
         if sizes[i][0] % 2 or sizes[i][1] % 2 or min(sizes[i]) < 2:
             raise ValueError(f"image_v1: input size {H}x{W}: level {i} is {sizes[i][0]}x{sizes[i][1]}, which the downsample cannot halve")
     return sizes
+
+
+DROPOUT_SITE = 1 << 62 | 1 << 33      # the bits every dropout site id of this family carries (include/kdiff_unet_drop.h, mask contract)
+
+
+def forward_layers(model):
+    """The residual blocks and attention layers of ``model`` in the order the forward walks them (the order of ``unet_vjp._primal``'s tape)."""
+    out = []
+    for block in model.u_net.d_blocks:
+        out += list(block)[1:]
+    for block in model.u_net.u_blocks:
+        out += list(block)[:-1]
+    return out
+
+
+def dropout_sites(model):
+    """The dropout sites of ``model`` (an ``ImageDenoiserModelV1``) in forward order: (site id, layer, kind, C).  The layer at position L of
+    ``forward_layers(model)``: a residual block has "conv1" = 2^62 | 2^33 | 2 L (Dropout2d behind its first convolution, C = c_mid) and "conv2" =
+    2^62 | 2^33 | (2 L + 1) (behind its second, C = c_out), an attention layer "attn" = 2^62 | 2^33 | 2 L (the softmax probabilities, C = c_in).
+    Bit 62 set, bit 63 clear, bit 33 set: disjoint from ``image_transformer_v2.dropout_sites``' ids under one key."""
+    out = []
+    for L, layer in enumerate(forward_layers(model)):
+        if isinstance(layer, _ResConvBlock):
+            out.append((DROPOUT_SITE | 2 * L, layer, "conv1", layer.c_mid))
+            out.append((DROPOUT_SITE | (2 * L + 1), layer, "conv2", layer.c_out))
+        else:
+            out.append((DROPOUT_SITE | 2 * L, layer, "attn", layer.c_in))
+    return out
 
 
 class _Plan:
@@ -363,6 +395,7 @@ class ImageDenoiserModelV1(nn.Module):
         self._plans = self._plan_cache.plans
         self._dual_cache = weights.PlanCache()         # the dual pass's plans: forward_jvp leaves ``_plans`` and its eviction order alone
         self._vjp_cache, self._vjp_fingerprint = weights.PlanCache(), None       # forward_vjp's weight-derived tensors (models/unet_vjp.py)
+        self._dropout_on, self._dropout_gen = False, None                        # enable_dropout(): not part of the state_dict
 
     def param_groups(self, base_lr=2e-4):
         """image_v1.py:117-133: the weights of ``mapping`` and ``u_net`` decay, everything else does not."""
@@ -379,6 +412,24 @@ class ImageDenoiserModelV1(nn.Module):
     def set_patch_size(self, patch_size):
         if patch_size != 1:
             raise ValueError(f"image_v1: patch_size={patch_size!r} is not supported on the HIP path (only patch_size=1)")
+
+    def enable_dropout(self, generator=None):
+        """Opt in to dropout in the training loss: from now on ``loss_forward`` (``Denoiser.loss``) of the model in training mode applies
+        ``dropout_rate`` at the reference's sites (``dropout_sites``), on masks of this project's counter-based generator
+        (include/kdiff_unet_drop.h, mask contract) -- not torch's dropout RNG stream.  Each such call draws one int64 key on the device from
+        ``generator`` (a torch.Generator on the model's device; None: the default generator of the input's device, so torch.manual_seed
+        governs it) without a host sync; the backward pass regenerates the same masks from it.  The sampling passes (``forward``,
+        ``forward_jvp``, ``forward_vjp``) have no dropout and keep refusing training mode with a rate: call model.eval() for them, which is
+        always the dropout-free objective.  The setting is not part of the state_dict.  Returns the model."""
+        if not 0.0 <= self.dropout_rate < 1.0:
+            raise ValueError(f"ImageDenoiserModelV1.enable_dropout: dropout_rate must lie in [0, 1) (dropout_rate = {self.dropout_rate})")
+        if generator is not None and not isinstance(generator, torch.Generator):
+            raise TypeError(f"enable_dropout: generator must be a torch.Generator or None (got {type(generator)})")
+        self._dropout_on, self._dropout_gen = True, generator
+        return self
+
+    def _dropout_applies(self):
+        return bool(self.training and self.dropout_rate)
 
     # ---- launch plans ---------------------------------------------------------------------------------------------------------------------
     def _weights_fingerprint(self):
@@ -421,15 +472,16 @@ class ImageDenoiserModelV1(nn.Module):
             raise ValueError("image_v1: unet_cond, cross_cond and return_variance are not supported on the HIP path")
 
     def _refuse_loss(self, input, sigma, mapping_cond, unet_cond=None, cross_cond=None, cross_cond_padding=None, return_variance=False):
-        """The refusals of ``loss_forward``: the parameters MAY require grad here; the data may not, and there is no dropout yet."""
+        """The refusals of ``loss_forward``: the parameters MAY require grad here; the data may not, and dropout is opt-in."""
         self._refuse_conditioning(unet_cond, cross_cond, cross_cond_padding, return_variance)
         for name, t in (("input", input), ("sigma", sigma), ("mapping_cond", mapping_cond)):
             if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
                 raise NotImplementedError(f"image_v1: loss_forward differentiates w.r.t. the parameters only; {name} gets no gradient (pass "
                                           f"{name}.detach(), or use forward_vjp for the input gradient)")
-        if self.training and self.dropout_rate:
+        if self._dropout_applies() and not self._dropout_on:
             raise NotImplementedError(f"image_v1: dropout_rate={self.dropout_rate} in training mode: the U-Net's Dropout2d is not implemented on the "
-                                      f"HIP path; call model.eval() for the dropout-free objective")
+                                      f"HIP path; call model.eval() for the dropout-free objective (or opt in with model.enable_dropout(): "
+                                      f"masks from this project's counter-based generator, in loss_forward only)")
         self._check_operands(input, mapping_cond)
 
     def _check_operands(self, input, mapping_cond, tangent=None, dual=False):
@@ -519,7 +571,8 @@ class ImageDenoiserModelV1(nn.Module):
         """F(input, sigma) for ``Denoiser.loss`` (which hands it the input already scaled by c_in): the forward's kernels on tensors of this
         call.  Under grad mode the output carries a ``grad_fn`` whose backward fills the ``.grad`` of every parameter that requires grad
         (models/unet_train.py); a parameter that does not costs no launch.  input, sigma and the conditioning get no gradient; training mode
-        with ``dropout_rate > 0`` is refused (``model.eval()`` gives the dropout-free objective).  The sampling passes above keep refusing
-        grad mode: training goes through here only."""
+        with ``dropout_rate > 0`` applies the dropout once ``enable_dropout()`` was called (one key drawn per call) and is refused without
+        it (``model.eval()`` gives the dropout-free objective).  The sampling passes above keep refusing grad mode: training goes through
+        here only."""
         from . import unet_train
         return unet_train.loss_forward(self, input, sigma, mapping_cond, **kwargs)

@@ -20,7 +20,16 @@ the backward; a second backward through a retained graph recomputes it.
     ``loss_forward`` receives the input already scaled by c_in, so no preconditioning is folded in.
 
 Arithmetic is fp32-grade (split-bf16 x 3 on the matrix cores, fp64 sums in the small rules) whatever ``KDIFF_GEMM`` says.  x, sigma and the
-conditioning get no gradient, and training mode with ``dropout_rate > 0`` is refused: the U-Net's Dropout2d has no HIP kernel yet.
+conditioning get no gradient.
+
+Dropout (training mode, ``dropout_rate > 0``, after ``model.enable_dropout()``; refused without it): ``loss_forward`` draws one int64 key on
+the device per call -- no host sync -- and hands it to the node as a saved input, so a second backward through a retained graph recomputes
+with the same masks.  ``make_drop`` fills the factors of ALL channel sites (two Dropout2d per residual block) in one ``kd_chan_mask_f32`` launch
+into a table [B, sum of C]; the convolutions of the primal and of the backward's recomputation apply them in their epilogues
+(``kd_conv2d_x3_drop``), the reverse walk applies the transpose with ``kd_chan_scale_f32`` (the weight-, bias- and AdaGN-gradient kernels
+take no mask), and the attention layers drop probabilities in ``kd_attn_global_drop_f32`` / ``kd_attn_global_drop_vjp_f32``.  No mask is
+stored: every consumer regenerates it from (key, site).  Contract: include/kdiff_unet_drop.h; sites: ``image_v1.dropout_sites``.
+``model.eval()`` and a rate of 0 take no key and no table and launch what they launched before.
 """
 from types import SimpleNamespace
 
@@ -118,8 +127,30 @@ def _cond_chain(model, c, keep, sink):
         sink.grads[id(model.mapping_cond.weight)] = _wgrad(g, keep.mc)
 
 
-def primal(model, x, sigma, mapping_cond):
-    """(F(x, sigma), state): the forward on tensors of this call, and what the backward needs of it."""
+def make_drop(model, key, B, consts):
+    """What the walks of models/unet_vjp.py take as ``drop`` for the loss call whose key (one int64 on the device) is ``key``: the key, the
+    rate, ``chan`` {residual block: (m1, m2)} -- the blocks' column ranges [B, C] of the table of channel factors, filled here in one launch --
+    and ``attn`` {attention layer: site id}."""
+    sites = v1.dropout_sites(model)
+    chan_sites = [(site, chan) for site, _, kind, chan in sites if kind != "attn"]
+    layout, _ = uo.chan_layout(chan_sites)
+    if getattr(consts, "drop_sites", None) is None:                     # the (site, offset, C) triples on this device: no copy per call
+        consts.drop_sites = torch.tensor(layout, dtype=torch.int64, device=key.device)
+    p = float(model.dropout_rate)
+    table = uo.chan_mask(key, layout, B, p, sites_dev=consts.drop_sites)
+    cols = {site: table[:, off:off + chan] for site, off, chan in layout}
+    chan, attn = {}, {}
+    for site, layer, kind, _ in sites:
+        if kind == "attn":
+            attn[layer] = site
+        elif kind == "conv1":
+            chan[layer] = (cols[site], cols[site + 1])
+    return SimpleNamespace(key=key, p=p, table=table, chan=chan, attn=attn)
+
+
+def primal(model, x, sigma, mapping_cond, drop=None):
+    """(F(x, sigma), state): the forward on tensors of this call, and what the backward needs of it.  ``drop``: the loss call's dropout key
+    (one int64 on the device; ``loss_forward`` draws it), None without dropout."""
     with torch.no_grad():
         x = x.contiguous()
         B, _, H, W = x.shape
@@ -134,9 +165,10 @@ def primal(model, x, sigma, mapping_cond):
         mc = None if mapping_cond is None else mapping_cond.to(device=x.device, dtype=torch.float32).contiguous()
         keep = SimpleNamespace(e=ws.ff if mc is None else ws.e, h1=ws.h1, h2=ws.h2, mc=mc)
         t0 = uo.unet_in(x, model.proj_in.weight, model.proj_in.bias)
-        last, tape = uv._primal(model, c, t0, sizes)
+        drop = None if drop is None else make_drop(model, drop, B, consts)
+        last, tape = uv._primal(model, c, t0, sizes, drop)
         out = uo.unet_out(last, model.proj_out.weight, model.proj_out.bias, tuple(x.shape))
-    return out, SimpleNamespace(c=c, keep=keep, tape=tape, last=last, sizes=sizes, fingerprint=fingerprint, x=x)
+    return out, SimpleNamespace(c=c, keep=keep, tape=tape, last=last, sizes=sizes, fingerprint=fingerprint, x=x, drop=drop)
 
 
 def backward(model, state, grad_out, want):
@@ -156,7 +188,7 @@ def backward(model, state, grad_out, want):
         if sink.wants(model.proj_out.bias):
             sink.grads[id(model.proj_out.bias)] = uo.bias_grad(go)
         g = uo.unet_in(go, c.consts.out_t)                               # proj_out^T: NCHW -> tokens
-        g = uv._reverse(model, c, state.tape, g, state.sizes, sink)
+        g = uv._reverse(model, c, state.tape, g, state.sizes, sink, state.drop)
         if sink.wants(model.proj_in.weight):
             sink.grads[id(model.proj_in.weight)] = _wgrad(g, x, gather=("a", ops.nat.WG_PATCH_NCHW), gather_geom=geom).view_as(model.proj_in.weight)
         if sink.wants(model.proj_in.bias):
@@ -167,13 +199,14 @@ def backward(model, state, grad_out, want):
 
 class _ParamGrad(torch.autograd.Function):
     """The inner model as an autograd node whose differentiable inputs are its parameters (``Denoiser.loss`` only), after ``_ParamGrad`` of
-    models/image_transformer_v2.py.  Forward: ``primal``; kept: its tape.  Backward: ``backward`` with the parameters autograd asks for."""
+    models/image_transformer_v2.py.  Forward: ``primal``; kept: its tape and the call's dropout key.  Backward: ``backward`` with the
+    parameters autograd asks for."""
 
     @staticmethod
-    def forward(ctx, x, model, sigma, mapping_cond, *params):
-        out, state = primal(model, x, sigma, mapping_cond)
+    def forward(ctx, x, model, sigma, mapping_cond, key, *params):
+        out, state = primal(model, x, sigma, mapping_cond, key)
         ctx.model, ctx.params, ctx.state = model, params, state
-        ctx.inputs = (x, sigma, mapping_cond)
+        ctx.inputs = (x, sigma, mapping_cond, key)                     # the dropout key with them: a recomputation draws the same masks
         return out
 
     @staticmethod
@@ -182,16 +215,19 @@ class _ParamGrad(torch.autograd.Function):
         if state is None:                                               # a second backward through a retained graph: the tape is gone
             _, state = primal(ctx.model, *ctx.inputs)
         ctx.state = None
-        need = ctx.needs_input_grad[4:]
+        need = ctx.needs_input_grad[5:]
         want = [p for p, n in zip(ctx.params, need) if n]
         grads = backward(ctx.model, state, grad, want)
-        return (None,) * 4 + tuple(grads.get(id(p)) if n else None for p, n in zip(ctx.params, need))
+        return (None,) * 5 + tuple(grads.get(id(p)) if n else None for p, n in zip(ctx.params, need))
 
 
 def loss_forward(model, x, sigma, mapping_cond=None, **kwargs):
     """F(x, sigma) of ``model`` (an ``ImageDenoiserModelV1``) for ``Denoiser.loss``: see the module docstring."""
     model._refuse_loss(x, sigma, mapping_cond, **kwargs)
+    key = None
+    if model._dropout_on and model._dropout_applies():                 # one key per call, drawn on the device: the host does not sync
+        key = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device=x.device, generator=model._dropout_gen)
     params = [p for p in model.parameters() if p.requires_grad] if torch.is_grad_enabled() else []
     if params:
-        return _ParamGrad.apply(x, model, sigma, mapping_cond, *params)
-    return primal(model, x, sigma, mapping_cond)[0]
+        return _ParamGrad.apply(x, model, sigma, mapping_cond, key, *params)
+    return primal(model, x, sigma, mapping_cond, key)[0]

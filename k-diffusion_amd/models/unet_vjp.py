@@ -20,6 +20,12 @@ the pre-norm t2 of a residual block, the qkv of an attention layer, the group st
 fp32-grade arithmetic whatever ``KDIFF_GEMM`` says, like the forward.  No launch plan of the forward or the dual pass is built, read or evicted:
 the few weight-derived tensors of this pass (the mappers' concatenated weight, the folded qkv weights, the transposed projections) live in a
 cache of their own, dropped when the weights fingerprint moves.
+
+``drop`` (the training loss in training mode after ``enable_dropout()``, models/unet_train.py: ``make_drop``; ``forward_vjp`` never passes
+one): the key of the loss call, the table of channel factors and every layer's site.  The channel masks ride in the epilogues of the two
+convolutions of a residual block (``kd_conv2d_x3_drop``), in the primal and in the recomputation alike; in reverse the gradient takes the
+mask's transpose (``unet_ops.chan_scale``) in front of each convolution's three consumers, and attention runs its dropout kernels.  None: the
+launches are the ones they were.
 """
 from types import SimpleNamespace
 
@@ -73,38 +79,44 @@ def _wb(c, norm):
     return c.table[:, off:off + 2 * norm.c_out]
 
 
-def _res_front(c, layer, x, hw):
-    """A residual block up to its second norm: (statistics of x, the first convolution's input t1, the pre-norm t2)."""
+def _res_front(c, layer, x, hw, drop=None):
+    """A residual block up to its second norm: (statistics of x, the first convolution's input t1, the pre-norm t2 -- behind the first
+    Dropout2d with ``drop``: the second norm's statistics see the mask)."""
     norm = layer.main[0]
     stats = uo.groupnorm_stats(x, c.B, norm.num_groups, norm.eps)
     t1 = uo.adagn_apply(x, stats, _wb(c, norm), gelu=True)
-    t2 = uo.conv2d(t1, layer.main[2].weight, c.B, *hw, bias=layer.main[2].bias)
+    t2 = uo.conv2d(t1, layer.main[2].weight, c.B, *hw, bias=layer.main[2].bias, chan_scale=None if drop is None else drop.chan[layer][0])
     return stats, t1, t2
 
 
-def _res_fwd(c, layer, x, y, hw):
-    _, _, t2 = _res_front(c, layer, x, hw)
+def _res_fwd(c, layer, x, y, hw, drop=None):
+    _, _, t2 = _res_front(c, layer, x, hw, drop)
     norm = layer.main[4]
     uo.adagn_apply(t2, uo.groupnorm_stats(t2, c.B, norm.num_groups, norm.eps), _wb(c, norm), gelu=True, out=t2)
     res = uo.conv2d(x, layer.skip.weight, c.B, *hw) if isinstance(layer.skip, nn.Conv2d) else x
-    uo.conv2d(t2, layer.main[6].weight, c.B, *hw, bias=layer.main[6].bias, residual=res, out=y)
+    uo.conv2d(t2, layer.main[6].weight, c.B, *hw, bias=layer.main[6].bias, residual=res, out=y,
+              chan_scale=None if drop is None else drop.chan[layer][1])
 
 
-def _res_vjp(c, layer, x, g, hw, sink=None):
+def _res_vjp(c, layer, x, g, hw, sink=None, drop=None):
     """The gradient of a residual block's input from the gradient g of its output.  ``sink`` (the training backward, models/unet_train.py) is
     shown every gradient a parameter of the block hangs on, beside the activation that met it in the forward; without one the launches are
-    ``forward_vjp``'s."""
-    stats0, t1, t2 = _res_front(c, layer, x, hw)
+    ``forward_vjp``'s.  With ``drop`` the second convolution's three consumers read m2 g from a buffer of its own (the skip path keeps g), and
+    the gradient that leaves the second norm is masked in place with m1 in front of the first convolution's."""
+    stats0, t1, t2 = _res_front(c, layer, x, hw, drop)
     n0, n4 = layer.main[0], layer.main[4]
     stats4 = uo.groupnorm_stats(t2, c.B, n4.num_groups, n4.eps)
+    g_m = g if drop is None else uo.chan_scale(g, drop.chan[layer][1], c.B)      # the gradient behind the second Dropout2d: a new buffer
     if sink is not None:
-        sink.conv(layer.main[6], g, lambda: uo.adagn_apply(t2, stats4, _wb(c, n4), gelu=True), hw)
+        sink.conv(layer.main[6], g_m, lambda: uo.adagn_apply(t2, stats4, _wb(c, n4), gelu=True), hw)
         if isinstance(layer.skip, nn.Conv2d):
             sink.conv(layer.skip, g, lambda: x, hw)
-    g2 = uo.conv2d_dgrad(g, layer.main[6].weight, c.B, *hw)
+    g2 = uo.conv2d_dgrad(g_m, layer.main[6].weight, c.B, *hw)
     if sink is not None:
         sink.norm(n4, t2, stats4, g2, gelu=True)
     uo.adagn_vjp_apply(t2, stats4, uo.adagn_vjp_stats(t2, stats4, _wb(c, n4), g2, gelu=True), _wb(c, n4), g2, gelu=True, out=g2)
+    if drop is not None:
+        uo.chan_scale(g2, drop.chan[layer][0], c.B, out=g2)
     if sink is not None:
         sink.conv(layer.main[2], g2, lambda: t1, hw)
     g1 = uo.conv2d_dgrad(g2, layer.main[2].weight, c.B, *hw)
@@ -124,20 +136,31 @@ def _attn_front(c, layer, x, hw):
     return stats, t1, qkv.view(c.B, hw[0] * hw[1], 3 * layer.c_in)
 
 
-def _attn_fwd(c, layer, x, y, hw):
+def _attn_core(layer, q3, drop):
+    """softmax(q k^T) v on the folded qkv; with ``drop`` the dropout on the probabilities at the layer's site."""
+    if drop is None:
+        return ops.attn_global(q3, layer.n_head)
+    return uo.attn_global_drop(q3, layer.n_head, drop.key, drop.attn[layer], drop.p)
+
+
+def _attn_fwd(c, layer, x, y, hw, drop=None):
     _, _, q3 = _attn_front(c, layer, x, hw)
-    a = ops.attn_global(q3, layer.n_head)
+    a = _attn_core(layer, q3, drop)
     uo.conv2d(a.view(-1, layer.c_in), layer.out_proj.weight, c.B, *hw, bias=layer.out_proj.bias, residual=x, out=y)
 
 
-def _attn_vjp(c, layer, x, g, hw, sink=None):
-    """The gradient of an attention layer's input from the gradient g of its output; ``sink`` as in ``_res_vjp``."""
+def _attn_vjp(c, layer, x, g, hw, sink=None, drop=None):
+    """The gradient of an attention layer's input from the gradient g of its output; ``sink`` as in ``_res_vjp``.  With ``drop`` the recomputed
+    attention output (out_proj's activation) and the reverse rule carry the probabilities' mask."""
     stats, t1, q3 = _attn_front(c, layer, x, hw)
     norm, C = layer.norm_in, layer.c_in
     if sink is not None:
-        sink.conv(layer.out_proj, g, lambda: ops.attn_global(q3, layer.n_head).view(-1, C), hw)
+        sink.conv(layer.out_proj, g, lambda: _attn_core(layer, q3, drop).view(-1, C), hw)
     ga = uo.conv2d_dgrad(g, layer.out_proj.weight, c.B, *hw)
-    gq = ops.attn_global_vjp(q3, ga.view(c.B, hw[0] * hw[1], C), layer.n_head)
+    if drop is None:
+        gq = ops.attn_global_vjp(q3, ga.view(c.B, hw[0] * hw[1], C), layer.n_head)
+    else:
+        gq = uo.attn_global_drop_vjp(q3, ga.view(c.B, hw[0] * hw[1], C), layer.n_head, drop.key, drop.attn[layer], drop.p)
     if sink is not None:                                                # gq is the gradient of the FOLDED projection's output: q rows / 8
         sink.conv(layer.qkv_proj, gq.view(-1, 3 * C), lambda: t1, hw, q_rows=C)
     g1 = uo.conv2d_dgrad(gq.view(-1, 3 * C), layer.qkv_proj.weight, c.B, *hw, q_rows=C)
@@ -146,13 +169,13 @@ def _attn_vjp(c, layer, x, g, hw, sink=None):
     return uo.adagn_vjp_apply(x, stats, uo.adagn_vjp_stats(x, stats, _wb(c, norm), g1), _wb(c, norm), g1, g_add=g, out=g1)
 
 
-def _primal(model, c, t0, sizes):
+def _primal(model, c, t0, sizes, drop=None):
     """The forward plan's walk (``image_v1._Plan``) on tensors of this call: (the last activation, the tape of steps with every layer's input)."""
     n, ch, B = len(model.depths), model.channels, c.B
     tape, cur, cats = [], t0, [None] * n
 
     def run(layer, x, y, hw):
-        (_res_fwd if isinstance(layer, v1._ResConvBlock) else _attn_fwd)(c, layer, x, y, hw)
+        (_res_fwd if isinstance(layer, v1._ResConvBlock) else _attn_fwd)(c, layer, x, y, hw, drop)
         tape.append(("layer", layer, x, hw))
         return y
     for i, block in enumerate(model.u_net.d_blocks):
@@ -182,14 +205,15 @@ def _primal(model, c, t0, sizes):
     return cur, tape
 
 
-def _reverse(model, c, tape, g, sizes, sink=None):
-    """The gradient of the first activation from the gradient g of the last, along the tape in reverse; ``sink`` as in ``_res_vjp``."""
+def _reverse(model, c, tape, g, sizes, sink=None, drop=None):
+    """The gradient of the first activation from the gradient g of the last, along the tape in reverse; ``sink`` as in ``_res_vjp``, ``drop``
+    the primal's."""
     ch, B = model.channels, c.B
     g_cat = {}                                                          # level -> gradient of its concat buffer [rows, 2 C]
     for step in reversed(tape):
         if step[0] == "layer":
             _, layer, x, hw = step
-            g = (_res_vjp if isinstance(layer, v1._ResConvBlock) else _attn_vjp)(c, layer, x, g, hw, sink)
+            g = (_res_vjp if isinstance(layer, v1._ResConvBlock) else _attn_vjp)(c, layer, x, g, hw, sink, drop)
         elif step[0] == "up":                                           # g: the concat buffer's; its left half came from up2
             i = step[1]
             g_cat[i - 1] = g

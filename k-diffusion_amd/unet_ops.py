@@ -1,15 +1,19 @@
 """Tensor-level wrappers over the C ABI of the image_v1 U-Net kernels (csrc/conv_x3.hip, csrc/unet_f32.hip; contracts: include/kdiff_hip.h)
 and of their reverse rules (csrc/unet_vjp_f32.hip; contracts: include/kdiff_unet_grad.h) and parameter-gradient rules (csrc/conv_wgrad_x3.hip,
-csrc/unet_train_f32.hip; contracts: include/kdiff_unet_train.h) -- the module's counterpart of ``ops``, as ``augmentation`` and ``data`` have
-theirs.
+csrc/unet_train_f32.hip; contracts: include/kdiff_unet_train.h) and dropout kernels (csrc/unet_drop_f32.hip and one entry point each of
+csrc/conv_x3.hip and csrc/vjp_f32.hip; contracts: include/kdiff_unet_drop.h) -- the module's counterpart of ``ops``, as ``augmentation`` and
+``data`` have theirs.
 
 Activations are fp32 NHWC, token-major: a 2-D tensor ``[B * H * W, C]`` whose row stride may exceed C (a column range of a wider buffer:
 ``buf[:, :C]`` and ``buf[:, C:]`` are the two halves of a skip concatenation, written in place by their producers).  Column 0 of such a view
 must stay 16-byte aligned.  ROCm tensors only; there is no CPU path.
 """
+import math
+
 import torch
 
 from . import _native as nat
+from . import ops
 from . import weights
 from .ops import _chk, _p, _stream
 
@@ -50,10 +54,12 @@ def pack_conv(weight, cache=True):
     return _packed.get(weight, None, None, build, cache=cache)
 
 
-def conv2d(x, weight, B, H, W, bias=None, residual=None, out=None, packed=None, bias_batch=None):
+def conv2d(x, weight, B, H, W, bias=None, residual=None, out=None, packed=None, bias_batch=None, chan_scale=None):
     """conv2d(x, weight, padding=ks // 2) + bias + residual on tokens x [B*H*W, C_in] -> [B*H*W, C_out] (``kd_conv2d_x3``), ks 1 or 3.
     ``out`` must not overlap x.  With ``bias_batch`` only the samples b < bias_batch get the bias (``kd_conv2d_x3_stacked``: a dual pass's
-    batch is [primal | tangent], and the tangent of conv(x) + bias has no bias)."""
+    batch is [primal | tangent], and the tangent of conv(x) + bias has no bias).  With ``chan_scale`` [B, C_out] (a site's column range of
+    ``chan_mask``'s table) the channel dropout of the training loss rides in the epilogue: (conv + bias) * chan_scale[b] + residual
+    (``kd_conv2d_x3_drop``)."""
     c_out, c_in, ks, _ = weight.shape
     ldx = _rows(x, "x", c_in)
     _tokens(x, B, H, W, "conv2d")
@@ -64,7 +70,14 @@ def conv2d(x, weight, B, H, W, bias=None, residual=None, out=None, packed=None, 
         raise ValueError("conv2d: out and residual have the rows of x")
     packed = pack_conv(weight) if packed is None else packed
     args = (_p(x), ldx, _p(packed), _p(None if bias is None else _chk(bias, "bias")), _p(residual), ldr, _p(out), ldy, B, H, W, c_in, c_out, ks)
-    if bias_batch is None:
+    if chan_scale is not None:
+        if bias_batch is not None:
+            raise ValueError("conv2d: chan_scale (the training loss's dropout) and bias_batch (the dual pass) exclude each other")
+        cs = _rows(chan_scale, "chan_scale", c_out)
+        if chan_scale.shape[0] != B:
+            raise ValueError(f"conv2d: chan_scale {tuple(chan_scale.shape)} != {(B, c_out)}")
+        nat.check(nat.lib().kd_conv2d_x3_drop(*args[:6], _p(chan_scale), cs, *args[6:], _stream()), "kd_conv2d_x3_drop")
+    elif bias_batch is None:
         nat.check(nat.lib().kd_conv2d_x3(*args, _stream()), "kd_conv2d_x3")
     else:
         nat.check(nat.lib().kd_conv2d_x3_stacked(*args, int(bias_batch), _stream()), "kd_conv2d_x3_stacked")
@@ -390,3 +403,104 @@ def bias_grad(g, out=None, accumulate=False, q_cols=0):
     nat.check(nat.lib().kd_bias_grad_f32(_p(g), ldg, _p(ws), _p(out), rows, cols, nchw, int(q_cols), int(bool(accumulate)), _stream()),
               "kd_bias_grad_f32")
     return out
+
+
+# ---- dropout of the training loss (csrc/unet_drop_f32.hip, csrc/conv_x3.hip, csrc/vjp_f32.hip; contracts: include/kdiff_unet_drop.h): what
+# ``ImageDenoiserModelV1.loss_forward`` adds in training mode after ``enable_dropout()``.  With a rate of 0 nothing here is called: the walk takes
+# no table and no key and launches what it launched before --------------------------------------------------------------------------------------------
+
+def drop_factors(p):
+    """(threshold, scale) of the mask contract for a rate p in (0, 1): keep iff word >= floor(p 2^32); a kept element times (float)(1 / (1 - p))."""
+    p = float(p)
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"dropout rate {p} outside (0, 1)")
+    return math.floor(p * 2.0 ** 32), 1.0 / (1.0 - p)
+
+
+def _key(key):
+    if _chk(key, "key", torch.int64).numel() != 1:
+        raise ValueError(f"dropout: the key is one int64 (got {key.numel()} elements)")
+    return _p(key)
+
+
+def chan_layout(sites):
+    """[(site id, column offset, C)] of the channel sites ``sites`` = [(site id, C)] in one table, and the table's width."""
+    out, off = [], 0
+    for site, chan in sites:
+        out.append((int(site), off, int(chan)))
+        off += int(chan)
+    return out, off
+
+
+def chan_mask(key, layout, B, p, sites_dev=None, out=None):
+    """table [B, sum of C]: the factor (0 or 1 / (1 - p)) of every (sample, channel) of ALL channel sites of a loss call, one launch
+    (``kd_chan_mask_f32``).  ``layout`` = ``chan_layout``'s triples; ``sites_dev``: the same triples as an int64 [n, 3] device tensor (built
+    here when None; the walk keeps one per device)."""
+    width = max((off + chan for _, off, chan in layout), default=0)
+    if not layout or any(off < 0 or chan <= 0 or not 0 <= site < 1 << 63 for site, off, chan in layout):
+        raise ValueError(f"chan_mask: layout {layout} is not a list of (site id, column offset, C)")
+    threshold, scale = drop_factors(p)
+    kp = _key(key)
+    if sites_dev is None:
+        sites_dev = torch.tensor(layout, dtype=torch.int64, device=key.device)
+    if tuple(_chk(sites_dev, "sites", torch.int64).shape) != (len(layout), 3):
+        raise ValueError(f"chan_mask: sites {tuple(sites_dev.shape)} != {(len(layout), 3)}")
+    out = torch.empty(B, width, device=key.device, dtype=torch.float32) if out is None else out
+    stride = _rows(out, "table")
+    if out.shape[0] != B or out.shape[1] < width:
+        raise ValueError(f"chan_mask: table {tuple(out.shape)} for batch {B} and {width} columns")
+    nat.check(nat.lib().kd_chan_mask_f32(kp, _p(sites_dev), len(layout), threshold, scale, _p(out), stride, B, _stream()), "kd_chan_mask_f32")
+    return out
+
+
+def chan_scale(g, m, B, out=None):
+    """out = g * m[b] per (sample, channel): the transpose of the channel mask on a gradient g [B*HW, C], m [B, C] a site's column range of the
+    table (``kd_chan_scale_f32``).  ``out`` may be g (in place)."""
+    ldg = _rows(g, "g")
+    chan = g.shape[1]
+    cs = _rows(m, "chan_scale", chan)
+    if m.shape[0] != B or g.shape[0] % B:
+        raise ValueError(f"chan_scale: chan_scale {tuple(m.shape)} / {g.shape[0]} rows for batch {B}")
+    out = torch.empty(g.shape[0], chan, device=g.device, dtype=torch.float32) if out is None else out
+    ldo = _rows(out, "out", chan)
+    if out.shape[0] != g.shape[0]:
+        raise ValueError("chan_scale: out has the rows of g")
+    nat.check(nat.lib().kd_chan_scale_f32(_p(g), ldg, _p(m), cs, _p(out), ldo, B, g.shape[0] // B, chan, _stream()), "kd_chan_scale_f32")
+    return out
+
+
+def _attn_dims(qkv, nh):
+    if _chk(qkv, "qkv").dim() != 3 or qkv.shape[2] != 3 * nh * 64:
+        raise ValueError(f"attention with dropout: qkv is [B, T, 3 * {nh} * 64] (got {tuple(qkv.shape)})")
+    return qkv.shape[0], qkv.shape[1]
+
+
+def attn_global_drop(qkv, nh, key, site, p, out=None):
+    """``ops.attn_global`` with dropout on the softmax probabilities (``kd_attn_global_drop_f32``): qkv [B, T, 3 nh 64] with the scale already
+    in q -> [B, T, nh 64].  p == 0: ``ops.attn_global`` itself."""
+    if not p:
+        return ops.attn_global(qkv, nh, out=out)
+    B, T = _attn_dims(qkv, nh)
+    threshold, scale = drop_factors(p)
+    out = torch.empty(B, T, nh * 64, device=qkv.device, dtype=torch.float32) if out is None else out
+    if tuple(_chk(out, "out").shape) != (B, T, nh * 64):
+        raise ValueError(f"attn_global_drop: out {tuple(out.shape)} != {(B, T, nh * 64)}")
+    nat.check(nat.lib().kd_attn_global_drop_f32(_p(qkv), _p(out), B, T, nh, _key(key), int(site), threshold, scale, _stream()),
+              "kd_attn_global_drop_f32")
+    return out
+
+
+def attn_global_drop_vjp(qkv, g_out, nh, key, site, p):
+    """g_qkv of ``attn_global_drop`` from the gradient g_out [B, T, nh 64] on its output (``kd_attn_global_drop_vjp_f32``); the masks are
+    regenerated from (key, site).  p == 0: ``ops.attn_global_vjp`` itself."""
+    if not p:
+        return ops.attn_global_vjp(qkv, g_out, nh)
+    B, T = _attn_dims(qkv, nh)
+    if tuple(_chk(g_out, "g_out").shape) != (B, T, nh * 64):
+        raise ValueError(f"attn_global_drop_vjp: g_out {tuple(g_out.shape)} != {(B, T, nh * 64)}")
+    threshold, scale = drop_factors(p)
+    g = torch.empty_like(qkv)
+    stats = torch.empty(2, B, nh, T, device=qkv.device, dtype=torch.float32)
+    nat.check(nat.lib().kd_attn_global_drop_vjp_f32(_p(qkv), _p(g_out), _p(g), _p(stats[0]), _p(stats[1]), B, T, nh, _key(key), int(site), threshold,
+                                                    scale, _stream()), "kd_attn_global_drop_vjp_f32")
+    return g
