@@ -21,6 +21,9 @@ zero-padded copies of A (timed without and with making the copies).
 ``--train --dropout P`` instead times the same training evaluation of a model with ``dropout_rate`` P in training mode after
 ``enable_dropout()`` against the SAME model in ``eval()`` (the dropout-free objective: the baseline, measured in the same session, alternating),
 same warm-up and sampling, with the time per kernel name of one more evaluation of each.
+``--train --wgrad bf16`` instead times the same training evaluation with and without ``set_wgrad_arithmetic("bf16")`` on the SAME model
+(alternating, 5 warm-up, 7 samples), with the time per kernel name of one more evaluation of each; then, per 3 x 3 convolution shape of the
+model's levels, ``kd_conv2d_wgrad_bf16`` against ``kd_conv2d_wgrad_x3`` on the same operands (alternating, 5 warm-up, 7 samples).
 Prints one JSON line per model.
 """
 import argparse
@@ -114,6 +117,68 @@ def dropout_bench(K, name, mc, sd, x, sigma, aug, B, rate):
     print(json.dumps(line), flush=True)
 
 
+def level_shapes(model, H, W):
+    """(h, w, c_in, c_out) of every 3 x 3 convolution shape of the model's levels."""
+    ch = model.inner_model.channels
+    shapes = []
+    for i, c in enumerate(ch):
+        for ci in sorted({c, ch[max(0, i - 1)], 2 * c if i < len(ch) - 1 else c}):
+            shapes.append((H >> i, W >> i, ci, c))
+    return shapes
+
+
+def wgrad_bench(K, name, model, x, sigma, aug, B, H, W):
+    """The ``--train --wgrad bf16`` lines of one model."""
+    dev = x.device
+    noise = torch.randn(x.shape, generator=torch.Generator().manual_seed(5)).to(dev)
+    den = K.Denoiser(model, 0.5)
+    model.requires_grad_(True)
+
+    def run(arithmetic):
+        model.set_wgrad_arithmetic(arithmetic)
+        model.zero_grad(set_to_none=True)
+        den.loss(x, noise, sigma, aug_cond=aug).mean().backward()
+    sides = {"split3_train_ms": lambda: run(None), "bf16_train_ms": lambda: run("bf16")}
+    for _ in range(5):
+        for fn in sides.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in sides}
+    for _ in range(7):
+        for k, fn in sides.items():
+            times[k].append(timed(fn))
+    line = {"model": name, "batch": B, **{k: [statistics.median(t), min(t), max(t)] for k, t in times.items()}}
+    line["bf16_over_split3"] = line["bf16_train_ms"][0] / line["split3_train_ms"][0]
+    K._native.prof_enable(True)
+    for k, fn in sides.items():
+        K._native.lib().kd_prof_reset()
+        fn()
+        torch.cuda.synchronize()
+        line[k.replace("_ms", "_kernel_ms")] = kernel_ms()
+    K._native.prof_enable(False)
+    print(json.dumps(line), flush=True)
+    model.set_wgrad_arithmetic(None).requires_grad_(False)
+    with torch.no_grad():
+        for h, w, ci, co in level_shapes(model, H, W):
+            a, gy = torch.randn(B * h * w, ci, device=dev), torch.randn(B * h * w, co, device=dev)
+            sides = {"conv2d_wgrad_x3_ms": lambda: K.unet_ops.conv2d_wgrad(gy, a, B, h, w, 3),
+                     "conv2d_wgrad_bf16_ms": lambda: K.unet_ops.conv2d_wgrad(gy, a, B, h, w, 3, bf16=True)}
+            for _ in range(5):
+                for fn in sides.values():
+                    fn()
+            torch.cuda.synchronize()
+            times = {k: [] for k in sides}
+            for _ in range(7):
+                for k, fn in sides.items():
+                    times[k].append(timed(fn))
+            x3, b16 = (fn() for fn in sides.values())
+            row = {"model": name, "shape": f"B{B} {h}x{w} {ci}->{co}", **{k: [statistics.median(t), min(t), max(t)] for k, t in times.items()},
+                   "chunks": K.unet_ops.conv_wgrad_chunks(B, h, w, ci, co)[1], "rel_diff": ((b16 - x3).abs().max() / x3.abs().max()).item()}
+            row["bf16_over_x3"] = row["conv2d_wgrad_bf16_ms"][0] / row["conv2d_wgrad_x3_ms"][0]
+            row["tflops_bf16"] = 2.0 * B * h * w * 9 * ci * co / row["conv2d_wgrad_bf16_ms"][0] / 1e9
+            print(json.dumps(row), flush=True)
+
+
 def train_bench(K, ur, name, model, sd, x, sigma, aug, B, H, W):
     """The ``--train`` lines of one model."""
     from torch.nn import functional as F
@@ -169,13 +234,8 @@ def train_bench(K, ur, name, model, sd, x, sigma, aug, B, H, W):
     print(json.dumps(line), flush=True)
     model.requires_grad_(False)
     # the weight-gradient kernel against nine ops.wgrad calls over shifted copies of A, per 3 x 3 shape of the levels
-    ch = model.inner_model.channels
-    shapes = []
-    for i, c in enumerate(ch):
-        for ci in sorted({c, ch[max(0, i - 1)], 2 * c if i < len(ch) - 1 else c}):
-            shapes.append((H >> i, W >> i, ci, c))
     with torch.no_grad():
-        for h, w, ci, co in shapes:
+        for h, w, ci, co in level_shapes(model, H, W):
             a, gy = torch.randn(B * h * w, ci, device=dev), torch.randn(B * h * w, co, device=dev)
 
             def shifted():
@@ -212,9 +272,12 @@ def main():
     ap.add_argument("--vjp", action="store_true")
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--dropout", type=float, default=None, metavar="P", help="with --train: dropout at rate P against eval() of the same model")
+    ap.add_argument("--wgrad", choices=["bf16"], default=None, help="with --train: set_wgrad_arithmetic('bf16') against the default on the same model")
     args = ap.parse_args()
     if args.dropout is not None and not args.train:
         ap.error("--dropout goes with --train")
+    if args.wgrad is not None and (not args.train or args.dropout is not None):
+        ap.error("--wgrad goes with --train, without --dropout")
     import k_diffusion_amd as K
     from tests import unet_ref as ur
     ur.USE_SDPA = True
@@ -234,6 +297,9 @@ def main():
         hip = lambda: model(x, sigma, aug_cond=aug)
         if args.train and args.dropout is not None:
             dropout_bench(K, name, mc, sd, x, sigma, aug, B, args.dropout)
+            continue
+        if args.train and args.wgrad is not None:
+            wgrad_bench(K, name, model, x, sigma, aug, B, H, W)
             continue
         if args.train:
             train_bench(K, ur, name, model, sd, x, sigma, aug, B, H, W)

@@ -14,6 +14,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_hip.h")
 GRAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_grad.h")
 TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_train.h")
 DROP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_drop.h")
+MIXED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_mixed.h")
 
 
 class NativeLibraryError(RuntimeError):
@@ -63,6 +64,15 @@ except OSError as e:
 if _drop.structs or _drop.constants or set(_drop.signatures) & (set(SIGNATURES) | set(GRAD_SIGNATURES) | set(TRAIN_SIGNATURES)):
     raise HeaderError(f"{DROP_HEADER_PATH}: prototypes of entry points the other three headers do not declare, and nothing else")
 DROP_SIGNATURES, DROP_RESTYPES = _drop.signatures, _drop.restypes
+# ... and the bf16 form of its convolution weight gradient (csrc/conv_wgrad_bf16.hip): a fifth header, a fifth table
+try:
+    with open(MIXED_HEADER_PATH) as _header:
+        _mixed = parse(_header.read())
+except OSError as e:
+    raise NativeLibraryError(f"{MIXED_HEADER_PATH}: the C ABI header the package binds from cannot be read ({e})") from e
+if _mixed.structs or _mixed.constants or set(_mixed.signatures) & (set(SIGNATURES) | set(GRAD_SIGNATURES) | set(TRAIN_SIGNATURES) | set(DROP_SIGNATURES)):
+    raise HeaderError(f"{MIXED_HEADER_PATH}: prototypes of entry points the other four headers do not declare, and nothing else")
+MIXED_SIGNATURES, MIXED_RESTYPES = _mixed.signatures, _mixed.restypes
 _i, _f = C.c_int, C.c_float                  # the kinds encode_call tells apart (the parser hands out these very objects)
 
 # PREC_FP8 is a mode of the NETWORK, not a KdGemm.precision value: the bf16 mode with the AdaRMSNorm -> wide projections of the K = 256 / 512
@@ -143,7 +153,7 @@ def lib():
                 "There is no CPU / PyTorch fallback for the sampling hot path.")
         handle = C.CDLL(LIB_PATH)
         for signatures, restypes in ((SIGNATURES, RESTYPES), (GRAD_SIGNATURES, GRAD_RESTYPES), (TRAIN_SIGNATURES, TRAIN_RESTYPES),
-                                     (DROP_SIGNATURES, DROP_RESTYPES)):
+                                     (DROP_SIGNATURES, DROP_RESTYPES), (MIXED_SIGNATURES, MIXED_RESTYPES)):
             for name, argtypes in signatures.items():
                 try:
                     fn = getattr(handle, name)

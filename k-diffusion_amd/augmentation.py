@@ -113,3 +113,11 @@ class KarrasAugmentWrapper(nn.Module):
         """The inner model's ``enable_dropout`` (opt-in dropout of the training loss); returns this wrapper."""
         self.inner_model.enable_dropout(generator)
         return self
+
+    def set_wgrad_arithmetic(self, arithmetic=None):
+        """The inner model's ``set_wgrad_arithmetic`` (opt-in bf16 weight gradients of the training loss); returns this wrapper."""
+        self.inner_model.set_wgrad_arithmetic(arithmetic)
+        return self
+
+    def _dropout_rates(self):
+        return self.inner_model._dropout_rates()

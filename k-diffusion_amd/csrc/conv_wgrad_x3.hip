@@ -25,6 +25,7 @@
 // partials in ascending order and writes nn.Conv2d's [co][ci][ky][kx] layout, so that the result is the parameter's .grad as it stands.  No
 // atomics: the order of every sum is fixed, a second run gives the same bits.
 #include "x3_common.h"
+#include "conv_wgrad_reduce.h"
 #include "../../include/kdiff_unet_train.h"
 
 namespace kd {
@@ -149,22 +150,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WgP p) {
       const int co = co0 + 32 * wm + mfma32_row(i, lane);
       dst[t * plane + (size_t)co * p.c_in] = acc[t][i];
     }
-}
-
-// dw[co][ci][tap] (+)= scale(co) * sum over the chunks, ascending, of ws[chunk][tap][co][ci]; a thread's index runs ci-fastest over the workspace
-__global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int c_out, int c_in, int taps,
-                                                                int nchunk, int q_rows, int accumulate) {
-  const long plane = (long)c_out * c_in, n_el = plane * taps;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_el; i += (long)gridDim.x * 256) {
-    const int tap = (int)(i / plane);
-    const long rem = i - tap * plane;
-    const int co = (int)(rem / c_in);
-    float sum = 0.f;
-    for (int k = 0; k < nchunk; ++k) sum += ws[(long)k * n_el + i];
-    if (co < q_rows) sum *= 0.125f;
-    float* o = dw + rem * taps + tap;
-    *o = accumulate ? *o + sum : sum;
-  }
 }
 
 template <int KS>

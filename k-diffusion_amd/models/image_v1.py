@@ -21,14 +21,16 @@ kernel launches over fp32 NHWC token buffers ``[B H W, C]``, built once per (bat
 
 * ``loss_forward`` (what ``Denoiser.loss`` calls: TRAINING) is the one pass behind autograd: a node whose differentiable inputs are the
   parameters; its backward is the reverse walk with the parameter-gradient kernels of csrc/conv_wgrad_x3.hip and csrc/unet_train_f32.hip
-  (``models/unet_train.py``).  In training mode with ``dropout_rate > 0`` it applies the reference's dropout once ``enable_dropout()`` was
+  (``models/unet_train.py``); ``set_wgrad_arithmetic("bf16")`` moves the weight-gradient products, and nothing else, to bf16 operands
+  (csrc/conv_wgrad_bf16.hip, ``ops.wgrad(bf16=True)``: train.py's ``--mixed-precision bf16``).  In training mode with ``dropout_rate > 0`` it applies the reference's dropout once ``enable_dropout()`` was
   called: Dropout2d behind both convolutions of a residual block (whole (sample, channel) maps, in the convolutions' epilogues) and dropout on
   the attention probabilities, on masks of the project's counter-based generator regenerated wherever they are needed, never stored
   (``dropout_sites``; include/kdiff_unet_drop.h).
 
 Scope: the forward pass, its forward-mode derivative, its reverse-mode derivative w.r.t. the input (explicit methods: ``forward_jvp``,
 ``forward_vjp``) and the parameter gradients of the training loss (``loss_forward``; sigma and the conditioning get no gradient anywhere) in
-fp32-grade (split-bf16x3) arithmetic whatever ``KDIFF_GEMM`` says, ``patch_size == 1``, ``skip_stages == 0``, no variance output, no cross
+fp32-grade (split-bf16x3) arithmetic whatever ``KDIFF_GEMM`` says (the weight-gradient products in bf16 after
+``set_wgrad_arithmetic("bf16")``), ``patch_size == 1``, ``skip_stages == 0``, no variance output, no cross
 attention, no ``unet_cond``, dropout in ``loss_forward`` only and only after ``enable_dropout()`` (otherwise training mode with
 ``dropout_rate > 0`` is refused; ``model.eval()`` is always the dropout-free objective), channels that are multiples of 64, even H and W at
 every downsample.  Anything else is refused in the constructor; the sampling passes (``forward``, ``forward_jvp``, ``forward_vjp``) raise
@@ -396,6 +398,7 @@ class ImageDenoiserModelV1(nn.Module):
         self._dual_cache = weights.PlanCache()         # the dual pass's plans: forward_jvp leaves ``_plans`` and its eviction order alone
         self._vjp_cache, self._vjp_fingerprint = weights.PlanCache(), None       # forward_vjp's weight-derived tensors (models/unet_vjp.py)
         self._dropout_on, self._dropout_gen = False, None                        # enable_dropout(): not part of the state_dict
+        self.wgrad_arithmetic = None                                             # set_wgrad_arithmetic(): not part of the state_dict
 
     def param_groups(self, base_lr=2e-4):
         """image_v1.py:117-133: the weights of ``mapping`` and ``u_net`` decay, everything else does not."""
@@ -427,6 +430,23 @@ class ImageDenoiserModelV1(nn.Module):
             raise TypeError(f"enable_dropout: generator must be a torch.Generator or None (got {type(generator)})")
         self._dropout_on, self._dropout_gen = True, generator
         return self
+
+    def set_wgrad_arithmetic(self, arithmetic=None):
+        """Opt in to bf16 weight gradients in the training loss.  ``None`` (the default): split-bf16 x 3, the family's fp32-grade arithmetic.
+        ``"bf16"``: every weight-gradient product of ``loss_forward``'s backward -- the convolutions' (``kd_conv2d_wgrad_bf16``,
+        include/kdiff_unet_mixed.h, ks = 3 and ks = 1) and the GEMMs of the mappers, ``mapping``, ``mapping_cond``, ``proj_in`` and ``proj_out``
+        (``ops.wgrad(bf16=True)``) -- rounds both operands once to bf16 and accumulates in fp32, one MFMA per product: a ``Conv2d`` / ``Linear``
+        backward of the reference under ``--mixed-precision bf16``.  Only those products move: the primal (so the loss), the data-gradient
+        convolutions, AdaGN and its (w, b) sums, the bias gradients, the attention rules, the way back through the mappers, the dropout masks
+        and ``forward_vjp`` keep their arithmetic.  The setting is not part of the state_dict.  Returns the model."""
+        if arithmetic not in (None, "bf16"):
+            raise ValueError(f"ImageDenoiserModelV1.set_wgrad_arithmetic: {arithmetic!r} (None or 'bf16')")
+        self.wgrad_arithmetic = arithmetic
+        return self
+
+    def _dropout_rates(self):
+        """(name, rate) of every dropout rate of the model: what ``enable_dropout`` serves (train.py's opt-in test, as the transformer's)."""
+        return [("dropout_rate", self.dropout_rate)]
 
     def _dropout_applies(self):
         return bool(self.training and self.dropout_rate)

@@ -22,6 +22,12 @@ the backward; a second backward through a retained graph recomputes it.
 Arithmetic is fp32-grade (split-bf16 x 3 on the matrix cores, fp64 sums in the small rules) whatever ``KDIFF_GEMM`` says.  x, sigma and the
 conditioning get no gradient.
 
+``model.set_wgrad_arithmetic("bf16")`` moves every weight-gradient PRODUCT, and nothing else, to bf16 operands with fp32 accumulation: the
+convolutions' go to ``kd_conv2d_wgrad_bf16`` (csrc/conv_wgrad_bf16.hip; ks = 3 and ks = 1), the GEMMs of the mappers, ``mapping``,
+``mapping_cond``, ``proj_in`` and ``proj_out`` to ``ops.wgrad(bf16=True)``.  The primal (so the loss bits), the data-gradient convolutions,
+AdaGN and its (w, b) sums, the bias gradients, the attention rules, ``g_table map_w`` (the way back through the mappers: a data gradient that
+uses ``ops.wgrad``) and the dropout masks stay as they are.
+
 Dropout (training mode, ``dropout_rate > 0``, after ``model.enable_dropout()``; refused without it): ``loss_forward`` draws one int64 key on
 the device per call -- no host sync -- and hands it to the node as a saved input, so a second backward through a retained graph recomputes
 with the same masks.  ``make_drop`` fills the factors of ALL channel sites (two Dropout2d per residual block) in one ``kd_chan_mask_f32`` launch
@@ -44,8 +50,9 @@ from . import unet_vjp as uv
 _X3 = ops.nat.PREC_SPLIT3
 
 
-def _wgrad(G, A, **kw):
-    return ops.wgrad(G, A, precision=_X3, **kw)
+def _wgrad(G, A, bf16=False, **kw):
+    """A weight-gradient GEMM dW = G^T A: split3, or (``set_wgrad_arithmetic("bf16")``) both operands rounded once to bf16."""
+    return ops.wgrad(G, A, precision=_X3, bf16=bf16, **kw)
 
 
 class _TrainConsts:
@@ -67,6 +74,7 @@ class _Sink:
 
     def __init__(self, model, c, want):
         self.c, self.want, self.grads = c, {id(p) for p in want}, {}
+        self.bf16 = model.wgrad_arithmetic == "bf16"                   # the weight-gradient products alone; every other rule stays fp32-grade
         norms = list(c.consts.offsets)
         chain = [model.mapping[0].weight, model.mapping[0].bias, model.mapping[2].weight, model.mapping[2].bias]
         if hasattr(model, "mapping_cond"):
@@ -82,7 +90,7 @@ class _Sink:
         """A convolution ``layer`` whose output has the gradient g and whose input was a() (built only if the weight is asked for)."""
         if self.wants(layer.weight):
             ks = layer.weight.shape[2]
-            self.grads[id(layer.weight)] = uo.conv2d_wgrad(g, a(), self.c.B, hw[0], hw[1], ks, q_rows=q_rows)
+            self.grads[id(layer.weight)] = uo.conv2d_wgrad(g, a(), self.c.B, hw[0], hw[1], ks, q_rows=q_rows, bf16=self.bf16)
         if self.wants(layer.bias):
             self.grads[id(layer.bias)] = uo.bias_grad(g, q_cols=q_rows)
 
@@ -99,7 +107,7 @@ def _cond_chain(model, c, keep, sink):
         return
     gt, offsets = sink.g_table, c.consts.offsets
     if any(sink.wants(m.mapper.weight) for m in offsets):
-        gw = _wgrad(gt, keep.h2)                                        # [sum of 2 C, feats]: every mapper's rows at its offset
+        gw = _wgrad(gt, keep.h2, bf16=sink.bf16)                                        # [sum of 2 C, feats]: every mapper's rows at its offset
         for m, off in offsets.items():
             if sink.wants(m.mapper.weight):
                 sink.grads[id(m.mapper.weight)] = gw[off:off + 2 * m.c_out]
@@ -113,18 +121,19 @@ def _cond_chain(model, c, keep, sink):
     tc = _train_consts(model, c.consts)
     # g_table map_w, the gradient of mapping's output: the sum runs over ALL mappers' columns (tens of thousands at the CIFAR-shaped model), which
     # the few-rows kernel would walk once per sample; read as a sum over ROWS of gt^T and map_w it is the weight-gradient GEMM's shape
+    # (a DATA gradient in the weight-gradient kernel's clothes: it stays split3 under set_wgrad_arithmetic("bf16"))
     g = _wgrad(gt.t().contiguous(), c.consts.map_w)
     for lin, w_t, x_in, has_more in ((model.mapping[2], tc.m2_t, keep.h1, True), (model.mapping[0], tc.m0_t, keep.e, hasattr(model, "mapping_cond"))):
         pre = uo.cond_mlp(x_in, lin.weight, lin.bias)                   # the pre-activation of this layer, recomputed
         g = uo.gelu_vjp(pre, g, out=g)
         if sink.wants(lin.weight):
-            sink.grads[id(lin.weight)] = _wgrad(g, x_in)
+            sink.grads[id(lin.weight)] = _wgrad(g, x_in, bf16=sink.bf16)
         if sink.wants(lin.bias):
             sink.grads[id(lin.bias)] = ops.colsum(g).reshape(-1)
         if has_more:
             g = uo.cond_mlp(g, w_t)
     if hasattr(model, "mapping_cond") and sink.wants(model.mapping_cond.weight):
-        sink.grads[id(model.mapping_cond.weight)] = _wgrad(g, keep.mc)
+        sink.grads[id(model.mapping_cond.weight)] = _wgrad(g, keep.mc, bf16=sink.bf16)
 
 
 def make_drop(model, key, B, consts):
@@ -183,14 +192,15 @@ def backward(model, state, grad_out, want):
         sink = _Sink(model, c, want)
         geom = (H, W, 1, 1, c_img)
         if sink.wants(model.proj_out.weight):
-            sink.grads[id(model.proj_out.weight)] = _wgrad(go, state.last, gather=("g", ops.nat.WG_PATCH_NCHW), gather_geom=geom).view_as(
+            sink.grads[id(model.proj_out.weight)] = _wgrad(go, state.last, bf16=sink.bf16, gather=("g", ops.nat.WG_PATCH_NCHW), gather_geom=geom).view_as(
                 model.proj_out.weight)
         if sink.wants(model.proj_out.bias):
             sink.grads[id(model.proj_out.bias)] = uo.bias_grad(go)
         g = uo.unet_in(go, c.consts.out_t)                               # proj_out^T: NCHW -> tokens
         g = uv._reverse(model, c, state.tape, g, state.sizes, sink, state.drop)
         if sink.wants(model.proj_in.weight):
-            sink.grads[id(model.proj_in.weight)] = _wgrad(g, x, gather=("a", ops.nat.WG_PATCH_NCHW), gather_geom=geom).view_as(model.proj_in.weight)
+            sink.grads[id(model.proj_in.weight)] = _wgrad(g, x, bf16=sink.bf16, gather=("a", ops.nat.WG_PATCH_NCHW), gather_geom=geom).view_as(
+                model.proj_in.weight)
         if sink.wants(model.proj_in.bias):
             sink.grads[id(model.proj_in.bias)] = uo.bias_grad(g)
         _cond_chain(model, c, state.keep, sink)

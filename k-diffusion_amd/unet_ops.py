@@ -338,11 +338,12 @@ def conv_wgrad_chunks(B, H, W, c_in, c_out):
     return per_chunk, -(-patches // per_chunk)
 
 
-def conv2d_wgrad(g, a, B, H, W, ks, out=None, accumulate=False, q_rows=0, chunks=None):
+def conv2d_wgrad(g, a, B, H, W, ks, out=None, accumulate=False, q_rows=0, chunks=None, bf16=False):
     """dW [C_out, C_in, ks, ks] (+)= the weight gradient of ``conv2d(a, weight)`` (ks 1 or 3, padding ks // 2) from the gradient g
     [B*H*W, C_out] on its output and its input a [B*H*W, C_in] (``kd_conv2d_wgrad_x3``).  ``q_rows``: the first q_rows output channels ran
     with a folded 1 / 8 (the q rows of a qkv projection), and the gradient of the stored weight takes it too.  ``chunks`` = (patches per chunk,
-    chunk count) overrides ``conv_wgrad_chunks`` (a test choosing its own cut of the sum)."""
+    chunk count) overrides ``conv_wgrad_chunks`` (a test choosing its own cut of the sum).  ``bf16``: both operands rounded once to bf16, one
+    bf16 MFMA per product with fp32 accumulation (``kd_conv2d_wgrad_bf16``, include/kdiff_unet_mixed.h) -- the same contract otherwise."""
     ldg, lda = _rows(g, "g"), _rows(a, "a")
     c_out, c_in = g.shape[1], a.shape[1]
     _tokens(g, B, H, W, "conv2d_wgrad")
@@ -355,8 +356,9 @@ def conv2d_wgrad(g, a, B, H, W, ks, out=None, accumulate=False, q_rows=0, chunks
         raise ValueError(f"conv2d_wgrad: out {tuple(out.shape)} != {(c_out, c_in, ks, ks)}")
     per_chunk, nchunk = conv_wgrad_chunks(B, H, W, c_in, c_out) if chunks is None else chunks
     ws = torch.empty(max(nchunk, 1) * ks * ks * c_out * c_in, device=g.device, dtype=torch.float32)
-    nat.check(nat.lib().kd_conv2d_wgrad_x3(_p(g), ldg, _p(a), lda, _p(ws), _p(out), B, H, W, c_in, c_out, ks, int(q_rows), int(per_chunk), int(nchunk),
-                                           int(bool(accumulate)), _stream()), "kd_conv2d_wgrad_x3")
+    name = "kd_conv2d_wgrad_bf16" if bf16 else "kd_conv2d_wgrad_x3"
+    nat.check(getattr(nat.lib(), name)(_p(g), ldg, _p(a), lda, _p(ws), _p(out), B, H, W, c_in, c_out, ks, int(q_rows), int(per_chunk), int(nchunk),
+                                       int(bool(accumulate)), _stream()), name)
     return out
 
 

@@ -16,6 +16,11 @@ sampler all run on this project's HIP kernels.  Differences from the reference, 
     workers with scikit-image; here K.augmentation warps the uploaded batch on the device, with parameters from this project's counter-based
     generator (one key per step from the default device generator -- not the reference's torch draws).  Without the flag such a config is
     refused; with ``augment_prob`` 0, ``aug_cond`` is zeros [B, 9], what the reference's disabled pipeline yields;
+  * both model families train: ``image_transformer_v2`` and the ``image_v1`` U-Net (bare, or in its augmentation wrapper, which is where
+    ``aug_cond`` goes; a bare U-Net gets none).  ``check_model_config`` refuses, before a device is asked for, what the U-Net cannot take:
+    class conditioning, augmentation without the wrapper, an ``input_size`` that some downsample cannot halve;
+  * ``--mixed-precision bf16`` is the weight gradients' arithmetic alone (``model.set_wgrad_arithmetic('bf16')``: bf16 operands, fp32
+    accumulation, on the trained model); everything else stays fp32;
   * a checkpoint also holds the RNG states and the position in the epoch, and the data order is a function of (seed, epoch), so that
     ``--resume`` continues the run it was saved from bit for bit (the reference restarts the epoch and its RNG streams).
 """
@@ -28,6 +33,7 @@ import os
 from pathlib import Path
 import sys
 import time
+from types import SimpleNamespace
 
 import torch
 from torch.utils import data
@@ -59,7 +65,7 @@ def parse_args(argv=None):
     p.add_argument('--evaluate-only', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--evaluate-every', type=int, default=0, help=argparse.SUPPRESS)
     p.add_argument('--evaluate-n', type=int, default=0, help=argparse.SUPPRESS)
-    p.add_argument('--mixed-precision', type=str, help="'bf16': the weight-gradient GEMMs run on bf16 operands with fp32 accumulation")
+    p.add_argument('--mixed-precision', type=str, help="'bf16': the weight-gradient GEMMs (and, for image_v1, convolutions) run on bf16 operands with fp32 accumulation")
     p.add_argument('--compile', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--checkpointing', action='store_true', help=argparse.SUPPRESS)
     args = p.parse_args(argv)
@@ -125,6 +131,24 @@ def check_dataset_config(config, class_emb_rows=None):
                          f'(num_classes + 1: the last row is the dropped label); the model has {class_emb_rows}')
 
 
+def check_model_config(config):
+    """Refuses, with a reason and before a device is asked for, a model section this command line cannot train.  Pure: it builds nothing.
+    For ``image_v1``: class conditioning, augmentation without the wrapper that takes ``aug_cond``, and an ``input_size`` that some
+    downsample cannot halve; ``patch_size``, ``skip_stages``, ``has_variance``, ``cross_cond_dim``, ``unet_cond_dim`` and the channel
+    multiples are the constructor's refusals, by field name."""
+    model_config, dataset_config = config['model'], config['dataset']
+    if dataset_config.get('num_classes', 0) > 0:
+        if model_config['type'] == 'image_v1':
+            raise NotImplementedError('dataset.num_classes > 0 with model type image_v1: the U-Net takes no class_cond, so Denoiser.loss has '
+                                      'nowhere to hand the labels; set dataset.num_classes to 0, or train an image_transformer_v2')
+    if model_config['type'] != 'image_v1':
+        return
+    if model_config.get('augment_prob', 0) > 0 and not model_config.get('augment_wrapper', True):
+        raise NotImplementedError('augment_prob > 0 with augment_wrapper: false: a bare image_v1 U-Net has nowhere for aug_cond to go; set '
+                                  'augment_wrapper to true, or augment_prob to 0')
+    K.models.image_v1.level_sizes(SimpleNamespace(depths=model_config['depths']), *model_config['input_size'])
+
+
 def main(argv=None):
     args = parse_args(argv)
 
@@ -141,9 +165,7 @@ def main(argv=None):
     if augment_prob > 0 and not args.device_augment:
         raise NotImplementedError('augment_prob > 0: KarrasAugmentationPipeline (scikit-image warps) is not implemented; set augment_prob to 0, '
                                   'or pass --device-augment to augment each batch on the device (K.augmentation)')
-    if model_config['type'] == 'image_v1':
-        raise NotImplementedError('model type image_v1: this command line does not train the U-Net yet; Denoiser.loss(...).backward() with '
-                                  'model.param_groups() and K.optim.AdamW trains it in a Python loop (in model.eval(): no Dropout2d yet)')
+    check_model_config(config)
     if opt_config['type'] != 'adamw':
         raise NotImplementedError(f'optimizer type {opt_config["type"]!r}: only adamw runs on the fused HIP step')
     check_dataset_config(config)
@@ -163,7 +185,9 @@ def main(argv=None):
     elapsed = 0.0
 
     inner_model = K.config.make_model(config)
-    check_dataset_config(config, inner_model.num_classes)
+    unet = model_config['type'] == 'image_v1'
+    takes_aug_cond = not unet or model_config['augment_wrapper']        # the transformer, or the U-Net in its augmentation wrapper
+    check_dataset_config(config, 0 if unet else inner_model.num_classes)          # the U-Net has no class-embedding table
     inner_model_ema = deepcopy(inner_model)
     print(f'Parameters: {K.utils.n_params(inner_model):,}')
     inner_model, inner_model_ema = inner_model.to(device), inner_model_ema.to(device)
@@ -171,8 +195,13 @@ def main(argv=None):
         inner_model.enable_dropout()
     if args.wgrad_bf16:                              # the trained model only: the EMA copy never takes gradients
         inner_model.set_wgrad_arithmetic('bf16')
-        print('Mixed precision bf16: the weight-gradient GEMMs round their operands to bf16 (fp32 accumulation); the forward pass, the '
-              'loss, the data-gradient GEMMs, the attention rules, the optimizer and the EMA stay fp32', flush=True)
+        if unet:
+            print('Mixed precision bf16: the weight-gradient convolutions and GEMMs round their operands to bf16 (fp32 accumulation); the '
+                  'forward pass, the loss, the data-gradient convolutions, AdaGN, the bias gradients, the attention rules, the optimizer and '
+                  'the EMA stay fp32', flush=True)
+        else:
+            print('Mixed precision bf16: the weight-gradient GEMMs round their operands to bf16 (fp32 accumulation); the forward pass, the '
+                  'loss, the data-gradient GEMMs, the attention rules, the optimizer and the EMA stay fp32', flush=True)
 
     lr = opt_config['lr'] if args.lr is None else args.lr
     opt = K.optim.AdamW(inner_model.param_groups(lr), lr=lr, betas=tuple(opt_config['betas']), eps=opt_config['eps'],
@@ -346,10 +375,12 @@ def main(argv=None):
                     reals, _, aug_cond = aug.batch(reals)
                 else:
                     aug_cond = reals.new_zeros([reals.shape[0], 9])
+                if takes_aug_cond:
+                    extra_args['aug_cond'] = aug_cond
                 noise = torch.randn_like(reals)
                 with K.utils.enable_stratified(step % accum, accum):
                     sigma = sample_density([reals.shape[0]], device=device)
-                losses = model.loss(reals, noise, sigma, aug_cond=aug_cond, **extra_args)
+                losses = model.loss(reals, noise, sigma, **extra_args)
                 loss = losses.mean().item()
                 losses_since_last_print.append(loss)
                 (losses.mean() / accum).backward()
