@@ -3,10 +3,14 @@
 
 Two models: the CIFAR-shaped one (depths [2, 4, 4], channels [128, 256, 512], 3 x 32 x 32, batch 64) and the MNIST-shaped one (channels
 [128, 128, 256], 1 x 28 x 28, batch 4), both with the augment wrapper and synthetic weights.  Per model: 10 warm-up forwards of each side, then 7
-samples of each, alternating, timed with HIP events; reported as median [min, max] in ms.  The torch side is tests/unet_ref.py's functional
-forward on the device (torch's conv / group-norm / SDPA kernels, depthwise resampling): the yardstick, not the code under test.
+samples of each, alternating, timed with HIP events; reported as median [min, max] in ms.  Three sides: the HIP forward (``hip_ms``, the
+fp32-grade split-bf16 x 3 convolutions), the HIP forward after ``set_conv_arithmetic("bf16")`` on a second model object with the same weights
+(``hip_bf16_ms``), and the torch side, tests/unet_ref.py's functional forward on the device (torch's conv / group-norm / SDPA kernels, depthwise
+resampling): the yardstick, not the code under test.  After the timed samples one more forward of each HIP arithmetic runs under the library's
+per-launch events, and the line carries the time per kernel name.
 
-``--profile`` instead runs 3 warm-up + 5 HIP forwards of ONE model and nothing else, for a kernel trace of its own:
+``--profile`` instead runs 3 warm-up + 5 HIP forwards of ONE model and nothing else (``--arithmetic bf16``: in the bf16 mode), for a kernel trace
+of its own:
     rocprofv3 --kernel-trace --stats -d <dir> -- python benchmarks/unet_bench.py --profile cifar
 ``--dual`` instead times the dual (primal + tangent) pass ``forward_jvp`` of ``log_likelihood`` at batch B against the forward at batch B and
 the forward at batch 2 B (the dual pass stacks the tangent behind the primal: 2 B samples in every buffer), same warm-up and sampling.
@@ -266,6 +270,7 @@ def train_bench(K, ur, name, model, sd, x, sigma, aug, B, H, W):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", choices=sorted(MODELS))
+    ap.add_argument("--arithmetic", choices=["bf16"], default=None, help="with --profile: set_conv_arithmetic('bf16') on the profiled model")
     ap.add_argument("--models", nargs="*", default=["cifar", "mnist"])
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--dual", action="store_true")
@@ -306,6 +311,7 @@ def main():
             continue
         with torch.no_grad():
             if args.profile:
+                model.set_conv_arithmetic(args.arithmetic)
                 for _ in range(8):
                     hip()
                 torch.cuda.synchronize()
@@ -351,21 +357,41 @@ def main():
                 continue
             sd_dev = ur.prepare(sd, torch.float32, dev)
             ref = lambda: ur.forward(sd_dev, x, sigma, aug_cond=aug, dtype=torch.float32, device=dev, grouped_resample=True, prepared=True)
+            # the third side: a second model object with the same weights after set_conv_arithmetic("bf16") (a change of the setting drops the
+            # plans, so the two arithmetics alternate on two objects)
+            model_b = K.config.make_model(cfg).eval().requires_grad_(False)
+            model_b.load_state_dict(sd)
+            model_b = model_b.to(dev).set_conv_arithmetic("bf16")
+            hip_b = lambda: model_b(x, sigma, aug_cond=aug)
             for _ in range(10):
                 hip()
+                hip_b()
                 if not args.no_torch:
                     ref()
             torch.cuda.synchronize()
-            t_hip, t_ref = [], []
+            t_hip, t_b16, t_ref = [], [], []
             for _ in range(7):
                 t_hip.append(timed(hip))
+                t_b16.append(timed(hip_b))
                 if not args.no_torch:
                     t_ref.append(timed(ref))
             err = None if args.no_torch else ((hip() - ref()).abs().max() / ref().abs().max()).item()
+            err_b = ((hip_b() - hip()).abs().max() / hip().abs().max()).item()
+            # one more forward of each arithmetic under the library's per-launch events: where the time goes
+            kernels = {}
+            K._native.prof_enable(True)
+            for key, fn in (("hip_kernel_ms", hip), ("hip_bf16_kernel_ms", hip_b)):
+                K._native.lib().kd_prof_reset()
+                fn()
+                torch.cuda.synchronize()
+                kernels[key] = kernel_ms()
+            K._native.prof_enable(False)
         flops = conv_flops(model, B, H, W)
         line = {"model": name, "batch": B, "hip_ms": [statistics.median(t_hip), min(t_hip), max(t_hip)],
+                "hip_bf16_ms": [statistics.median(t_b16), min(t_b16), max(t_b16)],
                 "torch_fp32_ms": None if args.no_torch else [statistics.median(t_ref), min(t_ref), max(t_ref)],
-                "hip_vs_torch_rel_diff": err, "conv_gflop_per_forward": flops / 1e9, "launches_per_forward": len(model.inner_model._plan(B, H, W, x.device).calls) + 6}
+                "hip_vs_torch_rel_diff": err, "hip_bf16_vs_hip_rel_diff": err_b, "conv_gflop_per_forward": flops / 1e9,
+                "launches_per_forward": len(model.inner_model._plan(B, H, W, x.device).calls) + 6, **kernels}
         print(json.dumps(line), flush=True)
 
 

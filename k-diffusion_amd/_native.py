@@ -15,6 +15,7 @@ GRAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_g
 TRAIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_train.h")
 DROP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_drop.h")
 MIXED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_mixed.h")
+UNET_BF16_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kdiff_unet_bf16.h")
 
 
 class NativeLibraryError(RuntimeError):
@@ -73,6 +74,16 @@ except OSError as e:
 if _mixed.structs or _mixed.constants or set(_mixed.signatures) & (set(SIGNATURES) | set(GRAD_SIGNATURES) | set(TRAIN_SIGNATURES) | set(DROP_SIGNATURES)):
     raise HeaderError(f"{MIXED_HEADER_PATH}: prototypes of entry points the other four headers do not declare, and nothing else")
 MIXED_SIGNATURES, MIXED_RESTYPES = _mixed.signatures, _mixed.restypes
+# ... and the bf16 form of its sampling forward's convolution (csrc/conv_bf16.hip): a sixth header, a sixth table
+try:
+    with open(UNET_BF16_HEADER_PATH) as _header:
+        _unet_bf16 = parse(_header.read())
+except OSError as e:
+    raise NativeLibraryError(f"{UNET_BF16_HEADER_PATH}: the C ABI header the package binds from cannot be read ({e})") from e
+if _unet_bf16.structs or _unet_bf16.constants or set(_unet_bf16.signatures) & (set(SIGNATURES) | set(GRAD_SIGNATURES) | set(TRAIN_SIGNATURES)
+                                                                               | set(DROP_SIGNATURES) | set(MIXED_SIGNATURES)):
+    raise HeaderError(f"{UNET_BF16_HEADER_PATH}: prototypes of entry points the other five headers do not declare, and nothing else")
+UNET_BF16_SIGNATURES, UNET_BF16_RESTYPES = _unet_bf16.signatures, _unet_bf16.restypes
 _i, _f = C.c_int, C.c_float                  # the kinds encode_call tells apart (the parser hands out these very objects)
 
 # PREC_FP8 is a mode of the NETWORK, not a KdGemm.precision value: the bf16 mode with the AdaRMSNorm -> wide projections of the K = 256 / 512
@@ -153,7 +164,8 @@ def lib():
                 "There is no CPU / PyTorch fallback for the sampling hot path.")
         handle = C.CDLL(LIB_PATH)
         for signatures, restypes in ((SIGNATURES, RESTYPES), (GRAD_SIGNATURES, GRAD_RESTYPES), (TRAIN_SIGNATURES, TRAIN_RESTYPES),
-                                     (DROP_SIGNATURES, DROP_RESTYPES), (MIXED_SIGNATURES, MIXED_RESTYPES)):
+                                     (DROP_SIGNATURES, DROP_RESTYPES), (MIXED_SIGNATURES, MIXED_RESTYPES),
+                                     (UNET_BF16_SIGNATURES, UNET_BF16_RESTYPES)):
             for name, argtypes in signatures.items():
                 try:
                     fn = getattr(handle, name)

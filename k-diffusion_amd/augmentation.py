@@ -119,5 +119,10 @@ class KarrasAugmentWrapper(nn.Module):
         self.inner_model.set_wgrad_arithmetic(arithmetic)
         return self
 
+    def set_conv_arithmetic(self, arithmetic=None):
+        """The inner model's ``set_conv_arithmetic`` (opt-in bf16 convolutions of the sampling forward); returns this wrapper."""
+        self.inner_model.set_conv_arithmetic(arithmetic)
+        return self
+
     def _dropout_rates(self):
         return self.inner_model._dropout_rates()

@@ -5,7 +5,8 @@ The module tree below exists to carry the reference's parameters under the refer
 so a k-diffusion checkpoint loads as it is -- and no sub-module's ``forward`` is ever called.  The model's forward is a fixed list of
 kernel launches over fp32 NHWC token buffers ``[B H W, C]``, built once per (batch, height, width):
 
-* a 3 x 3 / 1 x 1 convolution is one ``kd_conv2d_x3`` launch (bias, residual and the output's row stride in its epilogue);
+* a 3 x 3 / 1 x 1 convolution is one ``kd_conv2d_x3`` launch (bias, residual and the output's row stride in its epilogue) -- after
+  ``set_conv_arithmetic("bf16")`` one ``kd_conv2d_bf16`` launch (csrc/conv_bf16.hip: bf16 operands, fp32 accumulation), in this list only;
 * AdaGN (+ the GELU behind it) is a statistics pass and an apply pass; the (weight, bias) pairs of ALL AdaGN mappers come from one
   ``kd_cond_mlp_f32`` launch over the mappers' concatenated weight;
 * ``torch.cat([x, skip], 1)`` is two column ranges of one buffer which their producers write through the row stride;
@@ -30,7 +31,7 @@ kernel launches over fp32 NHWC token buffers ``[B H W, C]``, built once per (bat
 Scope: the forward pass, its forward-mode derivative, its reverse-mode derivative w.r.t. the input (explicit methods: ``forward_jvp``,
 ``forward_vjp``) and the parameter gradients of the training loss (``loss_forward``; sigma and the conditioning get no gradient anywhere) in
 fp32-grade (split-bf16x3) arithmetic whatever ``KDIFF_GEMM`` says (the weight-gradient products in bf16 after
-``set_wgrad_arithmetic("bf16")``), ``patch_size == 1``, ``skip_stages == 0``, no variance output, no cross
+``set_wgrad_arithmetic("bf16")``, the sampling forward's convolution products in bf16 after ``set_conv_arithmetic("bf16")``), ``patch_size == 1``, ``skip_stages == 0``, no variance output, no cross
 attention, no ``unet_cond``, dropout in ``loss_forward`` only and only after ``enable_dropout()`` (otherwise training mode with
 ``dropout_rate > 0`` is refused; ``model.eval()`` is always the dropout-free objective), channels that are multiples of 64, even H and W at
 every downsample.  Anything else is refused in the constructor; the sampling passes (``forward``, ``forward_jvp``, ``forward_vjp``) raise
@@ -229,9 +230,12 @@ class _Plan:
             emit(partial(uo.groupnorm_stats, x, B, norm.num_groups, norm.eps, out=stats))
             emit(partial(uo.adagn_apply, x, stats, wb, gelu=gelu, out=out))
 
+        # set_conv_arithmetic("bf16"): every convolution of the SAMPLING list on kd_conv2d_bf16; the dual list keeps the fp32-grade kernel
+        arithmetic = {"bf16": True} if model.conv_arithmetic == "bf16" and not dual else {}
+
         def conv(x, weight, hw, bias=None, residual=None, out=None, packed=None):
             emit(partial(uo.conv2d, x, weight, S, hw[0], hw[1], bias=bias, residual=residual, out=out,
-                         packed=uo.pack_conv(weight) if packed is None else packed, bias_batch=None if bias is None else bias_batch))
+                         packed=uo.pack_conv(weight) if packed is None else packed, bias_batch=None if bias is None else bias_batch, **arithmetic))
 
         def res_block(layer, x, y, hw):
             rows = x.shape[0]
@@ -399,6 +403,7 @@ class ImageDenoiserModelV1(nn.Module):
         self._vjp_cache, self._vjp_fingerprint = weights.PlanCache(), None       # forward_vjp's weight-derived tensors (models/unet_vjp.py)
         self._dropout_on, self._dropout_gen = False, None                        # enable_dropout(): not part of the state_dict
         self.wgrad_arithmetic = None                                             # set_wgrad_arithmetic(): not part of the state_dict
+        self.conv_arithmetic = None                                              # set_conv_arithmetic(): not part of the state_dict
 
     def param_groups(self, base_lr=2e-4):
         """image_v1.py:117-133: the weights of ``mapping`` and ``u_net`` decay, everything else does not."""
@@ -442,6 +447,22 @@ class ImageDenoiserModelV1(nn.Module):
         if arithmetic not in (None, "bf16"):
             raise ValueError(f"ImageDenoiserModelV1.set_wgrad_arithmetic: {arithmetic!r} (None or 'bf16')")
         self.wgrad_arithmetic = arithmetic
+        return self
+
+    def set_conv_arithmetic(self, arithmetic=None):
+        """Opt in to bf16 convolutions in the sampling forward.  ``None`` (the default): split-bf16 x 3, the family's fp32-grade arithmetic.
+        ``"bf16"``: every convolution of the residual and attention blocks in ``forward`` / ``forward_preconditioned`` rounds its activations
+        once to bf16 while staging them, takes the bf16 rounding of its weights and accumulates in fp32, one MFMA per product
+        (``kd_conv2d_bf16``, include/kdiff_unet_bf16.h): a ``Conv2d`` of the reference under ``torch.autocast(bfloat16)``.  Only those products
+        move: activations stay fp32 in memory, and ``proj_in`` / ``proj_out`` with the preconditioning, AdaGN, the mappers, resampling and
+        attention keep their arithmetic -- as do ``forward_jvp`` / ``log_likelihood``, ``forward_vjp`` and ``loss_forward`` with its
+        backward, whatever the setting.  A change drops the cached launch plans.  The setting is not part of the state_dict.  Returns the
+        model."""
+        if arithmetic not in (None, "bf16"):
+            raise ValueError(f"ImageDenoiserModelV1.set_conv_arithmetic: {arithmetic!r} (None or 'bf16')")
+        if arithmetic != self.conv_arithmetic:
+            self.conv_arithmetic = arithmetic
+            self._plan_cache.drop_all()
         return self
 
     def _dropout_rates(self):

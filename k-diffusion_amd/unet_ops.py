@@ -1,8 +1,9 @@
 """Tensor-level wrappers over the C ABI of the image_v1 U-Net kernels (csrc/conv_x3.hip, csrc/unet_f32.hip; contracts: include/kdiff_hip.h)
 and of their reverse rules (csrc/unet_vjp_f32.hip; contracts: include/kdiff_unet_grad.h) and parameter-gradient rules (csrc/conv_wgrad_x3.hip,
 csrc/unet_train_f32.hip; contracts: include/kdiff_unet_train.h) and dropout kernels (csrc/unet_drop_f32.hip and one entry point each of
-csrc/conv_x3.hip and csrc/vjp_f32.hip; contracts: include/kdiff_unet_drop.h) -- the module's counterpart of ``ops``, as ``augmentation`` and
-``data`` have theirs.
+csrc/conv_x3.hip and csrc/vjp_f32.hip; contracts: include/kdiff_unet_drop.h) and of the bf16 forms of the convolution and of its weight gradient
+(csrc/conv_bf16.hip, csrc/conv_wgrad_bf16.hip; contracts: include/kdiff_unet_bf16.h, include/kdiff_unet_mixed.h) -- the module's counterpart of
+``ops``, as ``augmentation`` and ``data`` have theirs.
 
 Activations are fp32 NHWC, token-major: a 2-D tensor ``[B * H * W, C]`` whose row stride may exceed C (a column range of a wider buffer:
 ``buf[:, :C]`` and ``buf[:, C:]`` are the two halves of a skip concatenation, written in place by their producers).  Column 0 of such a view
@@ -54,12 +55,17 @@ def pack_conv(weight, cache=True):
     return _packed.get(weight, None, None, build, cache=cache)
 
 
-def conv2d(x, weight, B, H, W, bias=None, residual=None, out=None, packed=None, bias_batch=None, chan_scale=None):
+def conv2d(x, weight, B, H, W, bias=None, residual=None, out=None, packed=None, bias_batch=None, chan_scale=None, bf16=False):
     """conv2d(x, weight, padding=ks // 2) + bias + residual on tokens x [B*H*W, C_in] -> [B*H*W, C_out] (``kd_conv2d_x3``), ks 1 or 3.
     ``out`` must not overlap x.  With ``bias_batch`` only the samples b < bias_batch get the bias (``kd_conv2d_x3_stacked``: a dual pass's
     batch is [primal | tangent], and the tangent of conv(x) + bias has no bias).  With ``chan_scale`` [B, C_out] (a site's column range of
     ``chan_mask``'s table) the channel dropout of the training loss rides in the epilogue: (conv + bias) * chan_scale[b] + residual
-    (``kd_conv2d_x3_drop``)."""
+    (``kd_conv2d_x3_drop``).  ``bf16``: activations and weights rounded once to bf16, one bf16 MFMA per product with fp32 accumulation
+    (``kd_conv2d_bf16``, include/kdiff_unet_bf16.h; the same packed image) -- the same contract otherwise, for the sampling forward alone: not
+    together with ``bias_batch`` or ``chan_scale``."""
+    if bf16 and (bias_batch is not None or chan_scale is not None):
+        raise ValueError(f"conv2d: bf16 excludes {'bias_batch' if bias_batch is not None else 'chan_scale'}: the dual pass (bias_batch) and the "
+                         "training loss (chan_scale) keep the fp32-grade arithmetic")
     c_out, c_in, ks, _ = weight.shape
     ldx = _rows(x, "x", c_in)
     _tokens(x, B, H, W, "conv2d")
@@ -70,7 +76,9 @@ def conv2d(x, weight, B, H, W, bias=None, residual=None, out=None, packed=None, 
         raise ValueError("conv2d: out and residual have the rows of x")
     packed = pack_conv(weight) if packed is None else packed
     args = (_p(x), ldx, _p(packed), _p(None if bias is None else _chk(bias, "bias")), _p(residual), ldr, _p(out), ldy, B, H, W, c_in, c_out, ks)
-    if chan_scale is not None:
+    if bf16:
+        nat.check(nat.lib().kd_conv2d_bf16(*args, _stream()), "kd_conv2d_bf16")
+    elif chan_scale is not None:
         if bias_batch is not None:
             raise ValueError("conv2d: chan_scale (the training loss's dropout) and bias_batch (the dual pass) exclude each other")
         cs = _rows(chan_scale, "chan_scale", c_out)

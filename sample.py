@@ -23,6 +23,9 @@ sample.py:59-60, and therefore cannot run its own class-conditional configs):
   --gather-uint8       8-bit conversion on the GPU before the all-gather of finished images (same PNG bytes, 4x less xGMI traffic).
                        The DEFAULT whenever there is a gather (more than one process) and PNG files are written -- the writer needs
                        nothing else; --gather-fp32 keeps the reference's fp32 gather (main() then returns fp32 images)
+  --unet-arithmetic bf16  image_v1 configs only: bf16 convolution products in the sampling forward (model.set_conv_arithmetic('bf16'):
+                       activations and weights rounded once to bf16, fp32 accumulation; everything else keeps its arithmetic).  For an
+                       image_transformer_v2 config the arithmetic mode is the environment variable KDIFF_GEMM
 With --seed the stochastic samplers are index-addressed too: one Brownian tree per global image index for the SDE samplers,
 a per-(index, call) stream for the ancestral ones (the reference draws both from rank-local global RNG state).
 """
@@ -59,7 +62,15 @@ def parse(argv=None):
     p.add_argument('--gather-uint8', action='store_true',
                    help='convert finished images to uint8 on the GPU before the all-gather (what the PNG writer needs; 4x less xGMI traffic)')
     p.add_argument('--gather-fp32', action='store_true', help='all-gather the finished images as fp32 even when only PNG files are wanted')
+    p.add_argument('--unet-arithmetic', choices=['bf16'], default=None,
+                   help="image_v1 configs: model.set_conv_arithmetic -- bf16 convolution products in the sampling forward (default: the fp32-grade "
+                        "split-bf16 x 3 convolutions)")
     args = p.parse_args(argv)
+    if args.unet_arithmetic is not None and (args.config or args.checkpoint):
+        model_type = K.config.load_config(args.config if args.config else args.checkpoint)['model']['type']
+        if model_type != 'image_v1':
+            p.error(f'--unet-arithmetic {args.unet_arithmetic} is the image_v1 U-Net\'s convolution arithmetic; this config is {model_type}, '
+                    'whose arithmetic mode is the environment variable KDIFF_GEMM (KDIFF_GEMM=bf16)')
     if args.gather_uint8 and args.gather_fp32:
         p.error('--gather-uint8 and --gather-fp32 exclude each other')
     if args.checkpoint is None and not args.random_weights:
@@ -167,6 +178,8 @@ def main(argv=None):
     else:
         inner_model.load_state_dict(K.checkpoint.load_inference_checkpoint(args.checkpoint))
     inner_model = inner_model.to(device)
+    if args.unet_arithmetic is not None:
+        inner_model.set_conv_arithmetic(args.unet_arithmetic)
     accelerator.print('Parameters:', K.utils.n_params(inner_model))
     model = K.Denoiser(inner_model, sigma_data=model_config['sigma_data'])
 
